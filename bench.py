@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- cine slices/sec of the reconstruction hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step and the run's set-up);
+`--dump-outputs DIR` also writes what the last timed step computed (DIR/reconstruction.npy, float32).  Everything else the
+line can carry -- the repeat / h2d regions, one-slice latency, the sustained region, per-family kernel times and rooflines,
+the CPU baseline and oracle parity, the other configurations and the training step -- runs only with `--full`.
 
 One "step" = one full forward of a BASELINE.json configuration on one synthetic cine slice already resident in HBM.
 Default (and the driver's line) is configs[1]: XF-VarNet, 6 cascades, 15 coils x 15 frames x 200x200, R=4 (sens-map network
@@ -146,10 +151,15 @@ def parse():
                          "largest count in 6..12 that divides --steps (whole rounds of streams: no half-empty last round), else 8")
     ap.add_argument("--batch", type=int, default=1,
                     help="slices per step: one forward over a (batch, t, coil, h, w, 2) k-space batch, the reference's batch axis")
-    ap.add_argument("--repeats", type=int, default=4, help="extra timed K-step regions after the contract one (median reported beside value)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-forwards", type=int, default=3)
-    ap.add_argument("--cpu-threads", type=str, default="sweep", help="'sweep' (8,16,32,64,physical) or a number")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeat / h2d regions, latency, sustained region, kernel families and rooflines, "
+                         "CPU baseline and parity, other configurations and the training step (off: set up, warm up, time K steps, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's reconstruction as DIR/reconstruction.npy (float32, <= 64 MB)")
+    ap.add_argument("--repeats", type=int, default=4, help="--full: extra timed K-step regions after the contract one (median reported beside value)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity checks it feeds")
+    ap.add_argument("--cpu-forwards", type=int, default=3, help="--full: timed forwards of the CPU baseline")
+    ap.add_argument("--cpu-threads", type=str, default="sweep", help="--full: 'sweep' (8,16,32,64,physical) or a number")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise RCCL (backend nccl), the device barrier and the all-gather of the volume assembly even at --gpus 1 "
                          "(start under `python -m torch.distributed.run --nproc-per-node=1`, or alone: rank 0 of a world of 1)")
@@ -158,9 +168,9 @@ def parse():
     ap.add_argument("--conv-plane-mask", type=int, default=-1, help="A/B: cine_set_conv_plane(mask) of the bench's thread: bit 0 the plane-wide 3x3 convs, bit 1 the transpose convs, bit 2 the wide-plane / volume kernel "
                          "(conv_wide_kernel: cfg 4, cfg 5, the sensitivity net), bit 4 SET = the general weight-gradient kernel; 7 = all lean kernels (the default)")
     ap.add_argument("--pin-numa", action="store_true", help="pin this process to its GPU's NUMA node at --gpus 1 too (always done for N > 1)")
-    ap.add_argument("--sustained-seconds", type=float, default=60.0, help="length of the extra sustained region (0 = skip)")
+    ap.add_argument("--sustained-seconds", type=float, default=60.0, help="--full: length of the extra sustained region (0 = skip)")
     ap.add_argument("--latency-only", action="store_true", help="diagnostics: print latency_modes_ms of --config (one slice alone, every launch form) and exit")
-    ap.add_argument("--headline-only", action="store_true", help="skip the latency / sustained regions and the other_configs / train_step extras of the default 1-GPU line")
+    ap.add_argument("--headline-only", action="store_true", help="--full: skip the latency / sustained regions and the other_configs / train_step extras of the default 1-GPU line")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="TEST ONLY (tests/test_distributed_cpu.py): run the launcher, sharding, timed region and all-gather on "
                          "gloo/CPU with a stand-in for the forward; the line is marked invalid and measures nothing")
@@ -359,6 +369,23 @@ def timed_steps(run, nsteps, batch, outs, world, sync, barrier, device):
     return dt, volume, per_rank
 
 
+DUMP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32.  An array larger than DUMP_BYTES is replaced by a fixed
+    sample of its elements (seed 0, flat indices in increasing order), so that two builds run with the same arguments compare
+    element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.nbytes > DUMP_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_BYTES // 4, replace=False))
+            a = np.ascontiguousarray(a.reshape(-1)[idx])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def leave_together(use_dist, barrier):
     """The end of every rank's main(): rank 0 still has host-side work after the timed region (kernel families, the line itself); the other
     ranks wait for it at ONE last barrier, so that no rank tears its communicator down while another could still enter a collective."""
@@ -421,12 +448,20 @@ def bench_streams(n):
     return _STREAM_POOL[:n]
 
 
+def make_slices(cfg, seeds, shape=(FRAMES, COILS, H, W)):
+    """The synthetic cine slices of a configuration, one per seed, made one after another: synth.make_cine_slice draws its mask from
+    numpy's GLOBAL RNG (np.random.seed(seed), then np.random.choice, as the reference's subsample.py does), so calls on several
+    threads at once take each other's draws and the inputs -- and everything computed from them -- would change from run to run."""
+    from cine_hip import synth
+    t, c, h, w = shape
+    return [synth.make_cine_slice(t, c, h, w, accel=cfg["accel"], seed=sd, noise_std=cfg["noise"]) for sd in seeds]
+
+
 class Workload:
     """One BASELINE configuration set up on this rank's GPU: S different slices resident in HBM, the drop-in model, one hipGraph
     per slice (its own stream), and the timed region of the contract over them."""
 
     def __init__(self, cfg_id, args, world, rank, local, dev, steps, inflight=0):
-        from concurrent.futures import ThreadPoolExecutor
         from cine_hip import synth
         self.cfg = cfg = CONFIGS[cfg_id]()
         self.args, self.world, self.rank, self.local, self.dev, self.steps = args, world, rank, local, dev, steps
@@ -436,13 +471,11 @@ class Workload:
             S = next((c for c in range(12, 5, -1) if steps % c == 0), 8) if steps >= 6 else max(1, steps)
         self.S, self.B = S, max(1, args.batch)
         B = self.B
-        # S DIFFERENT slices per rank (x B on the batch axis): seeds rank * S * B + ...; the phantoms are host work (0.8 s each):
-        # a small thread pool per rank, with the intra-op threads divided among the ranks of the node
+        # S DIFFERENT slices per rank (x B on the batch axis): seeds rank * S * B + ..., with the intra-op threads divided among the
+        # ranks of the node
         nthr = torch.get_num_threads()
-        torch.set_num_threads(max(1, nthr // max(world, 1) // 4))
-        with ThreadPoolExecutor(max_workers=4) as pool:
-            flat = list(pool.map(lambda sd: synth.make_cine_slice(FRAMES, COILS, H, W, accel=cfg["accel"], seed=sd, noise_std=cfg["noise"]),
-                                 [(rank * S + i) * B + j for i in range(S) for j in range(B)]))
+        torch.set_num_threads(max(1, nthr // max(world, 1)))
+        flat = make_slices(cfg, [(rank * S + i) * B + j for i in range(S) for j in range(B)])
         torch.set_num_threads(nthr)
         self.exs = exs = [flat[i * B:(i + 1) * B] for i in range(S)]
         self.host_mk = [torch.cat([e["masked_kspace"] for e in row]).pin_memory() for row in exs]
@@ -992,6 +1025,28 @@ def main():
         torch.cuda.synchronize()
     dt = wl.timed(args.steps)                                         # THE timed region: exactly K steps
     contract_per_rank_s = list(wl.per_rank_s)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"reconstruction": wl.outs[(args.steps - 1) * B:args.steps * B]})    # the last timed step's output
+    rccl_ranks = dist.get_world_size() if dist.is_initialized() else 1
+    slices = world * args.steps * B
+    line = {
+        "metric": cfg["metric"], "value": slices / dt, "unit": "cine slices/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": cfg["name"] + f"; {B} slice(s) per step (k-space batch axis), seeded random-init weights, "
+                               f"{S} different slices per rank",
+                   "slices_per_step": B,
+                   "launch": ("hipGraph replay" if use_graph else "eager") + f", {S} independent steps in flight on {S} HIP streams, "
+                             f"GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}",
+                   "parallelism": f"slice-sharded x{world}, one all-gather for volume assembly"},
+        "rccl_ranks": rccl_ranks, "rccl_initialised": bool(dist.is_initialized()),
+        "timed_region_s": dt, "per_rank_timed_region_s": contract_per_rank_s, "cpu_affinity": AFFINITY, "full": args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            line["forwards_run"] = getattr(wl, "nforward", None)
+            print(json.dumps(line))
+        return leave_together(use_dist, lambda: dist.barrier(device_ids=[local]))
     extra = sorted(wl.timed(args.steps) for _ in range(max(0, args.repeats)))
     dt_h2d = min(wl.timed(args.steps, h2d=True) for _ in range(2))
     dt_h2d_inline = wl.timed(args.steps, h2d="inline")
@@ -1003,7 +1058,6 @@ def main():
             wl.mks[k % S].copy_(wl.host_mk[k % S], non_blocking=True)
     torch.cuda.synchronize()
     link_gbs = 2 * S * wl.host_mk[0].numel() * 4 / (time.perf_counter() - t0) / 1e9
-    rccl_ranks = dist.get_world_size() if dist.is_initialized() else 1
     # the single-GPU diagnostics (one slice alone, the 60-s sustained region) belong to the N = 1 line: on N ranks they would keep N GPUs
     # busy for a minute each after the contract's region.  --sustained-seconds X forces the sustained region at N > 1 too (X > 0 given explicitly).
     extras = not args.headline_only and (world == 1 or args.sustained_explicit)
@@ -1024,24 +1078,12 @@ def main():
     fam = profile_families(wl.forward)
     fam = {k: (v[0] / B, v[1]) for k, v in fam.items()}            # per slice
     fft_ms = fam["fft_col_pass"][0] + fam["fft_row_pass"][0]
-    slices = world * args.steps * B
     roofline = conv_roofline(wl, fam, dt, slices)
     tr, tr_src = pmc_families(args.config)
     if tr and "conv3x3_mfma" in tr:
         roofline["traffic"] = tr["conv3x3_mfma"]["hbm_MB_per_launch"] * 1e6
         roofline["traffic_unit"] = f"HBM bytes per launch (mean over the launches of a slice), PMC FETCH_SIZE x2 + WRITE_SIZE, {tr_src}"
-    line = {
-        "metric": cfg["metric"], "value": slices / dt, "unit": "cine slices/sec", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": cfg["name"] + f"; {B} slice(s) per step (k-space batch axis), seeded random-init weights, "
-                               f"{S} different slices per rank",
-                   "slices_per_step": B,
-                   "launch": ("hipGraph replay" if use_graph else "eager") + f", {S} independent steps in flight on {S} HIP streams, "
-                             f"GPU_MAX_HW_QUEUES={os.environ.get('GPU_MAX_HW_QUEUES')}",
-                   "parallelism": f"slice-sharded x{world}, one all-gather for volume assembly"},
-        "rccl_ranks": rccl_ranks, "rccl_initialised": bool(dist.is_initialized()),
-        "timed_region_s": dt, "per_rank_timed_region_s": contract_per_rank_s, "cpu_affinity": AFFINITY,
+    line.update({
         "latency_ms_one_slice": best_lat[0] if best_lat else lat_med, "latency_ms_one_slice_min": best_lat[1] if best_lat else lat_min,
         "latency_ms_one_slice_graph_one_stream": lat_med,
         "latency_note": ("one slice alone, nothing else in flight, host clock around enqueue + stream sync: what run_inference.py:53-61 times per slice "
@@ -1062,7 +1104,7 @@ def main():
                                "best of 2 regions; _inline = the copy on the slice's own stream in front of its replay (round 5's form)",
         "roofline": roofline,
         "kernel_ms_per_slice": {k: round(v[0], 4) for k, v in fam.items()},
-    }
+    })
     line["forwards_run"] = None        # filled in just before the line is printed
     if cfg["fft_bytes"]:
         roof_fft = {"bound": "hbm", "kernel": "cine::imgdc200_kernel + imgdc_sum_kernel (x6: sens_expand + FFT2 + DC + IFFT2 + sens_reduce on the "

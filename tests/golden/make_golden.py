@@ -877,7 +877,30 @@ def g_fft_smooth():
     save("fft_smooth", **a)
 
 
-GENERATORS = dict(xpdnet_grad_cfg3_linear=g_xpdnet_grad_cfg3_linear, rnn_grad_cfg5_linear=g_rnn_grad_cfg5_linear, varnet_grad_cfg2_linear=g_varnet_grad_cfg2_linear, cinenet_grad_cfg4_linear=g_cinenet_grad_cfg4_linear, xpdnet_grad_cfg3=g_xpdnet_grad_cfg3, cinenet_grad_cfg4=g_cinenet_grad_cfg4, rnn_grad_cfg5=g_rnn_grad_cfg5, rnn_grad=g_rnn_grad, xpdnet_grad=g_xpdnet_grad, cinenet_grad=g_cinenet_grad, lightning=g_lightning, varnet_grad=g_varnet_grad, varnet_grad_cfg2=g_varnet_grad_cfg2, rnn=g_rnn, xpdnet=g_xpdnet, cinenet=g_cinenet, ops=g_ops, unet=g_unet, varnet_block=g_varnet_block,
+def g_dropin():
+    """What tests/test_dropin_glue.py needs of the reference when no checkout is present: the reference's SSIMLoss
+    (utils/losses.py:25-58, its hard-wired .to('cuda') an identity on CPU) on a fixed pair, and the layout of the DEFAULT
+    VarNetModule's model (varnet_module.py:74-90 defaults) as a Lightning checkpoint names it: key -> [shape, the key it
+    aliases] (the 'varnet.' prefix; tensors registered under several names point at the first name)."""
+    import json
+    orig_to = torch.Tensor.to
+    torch.Tensor.to = lambda self, *a, **k: self if a and a[0] == "cuda" else orig_to(self, *a, **k)
+    try:
+        g = torch.Generator().manual_seed(0)
+        x, y = torch.rand(1, 1, 4, 40, 36, generator=g), torch.rand(1, 1, 4, 40, 36, generator=g)
+        loss = RU.SSIMLoss()(x, y, torch.tensor([1.0]))
+    finally:
+        torch.Tensor.to = orig_to
+    net = RM.VarNet(num_cascades=12, sens_chans=8, sens_pools=4, chans=18, pools=4, dynamic_type="XF", weight_sharing=False)
+    first, table = {}, {}
+    for k, v in net.state_dict().items():
+        canon = first.setdefault((v.data_ptr(), tuple(v.shape)), "varnet." + k)
+        table["varnet." + k] = [list(v.shape), canon]
+    save("dropin_glue", ssim_x=x, ssim_y=y, ssim_loss=np.float64(float(loss)),
+         ckpt_layout=np.frombuffer(json.dumps(table).encode(), dtype=np.uint8))
+
+
+GENERATORS = dict(dropin=g_dropin, xpdnet_grad_cfg3_linear=g_xpdnet_grad_cfg3_linear, rnn_grad_cfg5_linear=g_rnn_grad_cfg5_linear, varnet_grad_cfg2_linear=g_varnet_grad_cfg2_linear, cinenet_grad_cfg4_linear=g_cinenet_grad_cfg4_linear, xpdnet_grad_cfg3=g_xpdnet_grad_cfg3, cinenet_grad_cfg4=g_cinenet_grad_cfg4, rnn_grad_cfg5=g_rnn_grad_cfg5, rnn_grad=g_rnn_grad, xpdnet_grad=g_xpdnet_grad, cinenet_grad=g_cinenet_grad, lightning=g_lightning, varnet_grad=g_varnet_grad, varnet_grad_cfg2=g_varnet_grad_cfg2, rnn=g_rnn, xpdnet=g_xpdnet, cinenet=g_cinenet, ops=g_ops, unet=g_unet, varnet_block=g_varnet_block,
                   varnet_tiny=g_varnet_tiny, masks=g_masks, varnet_full=g_varnet_full,
                   varnet_cfg1=g_varnet_cfg1, xpdnet_cfg3=g_xpdnet_cfg3,
                   cinenet_cfg4=g_cinenet_cfg4, rnn_cfg5=g_rnn_cfg5, metrics=g_metrics, frontend=g_frontend, fft_smooth=g_fft_smooth)

@@ -207,8 +207,10 @@ def _fake_sysfs(root, gpus, local_cpulists=None):
         (d / "cpulist").write_text(cl + "\n")
 
 
-def test_rank_numa_affinity_from_sysfs(tmp_path):
+def test_rank_numa_affinity_from_sysfs(tmp_path, monkeypatch):
     """bench.py pins a rank to its GPU's NUMA node from sysfs alone (no GPU call): KFD order -> PCI function -> numa_node -> cpulist."""
+    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):   # the fake sysfs's GPUs, not this machine's device mask
+        monkeypatch.delenv(var, raising=False)
     sys.path.insert(0, ROOT)
     import bench
     _fake_sysfs(tmp_path, [(0x05, 0), (0x85, 1), (0xc5, -1)])
@@ -232,9 +234,11 @@ def test_rank_numa_affinity_from_sysfs(tmp_path):
         assert after == before and not info["applied"] and info["why"]
 
 
-def test_rank_numa_affinity_falls_back_to_local_cpulist(tmp_path):
+def test_rank_numa_affinity_falls_back_to_local_cpulist(tmp_path, monkeypatch):
     """A box whose firmware does not name the GPU's node (numa_node = -1, what the driver's GPU boxes report: `cpu_affinity.applied`
     was false there): the PCI function's local_cpulist gives the CPUs next to the GPU, marked as node -1."""
+    for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):   # the fake sysfs's GPUs, not this machine's device mask
+        monkeypatch.delenv(var, raising=False)
     sys.path.insert(0, ROOT)
     import bench
     _fake_sysfs(tmp_path, [(0x05, -1), (0x85, -1)], local_cpulists=["0-3", ""])
@@ -252,3 +256,18 @@ def test_rank_numa_affinity_falls_back_to_local_cpulist(tmp_path):
         assert after == want and info["applied"] and info["numa_node"] == -1 and "local_cpulist" in info["source"]
     else:
         assert after == before and not info["applied"] and info["why"]
+
+
+def test_bench_slices_are_the_same_every_run():
+    """bench.py's inputs depend on the arguments alone: every slice equals what its seed makes on its own (make_cine_slice draws
+    its mask from numpy's global RNG, so slices made on several threads at once would take each other's draws)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from cine_hip import synth
+    cfg = bench.CONFIGS[5]()                                   # R = 8: a sparse, seed-dependent mask
+    seeds = list(range(40, 72))
+    for _ in range(2):
+        got = bench.make_slices(cfg, seeds, shape=(6, 2, 160, 32))
+        for sd, ex in zip(seeds, got):
+            want = synth.make_cine_slice(6, 2, 160, 32, accel=cfg["accel"], seed=sd, noise_std=cfg["noise"])
+            assert torch.equal(ex["mask"], want["mask"]) and torch.equal(ex["masked_kspace"], want["masked_kspace"]), sd

@@ -1,8 +1,9 @@
 """Drop-in boundary against the reference's own callers.
 
-Build-container only: needs the reference checkout (CINE_REFERENCE_ROOT or /root/reference), which never travels to the
-GPU box -- skipped there.  Each case runs in a fresh interpreter with exactly the path order INTEGRATION.md section 1
-prescribes (this build's package first, the reference checkout second) and stubs for the third-party packages the image
+The cases that run the reference's own modules (pl_modules, data) need its checkout (CINE_REFERENCE_ROOT or /root/reference)
+and skip without it; the SSIM parity and the layout of a reference-made checkpoint come from tests/golden/dropin_glue.npz
+(made by tests/golden/make_golden.py from the reference) and run anywhere.  Each reference case runs in a fresh interpreter
+with exactly the path order INTEGRATION.md section 1 prescribes (this build's package first, the reference checkout second) and stubs for the third-party packages the image
 lacks (pytorch_lightning, torchmetrics, bart, h5py, skimage): import-time stand-ins only, none of them is on the path
 under test.  The reference-made checkpoint is produced by a second interpreter that sees ONLY the reference.
 """
@@ -16,8 +17,8 @@ import pytest
 from conftest import PKG, ROOT
 
 REF = os.environ.get("CINE_REFERENCE_ROOT", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "reconstruction")),
-                                reason="reference checkout not present (build container only)")
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "reconstruction")),
+                                     reason="reference checkout not present (build container only)")
 
 STUBS = textwrap.dedent("""
     import sys, types, torch
@@ -49,6 +50,7 @@ def _run(code, pythonpath, extra_env=None):
     return r.stdout
 
 
+@needs_reference
 def test_reference_import_lines_resolve_with_integration_path_order():
     """The import lines of pl_modules/varnet_module.py:4-6, data_module.py:15, mri_module.py:18-19 and run_inference.py."""
     out = _run("""
@@ -75,6 +77,7 @@ def test_reference_import_lines_resolve_with_integration_path_order():
     assert out.strip().endswith("ok")
 
 
+@needs_reference
 def test_varnet_module_constructs_on_the_build_and_loads_a_reference_checkpoint(tmp_path):
     ckpt = str(tmp_path / "ref_varnet_module_state.pt")
     # (1) reference only: a Lightning-style state dict of the DEFAULT VarNetModule (varnet_module.py:74-90), 'varnet.' prefix
@@ -116,6 +119,7 @@ def test_varnet_module_constructs_on_the_build_and_loads_a_reference_checkpoint(
     assert out.strip().endswith("ok")
 
 
+@needs_reference
 def test_cinenet_and_xpdnet_modules_construct_on_the_build():
     out = _run("""
         import os, pathlib
@@ -133,23 +137,37 @@ def test_cinenet_and_xpdnet_modules_construct_on_the_build():
     assert out.strip().endswith("ok")
 
 
-def test_ssim_loss_matches_reference_on_cpu(tmp_path):
-    """The build's SSIMLoss (device-agnostic) against the reference's (utils/losses.py:25-58, hard-wired .to('cuda'))."""
-    vec = str(tmp_path / "ssim_vec.pt")
-    _run(f"""
-        torch.Tensor.to = (lambda orig: (lambda self, *a, **k: self if a and a[0] == "cuda" else orig(self, *a, **k)))(torch.Tensor.to)
-        from reconstruction.utils.losses import SSIMLoss
-        import reconstruction.utils.losses as L
-        assert L.__file__.startswith({REF!r})
-        g = torch.Generator().manual_seed(0)
-        x, y = torch.rand(1, 1, 4, 40, 36, generator=g), torch.rand(1, 1, 4, 40, 36, generator=g)
-        torch.save({{"x": x, "y": y, "loss": SSIMLoss()(x, y, torch.tensor([1.0]))}}, {vec!r})
-    """, [REF])
-    out = _run(f"""
-        from reconstruction.utils import SSIMLoss
-        v = torch.load({vec!r})
-        got = SSIMLoss()(v["x"], v["y"], torch.tensor([1.0]))
-        assert abs(float(got) - float(v["loss"])) < 1e-6, (float(got), float(v["loss"]))
-        print("ok")
-    """, [PKG, REF], {"CINE_REFERENCE_ROOT": REF})
-    assert out.strip().endswith("ok")
+def test_varnet_default_checkpoint_layout_loads_on_the_build(golden):
+    """The build's DEFAULT VarNetModule model (varnet_module.py:74-90) against the reference's: the same 'varnet.' keys, shapes and
+    aliases (tensors registered under several names share storage), and a checkpoint of that layout loads strict=True."""
+    import json
+    import torch
+    from reconstruction.models import VarNet
+    g = golden("dropin_glue")
+    layout = json.loads(bytes(g["ckpt_layout"]).decode())
+    gen = torch.Generator().manual_seed(3)
+    sd = {}
+    for k, (shape, canon) in layout.items():
+        sd[k] = sd[canon] if canon != k else torch.randn(shape, generator=gen)
+    net = VarNet(num_cascades=12, sens_chans=8, sens_pools=4, chans=18, pools=4, dynamic_type="XF", weight_sharing=False)
+    own = {"varnet." + k: v for k, v in net.state_dict().items()}
+    assert set(own) == set(sd), (sorted(set(own) ^ set(sd))[:5])
+    assert all(tuple(own[k].shape) == tuple(v.shape) for k, v in sd.items())
+    net.load_state_dict({k[len("varnet."):]: v for k, v in sd.items()}, strict=True)
+    mine = net.state_dict()
+    for k, (_, canon) in layout.items():
+        assert torch.equal(mine[k[len("varnet."):]], sd[k])
+        if canon != k:                                   # an alias in the reference: one storage in the build as well
+            assert mine[k[len("varnet."):]].data_ptr() == mine[canon[len("varnet."):]].data_ptr(), k
+    k0 = "cascades.3.model.0.unet.conv.layers.0.weight"
+    assert mine[k0].data_ptr() == mine["model.0.unet.conv.layers.0.weight"].data_ptr()
+
+
+def test_ssim_loss_matches_reference_on_cpu(golden):
+    """The build's SSIMLoss (device-agnostic) against the reference's (utils/losses.py:25-58, hard-wired .to('cuda')) on the pair
+    of tests/golden/dropin_glue.npz and the loss the reference computed for it."""
+    import torch
+    from reconstruction.utils import SSIMLoss
+    g = golden("dropin_glue")
+    got = SSIMLoss()(torch.from_numpy(g["ssim_x"]), torch.from_numpy(g["ssim_y"]), torch.tensor([1.0]))
+    assert abs(float(got) - float(g["ssim_loss"])) < 1e-6, (float(got), float(g["ssim_loss"]))

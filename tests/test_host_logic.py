@@ -41,9 +41,9 @@ def test_argument_validation_without_gpu():
     assert L.cine_xfyf_ws_bytes(1, 15, 200, 200) == 15 * 200 * 200 * 8
 
 
-def test_fft_engine_host_check():
+def test_fft_engine_host_check(tmp_path):
     """Compile csrc/fft_core.h for the host and compare the 200-point engine with a direct DFT."""
-    exe = "/tmp/cine_fft_host_check"
+    exe = str(tmp_path / "cine_fft_host_check")
     src = os.path.join(ROOT, "tests", "host", "fft_host_check.cpp")
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(PKG, "csrc"), src, "-o", exe], check=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
@@ -68,8 +68,10 @@ def test_default_constructor_matches_reference_key_count():
     assert len(M.VarNet(6, 8, 3, 16, 3, "XF").state_dict()) == 291
 
 
-def test_no_cpu_fallback():
+def test_no_cpu_fallback(monkeypatch):
     """CPU tensors must fail loudly, not silently run somewhere else."""
+    # a machine without a GPU: where one is visible, CPU tensors are staged through it (reconstruction/utils/fftc.py _run)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     import reconstruction.models as M
     import reconstruction.utils as U
     from cine_hip._lib import CineHipError

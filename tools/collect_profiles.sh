@@ -22,7 +22,7 @@ find $O -name "*_kernel_trace.csv" -delete
 exit 0
 fi
 if [ "$PART" != others ]; then
-python3 bench.py --steps 30 --warmup 3 > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --steps 30 --warmup 3 > $O/bench.json 2> $O/bench.err
 cd /tmp
 # kernel traces of the default command in BOTH modes: the timed one (3 graphs in flight) and one slice in flight
 rocprofv3 --kernel-trace --stats -d $O/trace_inflight -o t --output-format csv -- python3 $R/bench.py --steps 12 --warmup 3 --no-cpu-baseline --repeats 0 --headline-only > $O/trace_inflight.log 2>&1
@@ -40,7 +40,7 @@ fi
 if [ "$PART" != main ]; then
 # the other BASELINE configurations: one bench line (CPU baseline bounded to 16 threads, one forward) and one trace each
 for c in 3 4 5; do
-  python3 bench.py --config $c --steps 12 --warmup 3 --cpu-forwards 1 --cpu-threads 16 > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err
+  python3 bench.py --full --config $c --steps 12 --warmup 3 --cpu-forwards 1 --cpu-threads 16 > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err
   cd /tmp
   rocprofv3 --kernel-trace --stats -d $O/trace_cfg$c -o t --output-format csv -- python3 $R/bench.py --config $c --steps 6 --warmup 2 --no-cpu-baseline --repeats 0 --inflight 1 --headline-only > $O/trace_cfg$c.log 2>&1
   for k in FETCH_SIZE WRITE_SIZE; do
