@@ -714,12 +714,14 @@ _zero_states = {}
 
 
 def _zero_state(c: int, h: int, w: int, like: torch.Tensor) -> torch.Tensor:
-    """A shared READ-ONLY (1, c, h, w) zero tensor per device (hid_init of the time sweeps, recurrent_varnet.py:236): no fill per step."""
+    """A shared READ-ONLY (1, c, h, w) zero tensor per device (hid_init of the time sweeps, recurrent_varnet.py:236): no fill per step.
+    The fill runs on the stream that asked first; the cached tensor is read from every stream, so that stream is synchronised once."""
     key = (like.device, c, h, w)
     z = _zero_states.get(key)
     if z is None:
         z = torch.zeros((1, c, h, w), device=like.device, dtype=torch.float32)
         if not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(like.device).synchronize()
             _zero_states[key] = z
     return z
 

@@ -86,6 +86,7 @@ def apply_conv_plane(mask: int) -> None:
 
 # ---- side streams: the caller-owned streams the branch / side-lane entry points fork onto --------------------------------------------
 _SIDE_STREAMS = {}
+_SIDE_STREAMS_LOCK = threading.Lock()     # threads that run forwards on streams of their own share the table
 import os as _os
 UNET_BRANCHES = int(_os.environ.get("CINE_UNET_BRANCHES", "2"))   # default number of concurrent branches of a 2-D U-Net pass (cine_unet2d_forward_branches), see
                                                                   # `branches`: 2 -- the reference's scripts run ONE slice at a time (run_inference.py:53-61, every
@@ -104,13 +105,14 @@ def side_streams(device: torch.device, count: int = 1):
     main stream, outside any capture -- concurrent slices on different main streams never share a side stream."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     key = (idx, torch.cuda.current_stream(idx).cuda_stream)
-    have = _SIDE_STREAMS.get(key)
-    if have is None:
-        have = _SIDE_STREAMS[key] = []
-    while len(have) < count:
-        _no_capture("a side stream")
-        have.append(_pick_concurrent_stream(idx, [torch.cuda.current_stream(idx)] + have))
-    return have[:count]
+    with _SIDE_STREAMS_LOCK:
+        have = _SIDE_STREAMS.get(key)
+        if have is None:
+            have = _SIDE_STREAMS[key] = []
+        while len(have) < count:
+            _no_capture("a side stream")
+            have.append(_pick_concurrent_stream(idx, [torch.cuda.current_stream(idx)] + have))
+        return have[:count]
 
 
 PROBE_SIDE_STREAMS = _os.environ.get("CINE_PROBE_SIDE_STREAMS", "1") == "1"      # (this binding) 0: take whatever stream torch hands out
@@ -176,12 +178,13 @@ def release_side_streams(main_streams=None) -> None:
     """Forget (and thereby destroy) the side streams that belong to the given main streams (raw handles), or all of them.  Streams are a
     finite resource in effect: once more are alive than the runtime has hardware queues (GPU_MAX_HW_QUEUES), a new stream shares a queue with
     an existing one, and a side stream that shares its main stream's queue serialises with it.  Call after the work on those streams is done."""
-    if main_streams is None:
-        _SIDE_STREAMS.clear()
-        return
-    want = set(main_streams)
-    for key in [k for k in _SIDE_STREAMS if k[1] in want]:
-        del _SIDE_STREAMS[key]
+    with _SIDE_STREAMS_LOCK:
+        if main_streams is None:
+            _SIDE_STREAMS.clear()
+            return
+        want = set(main_streams)
+        for key in [k for k in _SIDE_STREAMS if k[1] in want]:
+            del _SIDE_STREAMS[key]
 
 
 def unet_branches() -> int:

@@ -24,12 +24,15 @@ _zeros = {}
 def zeros_ro(shape, like: torch.Tensor) -> torch.Tensor:
     """A READ-ONLY zero tensor, shared by every caller on the device (initial hidden states, recurrent_varnet.py:236, 118-121): no
     fill kernel per forward / per replayed graph.  Created outside hipGraph capture (the first eager forward); inside a capture
-    with nothing cached yet it falls back to a fresh tensor."""
+    with nothing cached yet it falls back to a fresh tensor.  The fill runs on the stream that asked first and the cached tensor is read
+    from every stream (slices in flight on streams of their own), so that stream is synchronised once, before the tensor is shared."""
     key = (like.device, like.dtype, tuple(shape))
     z = _zeros.get(key)
     if z is None:
         z = torch.zeros(shape, device=like.device, dtype=like.dtype)
         if not torch.cuda.is_current_stream_capturing():
+            if z.is_cuda:
+                torch.cuda.current_stream(like.device).synchronize()
             _zeros[key] = z
     return z
 
