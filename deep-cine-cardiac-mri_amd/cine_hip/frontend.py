@@ -84,19 +84,33 @@ def combine_target(images: torch.Tensor, sens: torch.Tensor, crop_target: Sequen
 def prepare_slice(kspace_txyc: torch.Tensor, crop_shape=(200, 200), n_slices: int = 15,
                   filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6):
     """reference data/mri_data.py:283-293 on the device.  kspace_txyc: raw (t, x, y, coil) complex64 (the HDF5 ``y`` array)
-    on the GPU.  Returns (kspace (t, coil, X, Y, 2) float32 of the filtered crop, filtered images (t, coil, X, Y, 2))."""
+    on the GPU.  Returns (kspace (t, coil, X, Y, 2) float32 of the filtered crop, filtered images (t, coil, X, Y, 2)).  Raw sizes the FFT
+    line engines take go through the full-image cine_fft2c; any other raw size through the windowed transform (ops.raw_window_ifft2c),
+    which computes only the kept frames and the crop."""
     if not kspace_txyc.is_cuda:
         raise CineHipError("prepare_slice: the HIP path needs a GPU tensor (no CPU fallback)")
-    k = _c2r((kspace_txyc.to(torch.complex64) * scaling).permute(0, 3, 1, 2).contiguous())
-    images = ops.fft2c(k, inverse=True)                                      # ifftn(norm=None) * sqrt(N) == ortho (:288-289)
-    _, filt = filtered_crop_center_and_slices(images, crop_shape, n_slices, filter_size)
+    t, nx, ny = kspace_txyc.shape[0], kspace_txyc.shape[1], kspace_txyc.shape[2]
+    if ops.fft_line_supported(nx) and ops.fft_line_supported(ny):
+        k = _c2r((kspace_txyc.to(torch.complex64) * scaling).permute(0, 3, 1, 2).contiguous())
+        images = ops.fft2c(k, inverse=True)                                  # ifftn(norm=None) * sqrt(N) == ortho (:288-289)
+        _, filt = filtered_crop_center_and_slices(images, crop_shape, n_slices, filter_size)
+    else:
+        # raw sizes the line engines refuse (e.g. 2x-oversampled readouts): only the kept frames and the centered crop of the image
+        # are computed, straight from the raw layout (:288-289 then transforms.py:209-214)
+        crop = ops.raw_window_ifft2c(kspace_txyc.to(torch.complex64), min(int(n_slices), t), crop_shape, scaling)
+        filt = gaussian_filter(crop, filter_size)
+    return _to_kspace(filt), filt
+
+
+def _to_kspace(filt: torch.Tensor) -> torch.Tensor:
+    """mri_data.py:291-292: the filtered crop (t, c, X, Y, 2) back to k-space with the reference's shift order."""
     # :291 transforms back with the shifts the other way round -- ifftshift(fftn(fftshift(x))) -- which differs from fft2c
     # (fftshift(fftn(ifftshift(x)))) along axes of ODD length by one sample on either side: fftshift(x) = roll(ifftshift(x), -1)
     # and ifftshift(y) = roll(fftshift(y), +1) there.  Even lengths (the reference's 200 x 200 crop): no difference.
     odd = [d for d, n in ((-3, filt.shape[-3]), (-2, filt.shape[-2])) if n % 2]
     x = torch.roll(filt, shifts=[-1] * len(odd), dims=odd).contiguous() if odd else filt
     kk = ops.fft2c(x)                                                        # fftn(norm=None) / sqrt(N) == ortho (:291-292)
-    return (torch.roll(kk, shifts=[1] * len(odd), dims=odd).contiguous() if odd else kk), filt
+    return torch.roll(kk, shifts=[1] * len(odd), dims=odd).contiguous() if odd else kk
 
 
 def espirit_maps(kspace: torch.Tensor, r: int = 24, k: int = 6, thresh: float = 1e-3, crop: float = 0.8,

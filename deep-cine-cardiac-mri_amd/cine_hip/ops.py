@@ -312,6 +312,35 @@ def fft1c(x: torch.Tensor, inverse: bool = False, variant: int = 0) -> torch.Ten
     return out
 
 
+def fft_line_supported(n: int) -> bool:
+    """Whether fft2c / fft1c (and every other transform of the library but raw_window_ifft2c) take line length n."""
+    return bool(lib().cine_fft_line_supported(int(n)))
+
+
+def raw_window_ifft2c(raw_txyc: torch.Tensor, n_frames: int, window: Sequence[int], scale: float = 1.0) -> torch.Tensor:
+    """The centered ``window`` (cx, cy) of (fftshift o ifft2 o ifftshift)(scale * raw[:n_frames]) (ortho), computed straight from the raw
+    (t, x, y, coil) k-space layout of the HDF5 ``y`` array (reference data/mri_data.py:283-289, then transforms.py:206-214): complex64
+    (t, x, y, coil) or float32 pairs (t, x, y, coil, 2) on the GPU -> (n_frames, coil, cx, cy, 2) float32.  Any size: this transform has
+    no line-length limit."""
+    if not isinstance(raw_txyc, torch.Tensor):
+        raise TypeError("raw_window_ifft2c: expected a tensor")
+    x = torch.view_as_real(raw_txyc) if raw_txyc.is_complex() else raw_txyc
+    if x.dim() != 5 or x.shape[-1] != 2:
+        raise ValueError("raw_window_ifft2c expects (t, x, y, coil) complex or (t, x, y, coil, 2) pairs")
+    t, nx, ny, c, _ = x.shape
+    cx, cy = int(window[0]), int(window[1])
+    n_frames = int(n_frames)
+    if not (0 < cx <= nx and 0 < cy <= ny and 0 < n_frames <= t and c > 0):
+        raise ValueError("Invalid shapes.")                                  # transforms.py:206-207
+    x = _dev(x, "raw_window_ifft2c input")
+    out = torch.empty((n_frames, c, cx, cy, 2), device=x.device, dtype=torch.float32)
+    nbytes = lib().cine_raw_window_ws_bytes(n_frames, nx, ny, c, cx, cy)
+    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    check(lib().cine_raw_window_ifft2c(x.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, t, nx, ny, c, n_frames, cx, cy, float(scale),
+                                       _stream()), "cine_raw_window_ifft2c")
+    return out
+
+
 # ------------------------------------------------------------------ coil operators
 def sens_reduce(k: torch.Tensor, sens: torch.Tensor, magnitude: bool = False,
                 destroy_input: bool = False) -> torch.Tensor:

@@ -971,9 +971,11 @@ static size_t lds_bytes(bool f200, int n, int lines) {
     return (f200 ? tile : 2 * tile) + (size_t)n * sizeof(cf);
 }
 
+static bool line_supported(int n) { return n <= kMaxGenericN || (n <= kMaxSmoothN && MixedRadix::smooth(n)); }
+
 static int check_n(int n, const char* what) {
     CINE_REQUIRE(n >= 1, CINE_EINVAL, "%s: length %d < 1", what, n);
-    CINE_REQUIRE(n <= kMaxGenericN || (n <= kMaxSmoothN && MixedRadix::smooth(n)), CINE_EUNSUPPORTED,
+    CINE_REQUIRE(line_supported(n), CINE_EUNSUPPORTED,
                  "%s: FFT length %d unsupported (2^a 3^b 5^c up to %d via the mixed-radix engine, any length up to %d via the direct one)",
                  what, n, kMaxSmoothN, kMaxGenericN);
     return CINE_OK;
@@ -1108,6 +1110,8 @@ extern "C" int cine_fft1c(const float* in, float* out, long nlines, int n, int i
     return plain_rows(reinterpret_cast<const cf*>(in), reinterpret_cast<cf*>(out), nlines, n, inverse != 0, s_in, s_out,
                       as_stream(stream));
 }
+
+extern "C" int cine_fft_line_supported(int n) { return n >= 1 && line_supported(n) ? 1 : 0; }
 
 // hybrid space = image along h, k-space along w: what a centered column IFFT of k-space gives.
 extern "C" int cine_kspace_to_hybrid(const float* k, float* hyb, long nimg, int h, int w, void* stream) {

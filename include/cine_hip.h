@@ -54,9 +54,11 @@ const char* cine_build_arch(void);      /* "gfx950" */
 
 /* fft2c (fftc.py:59-83) / ifft2c (fftc.py:86-110) over the last two spatial dims of
  * `nimg` images of h x w complex.  inverse = 0 forward, 1 inverse.  in == out allowed.
- * Line lengths (every transform of this header): 200 (the 10 x 20 engine), any 2^a 3^b 5^c <= 512 (mixed-radix Stockham engine),
- * any other length <= 400 (direct DFT in LDS); CINE_EUNSUPPORTED beyond. */
+ * Line lengths (every transform of this header except cine_raw_window_ifft2c, which has no length limit): 200 (the 10 x 20
+ * engine), any 2^a 3^b 5^c <= 512 (mixed-radix Stockham engine), any other length <= 400 (direct DFT in LDS); CINE_EUNSUPPORTED
+ * beyond.  cine_fft_line_supported(n) is 1 for the lengths these transforms take, 0 otherwise (n < 1 included). */
 int cine_fft2c(const float* in, float* out, int nimg, int h, int w, int inverse, void* stream);
+int cine_fft_line_supported(int n);
 
 /* fft1c (fftc.py:5-29) / ifft1c (fftc.py:32-56): `nlines` contiguous lines of n complex.
  * variant 0 = fftc.py shift order (ifftshift, transform, fftshift);
@@ -507,6 +509,16 @@ int cine_cg_adjoint_finish(const float* part, const float* rr_dev, const float* 
 /* data[:t_out, :, y0:y0+hout, x0:x0+wout] with y0 = (hin - hout) / 2, x0 = (win - wout) / 2 (transforms.py:209-214):
  * in (t_in, c, hin, win, 2) -> out (t_out, c, hout, wout, 2). */
 int cine_crop_select(const float* in, float* out, int t_in, int c, int hin, int win, int t_out, int hout, int wout, void* stream);
+/* The first step of the front-end for raw k-space of ANY size (mri_data.py:283-289 followed by the crop and frame selection of
+ * transforms.py:206-214), without the full image: raw (t_in, nx, ny, c) complex -- the HDF5 `y` layout, read in place -- ->
+ * out (t_out, c, cx, cy, 2) = (fftshift o ifft2 o ifftshift)(scale * raw[:t_out]) in ortho normalisation (shifts by N / 2 on both
+ * sides), rows x0 = (nx - cx) / 2 .. x0 + cx, columns y0 = (ny - cy) / 2 .. y0 + cy.  Two exact-fp32 complex GEMMs against window
+ * DFT matrices built in `ws` on every call; no length limit: any nx, ny >= 1, 1 <= cx <= nx, 1 <= cy <= ny, 1 <= t_out <= t_in,
+ * c >= 1 (else CINE_EINVAL), CINE_EUNSUPPORTED only past a grid limit (named in the message).  ws_bytes >= cine_raw_window_ws_bytes()
+ * (0 for invalid shapes).  Repeated calls are bit-identical. */
+int cine_raw_window_ifft2c(const float* raw, float* out, void* ws, size_t ws_bytes, int t_in, int nx, int ny, int c, int t_out,
+                           int cx, int cy, float scale, void* stream);
+size_t cine_raw_window_ws_bytes(int t_out, int nx, int ny, int c, int cx, int cy);
 /* One axis pass of scipy.ndimage.gaussian_filter as transforms.py:216-217 calls it (mode 'reflect', truncate 4.0, weights and
  * accumulation in float64, float32 result) over a (outer, n, inner) array of complex pairs: the real and imaginary parts
  * are filtered alike.  The caller runs one pass per axis with sigma > 0, in axis order (mri_data.py:279: [0.7, 0, 0.3, 0.3]). */
