@@ -68,6 +68,46 @@ def test_unet_backward_vs_oracle(dev, n, chans, pools, h, w):
     assert rel_err(xh.grad.cpu(), xr.grad) < TOL
 
 
+UNET_SWEEP = [
+    # (n, chans, pools, h, w): what the shape reaches in cine_unet2d_backward
+    (1, 5, 3, 23, 16),         # widths 16 / 8 / 4 / 2: every weight-gradient tile width; h 23 / 11 / 5 / 2: odd at every pool level
+    (2, 1, 2, 21, 11),         # one channel; odd widths 11 / 5 / 2 and heights 21 / 10 / 5: up-path crop and zero pad
+    (1, 18, 2, 27, 13),        # ragged 16-channel chunks; 13 / 6 / 3 wide
+    (3, 5, 1, 9, 33),          # 33 wide: a ragged last 16-pixel tile
+    (1, 18, 2, 122, 120),      # materialise: the pooled source of level 1 holds 18 x 61 x 60 >= 65 536 elements, 60 % 4 == 0
+]
+
+
+@pytest.mark.parametrize("n,chans,pools,h,w", UNET_SWEEP, ids=lambda v: str(v))
+def test_unet_backward_sweep_vs_oracle_float64(dev, n, chans, pools, h, w):
+    """cine_unet2d_backward against the oracle's FLOAT64 autograd (denoisers/unet.py:73-125): every weight gradient and the input
+    gradient, over the tile widths, odd sizes at each pool level, chans 1 / 5 / 18, n = 1 and a layer whose pooled source goes through
+    the weight gradient's materialise pre-pass.  A float32 run can sit on a LeakyReLU kink the float64 run does not (see
+    test_training_gradients_on_odd_shapes_vs_oracle_float64); an indexing mistake is there for every input: 1e-4 of each tensor's
+    largest gradient on the BEST of three inputs, 5e-2 on every one."""
+    from reconstruction.models.denoisers.unet import Unet
+    from oracle import regularisers as R
+    from cine_hip import synth
+    hip = Unet(chans, pools, 2, 2).to(dev)
+    synth.fill_parameters_(hip, 11)
+    ref = R.Unet(chans, pools, 2, 2).double()
+    ref.load_state_dict({k: v.double() for k, v in hip.state_dict().items()})
+    worst = []
+    for seed in (1, 3, 5):
+        x, gy = rnd(seed, n, 2, h, w), rnd(seed + 1, n, 2, h, w)
+        with torch.enable_grad():
+            xr = x.double().requires_grad_(True)
+            want = _grads(ref, (ref(xr) * gy.double()).sum())
+            xh = x.to(dev).requires_grad_(True)
+            got = _grads(hip, (hip(xh) * gy.to(dev)).sum())
+        errs = {k: rel_err(got[k].cpu(), w_) for k, w_ in want.items()}
+        errs["input"] = rel_err(xh.grad.cpu(), xr.grad)
+        assert set(got) == set(want)
+        worst.append(max(errs.items(), key=lambda kv: kv[1]))
+    assert min(e for _, e in worst) < TOL, worst
+    assert max(e for _, e in worst) < 5e-2, worst
+
+
 def test_unet_two_sets_and_determinism(dev):
     """Two weight sets in one launch sequence (the x-f / y-f U-Nets, varnet.py:224-226) == two single launches; a repeated
     backward pass is bit-identical (fixed-order reductions)."""
