@@ -417,6 +417,7 @@ int launch_conv_coarse(const ConvArgs& a, hipStream_t st, bool* handled) {
     const bool fast = coarse_fast_ok(a);
     if (!fast && !a.ypart) return CINE_OK;
     *handled = true;
+    diag_count(D_CONV_COARSE);
     const bool vol = a.vol != 0;
     const int mt = coarse_mt(a.rowsp, a.D, a.H, a.W, vol);
     CoarseArgs p{};

@@ -1082,6 +1082,7 @@ static int launch_cfg(ConvArgs a, hipStream_t st) {
         const int e = launch_conv_plane(a, CK, CT, WM, WN, MT, TW, st, &handled);
         if (e || handled) return e;
     }
+    diag_count(PAIR ? D_CONV_PAIR : (a.fast || a.vfast || a.wav) ? D_CONV_GENERAL_VEC : D_CONV_GENERAL_ELEM);
     ProfScope prof(fam, st);
     hipLaunchKernelGGL(kern, grid, dim3(C::NT), lds, st, a);
     return check_launch("conv_mfma_kernel");
@@ -1561,6 +1562,7 @@ extern "C" int cine_conv1x1_bias(const float* x, const float* part_x, int np_x, 
         const size_t lds = (size_t)(2 + cout) * cin * sizeof(float);
         hipStream_t st = as_stream(stream);
         ProfScope prof(F_CONV1, st);
+        diag_count(D_CONV1X1_STREAM);
         switch (cout) {
             case 1: hipLaunchKernelGGL(conv1x1_stream_kernel<1>, grid, dim3(256), lds, st, c); break;
             case 2: hipLaunchKernelGGL(conv1x1_stream_kernel<2>, grid, dim3(256), lds, st, c); break;
@@ -1619,6 +1621,7 @@ extern "C" int cine_pool3d_act(const float* x, const float* part, int np, float*
     const bool vec = w % 8 == 0 && reinterpret_cast<uintptr_t>(x) % 16 == 0 && reinterpret_cast<uintptr_t>(y) % 16 == 0;
     const long total = planes * (long)(d / 2) * (h / 2) * (vec ? w / 8 : w / 2);
     ProfScope prof(F_PACK, as_stream(stream));
+    diag_count(vec ? D_POOL3D_VEC : D_POOL3D_SCALAR);
     if (vec) hipLaunchKernelGGL(pool3d_act_kernel<true>, dim3(grid1d(total, 256, 16384)), dim3(256), 0, as_stream(stream), x, part, np, y, planes, d, h, w, eps, slope);
     else hipLaunchKernelGGL(pool3d_act_kernel<false>, dim3(grid1d(total, 256, 16384)), dim3(256), 0, as_stream(stream), x, part, np, y, planes, d, h, w, eps, slope);
     return check_launch("pool3d_act_kernel");

@@ -619,6 +619,7 @@ int launch_conv_plane(const ConvArgs& a, int ck, int ct, int wm, int wn, int mt,
 #define CINE_PLANE_CASE(CK_, CT_, WM_, WN_, MT_, TW_, MODE_, NEEDWHOLE)                                                   \
     if (ck == CK_ && ct == CT_ && wm == WM_ && wn == WN_ && mt == MT_ && tw == TW_ && mode == MODE_ && (whole || !(NEEDWHOLE))) { \
         *handled = true;                                                                                                  \
+        diag_count(D_CONV_PLANE);                                                                                         \
         return launch_plane<CK_, CT_, WM_, WN_, MT_, TW_, MODE_>(p, a.n, st);                                              \
     }
     CINE_PLANE_CASE(4, 1, 1, 4, 13, 16, 0, false)
@@ -914,6 +915,7 @@ int launch_tconv_plane(const ConvArgs& a, int mt, int tw, hipStream_t st, bool* 
 #define CINE_TCONV_CASE(CIN_, CT_, WM_, MT_, TW_)                                   \
     if (a.cin == CIN_ && mt == MT_ && tw == TW_) {                                   \
         *handled = true;                                                            \
+        diag_count(D_TCONV_PLANE);                                                  \
         return launch_tconv<CIN_, CT_, WM_, MT_, TW_>(p, a.n, st);                   \
     }
     CINE_TCONV_CASE(32, 1, 4, 13, 8)
@@ -1424,6 +1426,7 @@ int launch_conv_wide(const ConvArgs& a, int ct, int wm, int wn, int mt, int v3, 
 #define CINE_WIDE_CASE(CT_, WM_, WN_, MT_)                                                                     \
     if (ct == CT_ && wm == WM_ && wn == WN_ && mt == MT_) {                                                     \
         *handled = true;                                                                                        \
+        diag_count(v3 ? D_CONV_WIDE_V3 : D_CONV_WIDE);                                                          \
         if (v3) return mode ? launch_wide<CT_, WM_, WN_, MT_, 1, 1>(p, a.n, st) : launch_wide<CT_, WM_, WN_, MT_, 0, 1>(p, a.n, st); \
         return mode ? launch_wide<CT_, WM_, WN_, MT_, 1, 0>(p, a.n, st) : launch_wide<CT_, WM_, WN_, MT_, 0, 0>(p, a.n, st);         \
     }

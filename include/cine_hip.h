@@ -641,12 +641,15 @@ int cine_pad2d(const float* x, float* out, long planes, int h, int w, int top, i
 
 /* Diagnostics.  3x3 convolutions whose tile spans the plane's width (the x-f / y-f planes of the cascade U-Nets, reference
  * denoisers/unet.py:159-168) and the k2 s2 transpose convs between them (unet.py:212-218) run on lean kernels (csrc/conv_plane.hip)
- * that are BIT-IDENTICAL to the general one, and so do the 3x3 (x3) convolutions of wider planes and volumes in 16-wide column
+ * that are BIT-IDENTICAL to the general one (except a Haar-DWT source, mode 3, whose K chunks the lean kernel forms from two source
+ * channels x four bands instead of eight channels of one band: the same sums in another order), and so do the 3x3 (x3) convolutions of
+ * wider planes and volumes in 16-wide column
  * tiles (sensitivity network, CRNN cells, 3-D U-Net); `on` is a mask -- bit 0 the plane-wide 3x3 convolutions, bit 1 the
  * transpose convolutions, bit 2 the wide planes / volumes; a cleared bit routes that kind through the general kernel (the
  * bit-identity tests, A/B timing).  Bit 4 SET routes the plane-wide weight gradients of training (grad_kernels.hip:
  * wgrad_plane_kernel, also bit-identical) through the general weight-gradient kernel.  A setting of the CALLING THREAD (default 7
- * in every thread): it selects kernels for the launches that thread enqueues afterwards and never changes a result. */
+ * in every thread): it selects kernels for the launches that thread enqueues afterwards and changes no result but for that
+ * summation order. */
 int cine_set_conv_plane(int on);
 
 /* A second stream of the CALLING THREAD for the weight-gradient launches of cine_unet2d_backward / cine_unet3d_backward / cine_mwcnn_backward (they
@@ -789,7 +792,13 @@ int cine_ssim_loss_bwd(const float* x, const float* y, int t, int h, int w, int 
 int cine_profile_begin(void);
 /* Diagnostics: process-wide counts of launches that took one of two interchangeable routes, so that a test can prove WHICH ran
  * (`which`: 0 plane-wide weight gradients on the lean kernel, 1 on the general kernel, 2 U-Net passes run as concurrent branches,
- * 3 BCRNN layers run by the C time-sweep entry points).  reset != 0 returns the count and zeroes it; -1 for an unknown counter. */
+ * 3 BCRNN layers run by the C time-sweep entry points; the forward-convolution launches, counted where each is committed:
+ * 4 the lean plane-wide 3x3 kernel, 5 the plane-wide transpose-conv kernel, 6 the 16-wide column-tile kernel on 2-D planes,
+ * 7 the same in its three-pass volume form, 8 the coarse K-split kernel, 9 the streaming 1x1 kernel of cine_conv1x1_bias,
+ * 10 the general kernel's two-set pair form, 11 the general kernel with vectorised staging, 12 the general kernel with element-wise
+ * staging -- input-gradient launches on the general kernel count in 10 .. 12 too; 13 / 14 cine_pool3d_act on its float4 / scalar
+ * kernel).  reset != 0 returns the count and zeroes it;
+ * -1 for an unknown counter. */
 long cine_diag_counter(int which, int reset);
 /* Diagnostics: a one-workgroup kernel that runs for `microseconds` (1 .. 100 000; clock-bounded AND iteration-bounded: it always ends).  The
  * binding times two of them on two streams to learn whether the streams share a hardware queue (GPU_MAX_HW_QUEUES): streams on one queue run

@@ -29,16 +29,11 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from kernel_sweep import BAR, BAR_CAP, LONG_REDUCTION, Guarded, Workspace, Worst, _bar, cap_samples, case_id, hash_case, sweep, view_at
 
-BAR = 1e-5
-BAR_CAP = 1e-4
-LONG_REDUCTION = 100_000
 KINK_MARGIN = 1e-3
 EPS = 1e-5
 D_WGRAD_PLANE, D_WGRAD_GENERAL = 0, 1          # cine_diag_counter (csrc/common.h: Diag)
-GUARD = 8                                      # guard floats on each side of an output
-GUARD_VALUE = 1234.5
-WS_TAIL = 4096                                 # sentinel bytes behind a workspace
 
 
 # ================================================================== float64 references (CPU)
@@ -127,28 +122,6 @@ def kink_free_planes(seed, shape, scale=1.7, shift=0.3, gap=0.05, margin=KINK_MA
         if kink_margin(x) >= margin:
             return x
     raise AssertionError(f"kink_free_planes: no draw of {shape} keeps {margin} from the kink in {tries} tries")
-
-
-def sweep(seed, axes, count):
-    """`count` seeded cases over `axes` (name -> list of values) in which every value of every axis appears: each axis walks a
-    shuffled cycle of its values, so the combinations differ from case to case."""
-    rs = np.random.RandomState(seed)
-    cols = {}
-    for name, vals in axes.items():
-        order = []
-        while len(order) < count:
-            order.extend(rs.permutation(len(vals)).tolist())
-        cols[name] = [vals[i] for i in order[:count]]
-    return [{k: cols[k][i] for k in axes} for i in range(count)]
-
-
-def cap_samples(n, per_sample, budget):
-    """n reduced so that n * per_sample stays within budget (at least one sample): keeps the float64 references fast."""
-    return max(1, min(n, budget // per_sample))
-
-
-def case_id(c):
-    return "-".join(f"{k}{int(v) if isinstance(v, bool) else v}" for k, v in c.items())
 
 
 # ================================================================== case lists
@@ -292,14 +265,8 @@ def _near_constant_plane(seed):
 
 # ================================================================== GPU harness
 gpu = pytest.mark.gpu
-WORST = {}          # entry point -> (worst error / bar, case)
-
-
-def _record(what, err, bar, case):
-    r = err / bar
-    if r > WORST.get(what, (-1.0, None))[0]:
-        WORST[what] = (r, case)
-    assert err <= bar, f"{what} {case}: error {err:.3e} > bar {bar:.1e}"
+WORST = Worst()     # entry point -> (worst error / bar, case)
+_record = WORST.record
 
 
 @pytest.fixture(scope="module")
@@ -307,9 +274,7 @@ def dev():
     assert torch.cuda.is_available(), "-m gpu tests need an MI355X"
     yield torch.device("cuda:0")
     if WORST:
-        print("\nworst error / bar per entry point:")
-        for k in sorted(WORST):
-            print(f"  {k:28s} {WORST[k][0]:.3f}  {WORST[k][1]}")
+        WORST.report()
 
 
 def _L():
@@ -330,48 +295,7 @@ def _rand(seed, *shape):
     return torch.from_numpy(np.random.RandomState(seed).standard_normal(shape).astype(np.float32))
 
 
-class Guarded:
-    """A device tensor of `shape` at storage offset GUARD + off floats of a buffer whose other floats hold GUARD_VALUE."""
-
-    def __init__(self, shape, off, dev, fill=None):
-        self.n = int(np.prod(shape))
-        self.lo = GUARD + off
-        self.buf = torch.full((self.lo + self.n + GUARD,), GUARD_VALUE, device=dev)
-        self.t = self.buf[self.lo:self.lo + self.n].view(shape)
-        if fill is not None:
-            self.t.copy_(fill)
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def intact(self):
-        return bool((self.buf[:self.lo] == GUARD_VALUE).all()) and bool((self.buf[self.lo + self.n:] == GUARD_VALUE).all())
-
-
-def _view(x, off, dev):
-    """x on the device at storage offset off (a pointer 4 * off bytes past an aligned allocation)."""
-    return Guarded(x.shape, off, dev, x.to(dev)).t
-
-
-class Workspace:
-    """Exactly `nbytes` of workspace, carved from a larger buffer whose tail holds a sentinel pattern."""
-
-    def __init__(self, nbytes, dev):
-        self.nbytes = int(nbytes)
-        self.tail = (torch.arange(WS_TAIL, dtype=torch.int64) * 37 % 251).to(torch.uint8).to(dev)
-        self.buf = torch.zeros(self.nbytes + WS_TAIL, dtype=torch.uint8, device=dev)
-        self.buf[self.nbytes:] = self.tail
-
-    def ptr(self):
-        return self.buf.data_ptr()
-
-    def intact(self):
-        return torch.equal(self.buf[self.nbytes:], self.tail)
-
-
-def _bar(err_torch32, k):
-    """The bar for a reduction of k terms (module docstring)."""
-    return BAR if k <= LONG_REDUCTION else min(BAR_CAP, max(BAR, 2 * err_torch32))
+_view = view_at
 
 
 # ================================================================== weight gradients
@@ -501,14 +425,6 @@ def test_conv1x1_wgrad_sweep(dev, c):
 @pytest.mark.parametrize("c", WGRAD1_CASES[::4], ids=case_id)
 def test_conv1x1_wgrad_unaligned(dev, c, off):
     _run_wgrad(1, c, off, dev, seed=hash_case(c))
-
-
-def hash_case(c):
-    """A seed from the case's values (stable across runs, unlike hash())."""
-    s = 0
-    for v in c.values():
-        s = (s * 1_000_003 + (int(v) if not isinstance(v, str) else sum(map(ord, v)))) % 2_147_483_000
-    return s
 
 
 # ================================================================== input gradients
