@@ -132,6 +132,9 @@ _SIGS = {
     "cine_crop_select": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_raw_window_ifft2c": (c_int, [P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "cine_raw_window_ws_bytes": (c_size_t, [c_int] * 6),
+    "cine_coil_gram_ws_bytes": (c_size_t, [c_int] * 5),
+    "cine_coil_gram": (c_int, [P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "cine_coil_compress": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_fft_line_supported": (c_int, [c_int]),
     "cine_gauss_axis": (c_int, [P, P, c_long, c_int, c_long, c_double, P]),
     "cine_combine_target": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),

@@ -3,6 +3,11 @@
 ``prepare_slice``   reference data/mri_data.py:283-293, 302-303: raw k-space -> image space -> crop, frame selection,
                     Gaussian filter (data/transforms.py:186-220) -> k-space of the filtered crop, and the coil-combined
                     magnitude target.
+``coil_gram`` / ``coil_matrix_from_gram`` / ``compress_coils``
+                    SVD coil compression of the raw data (Buehrer et al., MRM 57:1131, 2007; Huang et al., MRI 26:133, 2008): the c
+                    physical coils projected onto V virtual coils BEFORE the inverse transform.  The reference has no such step; here
+                    it gives every scan of a data set the same shape (one SlicePipeline graph set) and lifts the 32-coil cap of the
+                    calibration.  ``prepare_slice(..., virtual_coils=V)`` runs it in place.
 ``espirit_maps``    what the reference gets from the BART toolbox (``bart ecalib -r N``, mri_data.py:296,
                     transforms.py:429): ESPIRiT sensitivity maps (Uecker et al., MRM 71:990-1001, 2014) with ecalib's
                     defaults -- 6 x 6 kernels, singular-value threshold 0.001, eigenvalue crop 0.8, first map.
@@ -81,14 +86,127 @@ def combine_target(images: torch.Tensor, sens: torch.Tensor, crop_target: Sequen
     return out
 
 
+def _raw_pairs(raw: torch.Tensor, what: str) -> torch.Tensor:
+    """raw (t, x, y, coil) complex64 or (t, x, y, coil, 2) float32 on the GPU -> contiguous, 16-byte aligned float32 pairs."""
+    if not isinstance(raw, torch.Tensor):
+        raise TypeError(f"{what}: expected a tensor")
+    if not raw.is_cuda:
+        raise CineHipError(f"{what}: the HIP path needs a GPU tensor (no CPU fallback)")
+    x = torch.view_as_real(raw.to(torch.complex64)) if raw.is_complex() else raw
+    if x.dim() != 5 or x.shape[-1] != 2:
+        raise ValueError(f"{what} expects (t, x, y, coil) complex or (t, x, y, coil, 2) pairs")
+    x = ops._dev(x, what)
+    return x.clone() if x.data_ptr() % 16 else x
+
+
+def _kept_frames(n_frames, t: int) -> int:
+    n = t if n_frames is None else min(int(n_frames), t)
+    if n < 1:
+        raise ValueError("Invalid shapes.")
+    return n
+
+
+def coil_gram(raw: torch.Tensor, n_frames: Optional[int] = None, region: int = 24) -> torch.Tensor:
+    """Calibration Gram matrix of the coils: raw (t, x, y, coil) complex64 -> G (coil, coil) complex128,
+    G[i, j] = sum over the first min(n_frames, t) frames and the central region x region block of k-space (clipped to the matrix, centred
+    as espirit_maps centres its block; region 0 = the whole matrix) of raw[..., i] * conj(raw[..., j]).  Float64 sums of exact products
+    in a fixed order: exactly Hermitian, bit-identical from call to call."""
+    x = _raw_pairs(raw, "coil_gram")
+    t, nx, ny, c, _ = x.shape
+    n = _kept_frames(n_frames, t)
+    region = int(region)
+    if region < 0:
+        raise ValueError("coil_gram: region must be >= 0")
+    gram = torch.empty((c, c), device=x.device, dtype=torch.complex128)
+    nbytes = lib().cine_coil_gram_ws_bytes(n, nx, ny, c, region)
+    ws = torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+    check(lib().cine_coil_gram(x.data_ptr(), gram.data_ptr(), ws.data_ptr(), nbytes, t, nx, ny, c, n, region, ops._stream()), "cine_coil_gram")
+    return gram
+
+
+def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """G (c, c) Hermitian -> (A (V, c) complex64, lam (c,) float64 descending): G = U diag(lam) U^H, A[v] = conj(U[:, v]) times the unit
+    phase that makes its largest-magnitude entry (lowest index on a tie) real and positive, rounded once to complex64.  Rows are
+    orthonormal and A G A^H = diag(lam[:V]).  A small dense step: torch.linalg.eigh in complex128 on the tensor's own device."""
+    if gram.dim() != 2 or gram.shape[0] != gram.shape[1] or gram.shape[0] < 1:
+        raise ValueError("coil_matrix_from_gram: gram must be a square matrix")
+    c = gram.shape[0]
+    v = int(virtual_coils)
+    if not 1 <= v <= c:
+        raise ValueError(f"coil_matrix_from_gram: virtual_coils must be in 1..{c}")
+    g = gram.to(torch.complex128)
+    if float((g - g.conj().transpose(0, 1)).abs().max()) > 1e-12 * float(g.abs().max()):
+        raise ValueError("coil_matrix_from_gram: gram is not Hermitian")
+    try:
+        ev, vec = torch.linalg.eigh(g)                                       # ascending
+    except RuntimeError as e:                                                # no silent host fallback
+        raise CineHipError(f"coil_matrix_from_gram: torch.linalg.eigh failed on {g.device}: {e}") from e
+    lam = ev.flip(0).contiguous()
+    a = vec.flip(1)[:, :v].conj().transpose(0, 1).contiguous()               # (V, c)
+    mag = a.abs()
+    idx = mag.argmax(dim=1, keepdim=True)                                    # the first of equal maxima
+    peak = a.gather(1, idx)
+    a = a * (peak.conj() / peak.abs())
+    a.scatter_(1, idx, mag.gather(1, idx).to(a.dtype))                       # exactly real there
+    return a.to(torch.complex64), lam
+
+
+def coil_compression_matrix(raw: torch.Tensor, virtual_coils: int, n_frames: Optional[int] = None,
+                            region: int = 24) -> Tuple[torch.Tensor, torch.Tensor]:
+    """coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils)."""
+    return coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils)
+
+
+def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[int] = None) -> torch.Tensor:
+    """out[t, x, y, v] = sum_c matrix[v, c] raw[t, x, y, c] for the first min(n_frames, t) frames: raw (t, x, y, coil) complex64, matrix
+    (V, coil) complex64 -> (T, x, y, V) complex64, the layout prepare_slice and ops.raw_window_ifft2c take.  Exact fp32, bit-identical
+    from call to call."""
+    x = _raw_pairs(raw, "compress_coils")
+    t, nx, ny, c, _ = x.shape
+    n = _kept_frames(n_frames, t)
+    if not isinstance(matrix, torch.Tensor) or matrix.dim() != 2 or matrix.shape[1] != c:
+        raise ValueError(f"compress_coils: matrix must be (V, {c})")
+    v = matrix.shape[0]
+    m = ops._dev(torch.view_as_real(matrix.to(torch.complex64)), "compress_coils matrix")
+    out = torch.empty((n, nx, ny, v, 2), device=x.device, dtype=torch.float32)
+    check(lib().cine_coil_compress(x.data_ptr(), m.data_ptr(), out.data_ptr(), t, nx, ny, c, n, v, ops._stream()), "cine_coil_compress")
+    return torch.view_as_complex(out)
+
+
+def _compressed(kspace_txyc: torch.Tensor, n_slices: int, virtual_coils, coil_matrix, cc_region: int) -> torch.Tensor:
+    """The coil-compression leg of prepare_slice: the raw data on virtual coils (kept frames only), or the input itself where
+    nothing is to be done."""
+    if virtual_coils is None and coil_matrix is None:
+        return kspace_txyc
+    c = kspace_txyc.shape[3]
+    if coil_matrix is not None:
+        if coil_matrix.dim() != 2 or coil_matrix.shape[1] != c:
+            raise ValueError(f"coil_matrix must be (V, {c})")
+        if virtual_coils is not None and coil_matrix.shape[0] != int(virtual_coils):
+            raise ValueError(f"coil_matrix has {coil_matrix.shape[0]} rows, virtual_coils is {int(virtual_coils)}")
+        return compress_coils(kspace_txyc, coil_matrix.to(kspace_txyc.device), n_slices)
+    v = int(virtual_coils)
+    if v < 1 or v > c:
+        raise ValueError(f"virtual_coils must be in 1..{c} (the coil count of this scan)")
+    if v == c:
+        return kspace_txyc                                                   # already V coils: today's path and bits
+    a, _ = coil_compression_matrix(kspace_txyc, v, n_slices, cc_region)
+    return compress_coils(kspace_txyc, a, n_slices)
+
+
 def prepare_slice(kspace_txyc: torch.Tensor, crop_shape=(200, 200), n_slices: int = 15,
-                  filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6):
+                  filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, virtual_coils: Optional[int] = None,
+                  coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24):
     """reference data/mri_data.py:283-293 on the device.  kspace_txyc: raw (t, x, y, coil) complex64 (the HDF5 ``y`` array)
     on the GPU.  Returns (kspace (t, coil, X, Y, 2) float32 of the filtered crop, filtered images (t, coil, X, Y, 2)).  Raw sizes the FFT
     line engines take go through the full-image cine_fft2c; any other raw size through the windowed transform (ops.raw_window_ifft2c),
-    which computes only the kept frames and the crop."""
+    which computes only the kept frames and the crop.
+    ``virtual_coils=V``: the coils are first compressed to V virtual coils with the matrix of this slice's kept frames
+    (coil_compression_matrix, calibration block cc_region), and everything runs on V coils; V equal to the coil count passes the data
+    through.  ``coil_matrix=A`` (V, coil): use a given matrix instead, e.g. one matrix for all slices of a scan."""
     if not kspace_txyc.is_cuda:
         raise CineHipError("prepare_slice: the HIP path needs a GPU tensor (no CPU fallback)")
+    kspace_txyc = _compressed(kspace_txyc, n_slices, virtual_coils, coil_matrix, cc_region)
     t, nx, ny = kspace_txyc.shape[0], kspace_txyc.shape[1], kspace_txyc.shape[2]
     if ops.fft_line_supported(nx) and ops.fft_line_supported(ny):
         k = _c2r((kspace_txyc.to(torch.complex64) * scaling).permute(0, 3, 1, 2).contiguous())
@@ -164,14 +282,17 @@ def ecalib(time_avg_kspace, *, r: int):
 
 
 def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(200, 200), crop_target=(180, 180), n_slices: int = 15,
-                    filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, ecalib_r: int = 200):
+                    filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, ecalib_r: int = 200, virtual_coils: Optional[int] = None,
+                    coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24):
     """``SliceDataset.__getitem__`` of the reference (data/mri_data.py:267-311) in one piece, on the device: scale -> IFFT2 -> crop +
     frame selection + Gaussian filter -> FFT2 (k-space of the filtered crop) -> sensitivity maps from the time-averaged k-space
     (ESPIRiT, where the reference shells out to ``bart ecalib -r 200``; pass ``sens`` (coil, X, Y) complex to use given maps) ->
     coil-combined magnitude target -> center crop.  ``source``: the raw (t, x, y, coil) complex array / tensor, or an already-open
     h5py-like mapping holding it under ``"y"`` (and optionally ``"mask"``): the reader stays the caller's.
     Returns the reference's sample tuple (kspace (t, coil, X, Y) complex64, mask, target (t, cx, cy) float32, attrs, fname, dataslice)
-    as numpy arrays, like the reference (the ``*DataTransform`` classes take it from there, data/transforms.py:300-352)."""
+    as numpy arrays, like the reference (the ``*DataTransform`` classes take it from there, data/transforms.py:300-352).
+    ``virtual_coils`` / ``coil_matrix`` / ``cc_region``: as in prepare_slice; k-space, the calibration and ``sens`` are then on the V
+    virtual coils, so raw data with more than 32 coils calibrates whenever V <= 32."""
     import numpy as np
     if hasattr(source, "keys") and "y" in source:
         raw = np.asarray(source["y"])
@@ -182,7 +303,9 @@ def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(2
     if not torch.cuda.is_available():
         raise CineHipError("prepare_example: the front-end kernels need a GPU (no CPU fallback)")
     y = torch.as_tensor(raw).to(torch.complex64).cuda()
-    kspace, filt = prepare_slice(y, crop_shape, n_slices, filter_size, scaling)            # (t, c, X, Y, 2) each
+    kspace, filt = prepare_slice(y, crop_shape, n_slices, filter_size, scaling, virtual_coils, coil_matrix, cc_region)   # (t, c, X, Y, 2) each
+    if sens is not None and (virtual_coils is not None or coil_matrix is not None) and tuple(sens.shape)[0] != kspace.shape[1]:
+        raise ValueError(f"sens has {tuple(sens.shape)[0]} coils, the compressed data {kspace.shape[1]}")
     if sens is None:
         time_avg = torch.view_as_complex(kspace.mean(dim=0, keepdim=True).contiguous()).permute(0, 2, 3, 1)     # (1, X, Y, coil), :295
         smaps = ecalib(time_avg, r=ecalib_r).permute(2, 0, 1).contiguous()                  # (coil, X, Y), :297-298

@@ -519,6 +519,24 @@ int cine_crop_select(const float* in, float* out, int t_in, int c, int hin, int 
 int cine_raw_window_ifft2c(const float* raw, float* out, void* ws, size_t ws_bytes, int t_in, int nx, int ny, int c, int t_out,
                            int cx, int cy, float scale, void* stream);
 size_t cine_raw_window_ws_bytes(int t_out, int nx, int ny, int c, int cx, int cy);
+/* SVD coil compression (Buehrer et al., MRM 57:1131, 2007; Huang et al., MRI 26:133, 2008; BART's `cc`) of raw (t_in, nx, ny, c)
+ * complex in the HDF5 `y` layout, in front of everything above.  The reference has no such step: its loader takes the coil count
+ * the file holds (mri_data.py:283); this engine captures graphs per shape, so a fixed number of virtual coils keeps one graph set.
+ * cine_coil_gram: gram (c, c) complex128 (double pairs, row-major), gram[i][j] = sum_{t < t_use} sum_{(x, y) in R} raw[t, x, y, i] *
+ * conj(raw[t, x, y, j]) over the central rx x ry block of k-space, rx = min(region, nx), ry = min(region, ny), x0 = nx / 2 - rx / 2,
+ * y0 = ny / 2 - ry / 2; region 0 = the whole matrix.  Exact float32 products added in float64 in an order fixed by the shape (no
+ * atomics): exactly Hermitian, repeated calls are bit-identical.  ws_bytes >= cine_coil_gram_ws_bytes(t_use, nx, ny, c, region)
+ * (0 for invalid shapes and for more than 128 coils).
+ * cine_coil_compress: out (t_out, nx, ny, v) complex, out[t, x, y, j] = sum_k matrix[j][k] raw[t, x, y, k] with matrix (v, c) complex
+ * row-major (the leading eigenvectors of gram, conjugated; the eigen-decomposition itself is the caller's): one pass over the
+ * samples, exact fp32 (a k-ordered fmaf chain on v_mfma_f32_16x16x4_f32), repeated calls are bit-identical.
+ * Both: 1 <= t_use, t_out <= t_in, sizes >= 1, region >= 0, 1 <= v <= c, distinct non-null pointers, raw / gram / ws / out 16-byte
+ * aligned (else CINE_EINVAL); at most 128 coils and 32 virtual coils (else CINE_EUNSUPPORTED, the limit is in the message). */
+size_t cine_coil_gram_ws_bytes(int t, int nx, int ny, int c, int region);
+int cine_coil_gram(const float* raw, double* gram, void* ws, size_t ws_bytes, int t_in, int nx, int ny, int c, int t_use, int region,
+                   void* stream);
+int cine_coil_compress(const float* raw, const float* matrix, float* out, int t_in, int nx, int ny, int c, int t_out, int v,
+                       void* stream);
 /* One axis pass of scipy.ndimage.gaussian_filter as transforms.py:216-217 calls it (mode 'reflect', truncate 4.0, weights and
  * accumulation in float64, float32 result) over a (outer, n, inner) array of complex pairs: the real and imaginary parts
  * are filtered alike.  The caller runs one pass per axis with sigma > 0, in axis order (mri_data.py:279: [0.7, 0, 0.3, 0.3]). */
