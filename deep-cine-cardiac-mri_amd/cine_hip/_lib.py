@@ -132,6 +132,7 @@ _SIGS = {
     "cine_crop_select": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_raw_window_ifft2c": (c_int, [P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "cine_raw_window_ws_bytes": (c_size_t, [c_int] * 6),
+    "cine_raw_ingest": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "cine_coil_gram_ws_bytes": (c_size_t, [c_int] * 5),
     "cine_coil_gram": (c_int, [P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_coil_compress": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),

@@ -8,6 +8,9 @@
                     physical coils projected onto V virtual coils BEFORE the inverse transform.  The reference has no such step; here
                     it gives every scan of a data set the same shape (one SlicePipeline graph set) and lifts the 32-coil cap of the
                     calibration.  ``prepare_slice(..., virtual_coils=V)`` runs it in place.
+``prepare_masked_slice``
+                    prepare_slice's k-space with the row mask applied, device in, device out, capturable by a hipGraph: what
+                    ``SlicePipeline.submit_raw`` runs per slice.  Line-engine raw sizes enter through ops.raw_ingest (kept frames only).
 ``espirit_maps``    what the reference gets from the BART toolbox (``bart ecalib -r N``, mri_data.py:296,
                     transforms.py:429): ESPIRiT sensitivity maps (Uecker et al., MRM 71:990-1001, 2014) with ecalib's
                     defaults -- 6 x 6 kernels, singular-value threshold 0.001, eigenvalue crop 0.8, first map.
@@ -157,10 +160,10 @@ def coil_compression_matrix(raw: torch.Tensor, virtual_coils: int, n_frames: Opt
     return coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils)
 
 
-def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[int] = None) -> torch.Tensor:
+def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[t, x, y, v] = sum_c matrix[v, c] raw[t, x, y, c] for the first min(n_frames, t) frames: raw (t, x, y, coil) complex64, matrix
     (V, coil) complex64 -> (T, x, y, V) complex64, the layout prepare_slice and ops.raw_window_ifft2c take.  Exact fp32, bit-identical
-    from call to call."""
+    from call to call.  ``out``: a contiguous, 16-byte aligned float32 (T, x, y, V, 2) GPU tensor to write into."""
     x = _raw_pairs(raw, "compress_coils")
     t, nx, ny, c, _ = x.shape
     n = _kept_frames(n_frames, t)
@@ -168,7 +171,11 @@ def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[i
         raise ValueError(f"compress_coils: matrix must be (V, {c})")
     v = matrix.shape[0]
     m = ops._dev(torch.view_as_real(matrix.to(torch.complex64)), "compress_coils matrix")
-    out = torch.empty((n, nx, ny, v, 2), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((n, nx, ny, v, 2), device=x.device, dtype=torch.float32)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, nx, ny, v, 2)
+              and out.is_contiguous()):
+        raise CineHipError(f"compress_coils: out must be a contiguous float32 GPU tensor of shape {(n, nx, ny, v, 2)}")
     check(lib().cine_coil_compress(x.data_ptr(), m.data_ptr(), out.data_ptr(), t, nx, ny, c, n, v, ops._stream()), "cine_coil_compress")
     return torch.view_as_complex(out)
 
@@ -229,6 +236,80 @@ def _to_kspace(filt: torch.Tensor) -> torch.Tensor:
     x = torch.roll(filt, shifts=[-1] * len(odd), dims=odd).contiguous() if odd else filt
     kk = ops.fft2c(x)                                                        # fftn(norm=None) / sqrt(N) == ortho (:291-292)
     return torch.roll(kk, shifts=[1] * len(odd), dims=odd).contiguous() if odd else kk
+
+
+def _to_kspace_hip(filt: torch.Tensor) -> torch.Tensor:
+    """_to_kspace with the library's own roll kernel on both sides (a roll is a copy: the same bits)."""
+    odd = [d for d, n in ((-3, filt.shape[-3]), (-2, filt.shape[-2])) if n % 2]
+    x = ops.roll(filt, [-1] * len(odd), odd) if odd else filt
+    kk = ops.fft2c(x)
+    return ops.roll(kk, [1] * len(odd), odd) if odd else kk
+
+
+def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_shape=(200, 200), n_slices: int = 15,
+                         filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix: Optional[torch.Tensor] = None,
+                         apply_mask: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Raw k-space of one cine slice -> the model's input, device in, device out: ``ops.apply_mask(prepare_slice(raw, ...)[0], mask)[None]``
+    bit for bit, without a host synchronisation, a data-dependent shape or a launch outside the current stream, so that
+    ``torch.cuda.graph`` captures it on any stream (run it once eagerly on that stream first, like a model's forward).  This is what
+    ``SlicePipeline.submit_raw`` replays per slice.
+
+    raw   (t, x, y, coil) complex64 or (t, x, y, coil, 2) float32 on the GPU, 16-byte aligned.  Only the first min(n_slices, t) frames are
+          read.  Sizes the FFT line engines take: ops.raw_ingest (scale, coils in front) -> ifft2c of the kept frames -> crop -> Gaussian
+          filter; any other size: ops.raw_window_ifft2c -> filter, as in prepare_slice.  Then the forward transform of the crop with the
+          reference's shift order (mri_data.py:291-292).
+    mask  the row mask on the crop grid, uint8 or bool on the GPU, (1, T | 1, 1, X, 1, 1) (or any shape with T X or X entries in that
+          order).  ``apply_mask=False`` hands the k-space on unmasked -- prospectively undersampled data, where the reference also
+          only passes the stored mask on (data/transforms.py:331-339); ``mask`` may then be None.
+    coil_matrix  A (V, coil) complex64 ON THE GPU: compress_coils first, everything else on V virtual coils.  The per-slice
+          ``virtual_coils=`` of prepare_slice is not offered here: its eigen-decomposition checks the Gram matrix on the host, which
+          waits for the device.  Compute one matrix per scan with coil_compression_matrix and pass it.
+    out   a contiguous float32 (1, T, C, X, Y, 2) GPU tensor to write the result into (the pipeline's static buffer).
+    Returns masked k-space (1, T, C, X, Y, 2) float32."""
+    x = torch.view_as_real(raw) if isinstance(raw, torch.Tensor) and raw.is_complex() and raw.dtype == torch.complex64 else raw
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("prepare_masked_slice: expected a tensor")
+    if not x.is_cuda:
+        raise CineHipError("prepare_masked_slice: the HIP path needs a GPU tensor (no CPU fallback)")
+    if x.dtype != torch.float32 or x.dim() != 5 or x.shape[-1] != 2:
+        raise CineHipError(f"prepare_masked_slice: raw must be (t, x, y, coil) complex64 or (t, x, y, coil, 2) float32, got {tuple(raw.shape)} {raw.dtype}")
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        raise CineHipError("prepare_masked_slice: raw must be contiguous and 16-byte aligned (a copy here would hide a launch from the caller)")
+    t, nx, ny, c, _ = x.shape
+    cx, cy = int(crop_shape[0]), int(crop_shape[1])
+    if not (0 < cx <= nx and 0 < cy <= ny):
+        raise ValueError("Invalid shapes.")                                  # transforms.py:206-207
+    n = _kept_frames(n_slices, t)
+    if coil_matrix is not None:
+        if not isinstance(coil_matrix, torch.Tensor) or coil_matrix.dim() != 2 or coil_matrix.shape[1] != c:
+            raise ValueError(f"coil_matrix must be (V, {c})")
+        if not coil_matrix.is_cuda or coil_matrix.dtype != torch.complex64:
+            raise CineHipError("prepare_masked_slice: coil_matrix must be a complex64 GPU tensor (a host matrix would be copied synchronously)")
+        x = torch.view_as_real(compress_coils(x, coil_matrix, n))            # (n, x, y, V, 2)
+        c = coil_matrix.shape[0]
+    if ops.fft_line_supported(nx) and ops.fft_line_supported(ny):
+        images = ops.fft2c(ops.raw_ingest(x, n, scaling), inverse=True)      # the kept frames only
+        filt = gaussian_filter(crop_select(images, n, (cx, cy)), filter_size)
+    else:
+        filt = gaussian_filter(ops.raw_window_ifft2c(x, n, (cx, cy), scaling), filter_size)
+    kk = _to_kspace_hip(filt)                                                # (n, c, cx, cy, 2)
+    shape = (1, n, c, cx, cy, 2)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape
+                                and out.is_contiguous()):
+        raise CineHipError(f"prepare_masked_slice: out must be a contiguous float32 GPU tensor of shape {shape}")
+    if not apply_mask:
+        return kk.view(shape) if out is None else out.copy_(kk.view(shape))
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool):
+        raise CineHipError("prepare_masked_slice: mask must be a uint8 or bool GPU tensor")
+    m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    if m.numel() == cx and n > 1:
+        m = m.reshape(1, cx).expand(n, cx).contiguous()                      # one pattern for all frames
+    elif m.numel() != n * cx:
+        raise ValueError(f"prepare_masked_slice: mask {tuple(mask.shape)} is not a row mask (1, {n} | 1, 1, {cx}, 1, 1)")
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    ops.apply_mask(kk, m, out=out.view(n, c, cx, cy, 2))
+    return out
 
 
 def espirit_maps(kspace: torch.Tensor, r: int = 24, k: int = 6, thresh: float = 1e-3, crop: float = 0.8,

@@ -341,6 +341,30 @@ def raw_window_ifft2c(raw_txyc: torch.Tensor, n_frames: int, window: Sequence[in
     return out
 
 
+def raw_ingest(raw_txyc: torch.Tensor, n_frames: int, scale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``scale * raw[:n_frames]`` with the coil axis in front of the image axes (reference data/mri_data.py:283-289), in one pass: raw
+    (t, x, y, coil) complex64 or float32 pairs (t, x, y, coil, 2) on the GPU, 16-byte aligned -> (n_frames, coil, x, y, 2) float32, what
+    ``fft2c(inverse=True)`` takes.  Equal, bit for bit, to ``view_as_real((raw[:n_frames] * scale).permute(0, 3, 1, 2).contiguous())``.
+    ``out``: a contiguous, 16-byte aligned float32 tensor of that shape to write into."""
+    if not isinstance(raw_txyc, torch.Tensor):
+        raise TypeError("raw_ingest: expected a tensor")
+    x = torch.view_as_real(raw_txyc) if raw_txyc.is_complex() else raw_txyc
+    if x.dim() != 5 or x.shape[-1] != 2:
+        raise ValueError("raw_ingest expects (t, x, y, coil) complex or (t, x, y, coil, 2) pairs")
+    x = _dev(x, "raw_ingest input")
+    t, nx, ny, c, _ = x.shape
+    n_frames = int(n_frames)
+    if not (0 < n_frames <= t and nx > 0 and ny > 0 and c > 0):
+        raise ValueError("Invalid shapes.")
+    shape = (n_frames, c, nx, ny, 2)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.float32)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+        raise CineHipError(f"raw_ingest: out must be a contiguous float32 GPU tensor of shape {shape}")
+    check(lib().cine_raw_ingest(x.data_ptr(), out.data_ptr(), t, nx, ny, c, n_frames, float(scale), _stream()), "cine_raw_ingest")
+    return out
+
+
 # ------------------------------------------------------------------ coil operators
 def sens_reduce(k: torch.Tensor, sens: torch.Tensor, magnitude: bool = False,
                 destroy_input: bool = False) -> torch.Tensor:

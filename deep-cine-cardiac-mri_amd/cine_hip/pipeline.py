@@ -47,6 +47,18 @@ Shapes: the graphs, buffers and events form one SET keyed by the input shapes an
 with a new key drains the pending slices (their results stay queued), frees the old set and builds a new one (one eager
 forward per slot stream, then two captures per slot).
 
+Raw input (``submit_raw``): the raw k-space ``(t, x, y, coil)`` of a slice, complex64 or float32 pairs, from the same four places.  Only
+``raw[:min(n_frames, t)]`` -- a contiguous prefix -- is copied, on the copy stream, into a raw buffer of the slice's (slot, parity); the
+graph of that (slot, parity) then holds ``frontend.prepare_masked_slice`` (scaling, inverse transform, crop, Gaussian filter, forward
+transform, masking, written into the static k-space buffer) AND the model's forward that reads it.  Same events, same schedule, same
+streams.  The set key of raw input is ``raw_set_key(...)``: kind, kept raw shape, crop, filter, scaling, apply_mask, mask shape, sens
+shape; ``submit`` and ``submit_raw`` may alternate, a change of kind is a change of key.  With ``coil_matrix=A`` (V, coil) the matrix is
+copied with the raw data and ``compress_coils`` runs eagerly on the slot's stream in front of the replay, into a static (T, x, y, V)
+buffer the graph starts from: the coil count is not part of the key, scans with different coil counts and one V share a set, and the
+raw buffers (plain byte buffers then) are replaced by larger ones, after a drain, when a larger scan arrives.  ``2 * slots`` raw
+buffers are checked against ``torch.cuda.mem_get_info`` before they are allocated.  A raw slice's copy is long (5.5 ms for 311 MB):
+on a hardware queue shared with slot streams it waits behind whole replays, so the ``slots + 1`` queues above matter more here.
+
 ``graphs=False`` is the explicit eager mode: same slots, streams, buffers, copies and events, with the launch sequence
 enqueued on the slot's stream for every slice.  A failure raises ``CineHipError``; nothing falls back to eager launches.
 
@@ -59,7 +71,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import ops
+from . import frontend, ops
 from ._lib import CineHipError
 
 
@@ -186,48 +198,169 @@ def _mask_shape(mask_shape, ks_shape):
     return (b, t, 1, h, m[4], 1)
 
 
+def _check_mask(mask, ks_shape):
+    """(mask as given or canonical host uint8, kind, the shape its buffer has)."""
+    if isinstance(mask, np.ndarray):
+        mask = torch.from_numpy(mask)
+    if not isinstance(mask, torch.Tensor):
+        raise CineHipError(f"mask: expected a torch tensor or a numpy array, got {type(mask).__name__}")
+    want = _mask_shape(mask.shape, ks_shape)
+    if mask.is_cuda:
+        if mask.dtype not in (torch.uint8, torch.bool):
+            raise CineHipError(f"mask: a device mask must be uint8 or bool (got {mask.dtype}); pass other dtypes from the host")
+        return mask, "device", want
+    m = mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
+    m = m.expand(want)
+    canonical = m.is_contiguous() and m.is_pinned()
+    return (m, "pinned", want) if canonical else (m.contiguous(), "pageable", want)
+
+
+def _check_sens(pipe, sens_maps, ks_shape, general: bool):
+    """(float32 pairs or None, kind or None)."""
+    b, _, c, h, w, _ = ks_shape
+    if sens_maps is not None:
+        if not pipe._takes_sens:
+            raise CineHipError(f"{type(pipe.model).__name__} takes no sens_maps")
+        s, kind = _pairs(sens_maps, "sens_maps")
+        if tuple(s.shape) != (b, 1, c, h, w, 2):
+            raise CineHipError(f"sens_maps: shape {tuple(s.shape)}; expected {(b, 1, c, h, w, 2)} for this k-space")
+        return s, kind
+    if pipe._needs_sens:
+        raise CineHipError(f"{type(pipe.model).__name__} needs sens_maps")
+    if general:
+        raise CineHipError("the mask varies along w: the ACS window of the sensitivity network is found on the device from row masks "
+                           "only; pass sens_maps (VarNet) or use a row mask (b|1, t|1, 1, h, 1, 1)")
+    return None, None
+
+
+def _same_device(pipe, named):
+    for name, x in named:
+        if x is not None and x.is_cuda and x.device != pipe.device:
+            raise CineHipError(f"{name} is on {x.device}, the pipeline's device is {pipe.device}")
+
+
 class _Source:
     """One slice's validated inputs: torch views in their original place, the canonical mask, the set key."""
+    raw = None                                      # no front-end in this set's graphs
+    input_names = ("mk", "mask", "sens")
 
     def __init__(self, pipe, masked_kspace, mask, sens_maps):
         mk, self.mk_kind = _pairs(masked_kspace, "masked_kspace")
         if mk.dim() != 6:
             raise CineHipError(f"masked_kspace: shape {tuple(mk.shape)}; expected (b, t, c, h, w, 2) or complex (b, t, c, h, w)")
         self.mk = mk
-        b, t, c, h, w, _ = mk.shape
-        if isinstance(mask, np.ndarray):
-            mask = torch.from_numpy(mask)
-        if not isinstance(mask, torch.Tensor):
-            raise CineHipError(f"mask: expected a torch tensor or a numpy array, got {type(mask).__name__}")
-        want = _mask_shape(mask.shape, mk.shape)
-        if mask.is_cuda:
-            if mask.dtype not in (torch.uint8, torch.bool):
-                raise CineHipError(f"mask: a device mask must be uint8 or bool (got {mask.dtype}); pass other dtypes from the host")
-            self.mask, self.mask_kind = mask, "device"
-        else:
-            m = mask if mask.dtype == torch.uint8 else (mask != 0).to(torch.uint8)
-            m = m.expand(want)
-            canonical = m.is_contiguous() and m.is_pinned()
-            self.mask, self.mask_kind = (m, "pinned") if canonical else (m.contiguous(), "pageable")
-        self.mask_shape = want
-        general = want[4] > 1
-        self.sens, self.sens_kind = None, None
-        if sens_maps is not None:
-            if not pipe._takes_sens:
-                raise CineHipError(f"{type(pipe.model).__name__} takes no sens_maps")
-            s, self.sens_kind = _pairs(sens_maps, "sens_maps")
-            if tuple(s.shape) != (b, 1, c, h, w, 2):
-                raise CineHipError(f"sens_maps: shape {tuple(s.shape)}; expected {(b, 1, c, h, w, 2)} for this k-space")
-            self.sens = s
-        elif pipe._needs_sens:
-            raise CineHipError(f"{type(pipe.model).__name__} needs sens_maps")
-        elif general:
-            raise CineHipError("the mask varies along w: the ACS window of the sensitivity network is found on the device from row masks "
-                               "only; pass sens_maps (VarNet) or use a row mask (b|1, t|1, 1, h, 1, 1)")
-        for name, x in (("masked_kspace", self.mk), ("mask", self.mask), ("sens_maps", self.sens)):
-            if x is not None and x.is_cuda and x.device != pipe.device:
-                raise CineHipError(f"{name} is on {x.device}, the pipeline's device is {pipe.device}")
-        self.key = (tuple(mk.shape), want, None if self.sens is None else tuple(self.sens.shape))
+        self.mk_shape = tuple(mk.shape)
+        self.mask, self.mask_kind, self.mask_shape = _check_mask(mask, mk.shape)
+        self.sens, self.sens_kind = _check_sens(pipe, sens_maps, mk.shape, self.mask_shape[4] > 1)
+        _same_device(pipe, (("masked_kspace", self.mk), ("mask", self.mask), ("sens_maps", self.sens)))
+        self.key = (tuple(mk.shape), self.mask_shape, None if self.sens is None else tuple(self.sens.shape))
+
+    def alloc(self, pipe):
+        dev = pipe.device
+        return {"mk": torch.empty(self.mk_shape, device=dev, dtype=torch.float32),
+                "mask": torch.empty(self.mask_shape, device=dev, dtype=torch.uint8),
+                "sens": None if self.sens is None else torch.empty(self.sens.shape, device=dev, dtype=torch.float32)}
+
+    def items(self, b):
+        """(name, destination in buffer set b, source, kind) of every input the copy stream moves."""
+        it = [("mk", b["mk"], self.mk, self.mk_kind), ("mask", b["mask"], self.mask, self.mask_kind)]
+        if self.sens is not None:
+            it.append(("sens", b["sens"], self.sens, self.sens_kind))
+        return it
+
+
+_CC_MAX_COILS, _CC_MAX_VIRTUAL = 128, 32            # the limits of cine_coil_compress (include/cine_hip.h)
+
+
+def raw_set_key(raw_shape, n_frames, crop_shape, filter_size, scaling, apply_mask, mask_shape, sens_shape, coil_matrix_shape=None):
+    """The key of the graph set that serves a ``submit_raw`` call, from shapes and settings alone: kind, kept raw shape, virtual coils,
+    crop, filter, scaling, apply_mask, mask shape, sens shape.  With a coil matrix the raw coil count is NOT part of it: the compression
+    runs in front of the graph, so scans with different coil counts and one V share a set."""
+    t, nx, ny, c = (int(v) for v in tuple(raw_shape)[:4])
+    n = min(int(n_frames), t)
+    if n < 1 or nx < 1 or ny < 1 or c < 1:
+        raise ValueError("Invalid shapes.")
+    kept = (n, nx, ny, c) if coil_matrix_shape is None else (n, nx, ny)
+    v = None if coil_matrix_shape is None else int(tuple(coil_matrix_shape)[0])
+    return ("raw", kept, v, (int(crop_shape[0]), int(crop_shape[1])), tuple(float(f) for f in filter_size), float(scaling),
+            bool(apply_mask), tuple(int(m) for m in mask_shape), None if sens_shape is None else tuple(int(m) for m in sens_shape))
+
+
+class _RawSource:
+    """One raw slice's validated inputs (``submit_raw``): the kept frames of the raw data in their original place, mask, sens, the coil
+    matrix, the front-end's settings, the set key."""
+    input_names = ("raw", "mask", "sens", "cmat")
+
+    def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask):
+        if not isinstance(raw, (np.ndarray, torch.Tensor)):
+            raise CineHipError(f"raw: expected a torch tensor or a numpy array, got {type(raw).__name__}")
+        if raw.ndim < 4 or raw.shape[0] < 1 or int(n_frames) < 1:
+            raise ValueError("Invalid shapes.")
+        x, self.raw_kind = _pairs(raw[:min(int(n_frames), raw.shape[0])], "raw")     # the frame axis is the slowest: a contiguous prefix
+        if x.dim() != 5:
+            raise CineHipError(f"raw: shape {tuple(x.shape)}; expected (t, x, y, coil) complex64 or (t, x, y, coil, 2) float32")
+        self.raw = x
+        n, nx, ny, c, _ = x.shape
+        self.n, self.c = n, c
+        self.crop = (int(crop_shape[0]), int(crop_shape[1]))
+        if not (0 < self.crop[0] <= nx and 0 < self.crop[1] <= ny):
+            raise ValueError("Invalid shapes.")                              # transforms.py:206-207
+        self.filter = tuple(float(f) for f in filter_size)
+        if len(self.filter) != 4:
+            raise CineHipError("filter_size: one sigma per axis of (t, coil, x, y)")
+        self.scaling, self.apply_mask = float(scaling), bool(apply_mask)
+        self.cmat, self.cmat_kind = None, None
+        if coil_matrix is not None:
+            a, self.cmat_kind = _pairs(coil_matrix, "coil_matrix")
+            if a.dim() != 3 or a.shape[1] != c:
+                raise CineHipError(f"coil_matrix: shape {tuple(a.shape[:-1])}; expected (V, {c}) for this scan's {c} coils")
+            if not (1 <= a.shape[0] <= min(c, _CC_MAX_VIRTUAL) and c <= _CC_MAX_COILS):
+                raise CineHipError(f"coil_matrix (V, coil) = {tuple(a.shape[:-1])}: 1 <= V <= coil, at most {_CC_MAX_VIRTUAL} virtual and "
+                                   f"{_CC_MAX_COILS} physical coils")
+            self.cmat = a
+        self.v = None if self.cmat is None else self.cmat.shape[0]
+        self.mk_shape = (1, n, self.v or c, self.crop[0], self.crop[1], 2)
+        self.mask, self.mask_kind, self.mask_shape = _check_mask(mask, self.mk_shape)
+        if self.mask_shape[4] > 1:
+            raise CineHipError("submit_raw: the front-end applies row masks (1, t|1, 1, X, 1, 1) only")
+        self.sens, self.sens_kind = _check_sens(pipe, sens_maps, self.mk_shape, False)
+        _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat)))
+        self.raw_nbytes = x.numel() * 4
+        self.key = raw_set_key((n, nx, ny, c), n, self.crop, self.filter, self.scaling, self.apply_mask, self.mask_shape,
+                               None if self.sens is None else self.sens.shape, None if self.cmat is None else self.cmat.shape)
+
+    def alloc(self, pipe):
+        """raw: a byte buffer (with a coil matrix it may be replaced by a larger one later: no graph holds its address).  cc: what the
+        eager compression writes and the graph reads.  mk: written and read inside the graph."""
+        dev = pipe.device
+        n, nx, ny = self.raw.shape[:3]
+        b = {"raw": torch.empty(self.raw_nbytes, device=dev, dtype=torch.uint8),
+             "cmat": None if self.v is None else torch.empty(self.v * _CC_MAX_COILS * 8, device=dev, dtype=torch.uint8),
+             "cc": None if self.v is None else torch.empty((n, nx, ny, self.v, 2), device=dev, dtype=torch.float32),
+             "mk": torch.empty(self.mk_shape, device=dev, dtype=torch.float32),
+             "mask": torch.empty(self.mask_shape, device=dev, dtype=torch.uint8),
+             "sens": None if self.sens is None else torch.empty(self.sens.shape, device=dev, dtype=torch.float32)}
+        b["front"] = b["cc"] if self.v is not None else self.raw_view(b)
+        return b
+
+    def raw_view(self, b):
+        return b["raw"][:self.raw_nbytes].view(torch.float32).view(self.raw.shape)
+
+    def cmat_view(self, b):
+        return b["cmat"][:self.cmat.numel() * 4].view(torch.float32).view(self.cmat.shape)
+
+    def items(self, b):
+        it = [("raw", self.raw_view(b), self.raw, self.raw_kind), ("mask", b["mask"], self.mask, self.mask_kind)]
+        if self.sens is not None:
+            it.append(("sens", b["sens"], self.sens, self.sens_kind))
+        if self.cmat is not None:
+            it.append(("cmat", self.cmat_view(b), self.cmat, self.cmat_kind))
+        return it
+
+
+def _settings_only(src: "_RawSource"):
+    """The front-end's settings of a raw set, without the tensors of the slice that built it."""
+    return collections.namedtuple("RawSettings", "crop n filter scaling apply_mask")(src.crop, src.n, src.filter, src.scaling, src.apply_mask)
 
 
 class SliceHandle:
@@ -246,7 +379,9 @@ class _Set:
 
     def __init__(self, key):
         self.key = key
-        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"}
+        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front" in a raw set)
+        self.raw = None         # the front-end's settings when the graphs start from raw data (the _RawSource that built the set)
+        self.raw_bytes = 0      # capacity of each raw byte buffer
         self.graphs = {}        # (slot, parity) -> (graph, static outputs)
         self.ready = {}         # (slot, parity) -> event recorded on the copy stream behind the copy into the set
         self.done = {}          # (slot, parity) -> event recorded on the slot stream behind the output copy of the set's reader
@@ -286,6 +421,7 @@ class SlicePipeline:
         self._recs = {}           # index -> [handle, outputs, inputs kept alive until the slice is done]
         self._set = None
         self._closed = False
+        self._builds = 0
         self.streams, self.copy_stream = pipeline_streams(device, slots)
 
     # ---- public ----------------------------------------------------------------------------------------------------------
@@ -293,13 +429,32 @@ class SlicePipeline:
         """Enqueue one slice.  Returns at once, unless 2 x slots slices are pending: then it waits for the oldest one."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit after close()")
-        src = _Source(self, masked_kspace, mask, sens_maps)
+        return self._submit(_Source(self, masked_kspace, mask, sens_maps), tag)
+
+    def submit_raw(self, raw, mask, sens_maps=None, tag=None, *, crop_shape=(200, 200), n_frames: int = 15,
+                   filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True) -> SliceHandle:
+        """Enqueue one slice from its RAW k-space (t, x, y, coil) -- complex64 or float32 pairs, in any of the four places ``submit`` takes
+        its input from.  Only ``raw[:min(n_frames, t)]`` is copied to the device.  ``frontend.prepare_masked_slice`` and the model run on
+        the slot's stream inside the slot's graph; see the module docstring.  ``mask``: the row mask on the crop grid; ``sens_maps``
+        (1, 1, C, X, Y, 2) on the crop grid (on the V virtual coils with ``coil_matrix`` (V, coil))."""
+        if self._closed:
+            raise CineHipError("SlicePipeline: submit_raw after close()")
+        return self._submit(_RawSource(self, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask), tag)
+
+    @property
+    def set_builds(self) -> int:
+        """How many graph sets this pipeline has built so far (one per change of the set key)."""
+        return self._builds
+
+    def _submit(self, src, tag) -> SliceHandle:
         with torch.cuda.device(self.device):
             if self._set is None or self._set.key != src.key:
                 self._retire_all()
                 self._set = None                               # one set alive: the old graphs and buffers go first
                 self._sched.new_buffers()
                 self._set = self._build(src)
+            elif src.raw is not None and src.raw_nbytes > self._set.raw_bytes:
+                self._grow_raw(src.raw_nbytes)                 # a scan with more coils than any before it (coil_matrix given)
             k0 = self._sched.must_retire()
             if k0 is not None:
                 self._recs[k0][0]._event.synchronize()
@@ -310,7 +465,7 @@ class SlicePipeline:
             h = SliceHandle(step.index, step.index if tag is None else tag, step.slot, step.parity, ev_done)
             try:
                 keep = self._copy_in(src, key, wait_done=step.copy_after is not None)
-                outs = self._launch(key)
+                outs = self._launch(key, src)
             except Exception:
                 self._recs[step.index] = [h, None, None]
                 raise
@@ -386,17 +541,59 @@ class SlicePipeline:
                 raise CineHipError(f"SlicePipeline: {type(self.model).__name__}.forward returned {type(o).__name__}, not a tensor")
             return (o, ops.zero_filled_rss(b["mk"])) if self.zero_filled else (o,)
 
-    def _build(self, src: _Source) -> _Set:
+    def _pre(self, b, src) -> None:
+        """What runs eagerly on the slot's stream in front of the graph: with a coil matrix, the compression of this scan's raw data
+        (any coil count) into the static (T, x, y, V) buffer the graph starts from."""
+        if src.raw is not None and src.cmat is not None:
+            with torch.no_grad():
+                frontend.compress_coils(src.raw_view(b), torch.view_as_complex(src.cmat_view(b)), src.n, out=b["cc"])
+
+    def _body(self, b):
+        """The slice's launch sequence on the current stream, the part a graph holds: the front-end of a raw set, the model's forward
+        (+ the zero-filled image)."""
+        r = self._set.raw
+        if r is not None:
+            with torch.no_grad():
+                frontend.prepare_masked_slice(b["front"], b["mask"], r.crop, r.n, r.filter, r.scaling, None, r.apply_mask, out=b["mk"])
+        return self._run(b)
+
+    def _raw_memory(self, nbytes: int) -> None:
+        """2 x slots raw buffers of nbytes each have to fit into the free memory the driver reports: no silent fallback."""
+        need = 2 * self.slots * nbytes
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free:
+            raise CineHipError(f"SlicePipeline: {2 * self.slots} raw buffers of {nbytes} bytes need {need} bytes, {free} are free on "
+                               f"{self.device}; slots={int(free // (2 * nbytes))} would fit")
+
+    def _grow_raw(self, nbytes: int) -> None:
+        """Larger raw byte buffers for every (slot, parity).  Only a set with a coil matrix gets here: its graphs start from the
+        compressed buffer, so nothing has to be captured again."""
+        self._retire_all()
+        st = self._set
+        for b in st.bufs.values():
+            b["raw"] = None
+        self._raw_memory(nbytes)
+        try:
+            for b in st.bufs.values():
+                b["raw"] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+        except Exception as e:
+            self._set = None
+            raise CineHipError(f"SlicePipeline: allocating raw buffers of {nbytes} bytes failed: {type(e).__name__}: {e}") from e
+        st.raw_bytes = nbytes
+
+    def _build(self, src) -> _Set:
         """Buffers for every (slot, parity), filled with this slice's inputs; with graphs, one eager forward per slot stream
         (per-stream caches are filled outside capture) and one capture per buffer set."""
         S, dev = self.slots, self.device
+        self._builds += 1
         st = _Set(src.key)
         try:
+            if src.raw is not None:
+                self._raw_memory(src.raw_nbytes)
+                st.raw, st.raw_bytes = _settings_only(src), src.raw_nbytes     # the settings, not the first slice's data
             for i in range(S):
                 for p in (0, 1):
-                    st.bufs[(i, p)] = {"mk": torch.empty(src.mk.shape, device=dev, dtype=torch.float32),
-                                       "mask": torch.empty(src.mask_shape, device=dev, dtype=torch.uint8),
-                                       "sens": None if src.sens is None else torch.empty(src.sens.shape, device=dev, dtype=torch.float32)}
+                    st.bufs[(i, p)] = src.alloc(self)
                     st.ready[(i, p)] = torch.cuda.Event()
                     st.done[(i, p)] = torch.cuda.Event()
             self._set = st
@@ -405,7 +602,7 @@ class SlicePipeline:
                 b0 = st.bufs[(0, 0)]
                 for key, b in st.bufs.items():
                     if key != (0, 0):
-                        for name in ("mk", "mask", "sens"):
+                        for name in src.input_names:
                             if b[name] is not None:
                                 b[name].copy_(b0[name])
             self.copy_stream.synchronize()
@@ -414,12 +611,14 @@ class SlicePipeline:
                     s = self.streams[i]
                     s.wait_stream(torch.cuda.current_stream(dev))
                     with torch.cuda.stream(s):
-                        self._run(st.bufs[(i, 0)])                 # warm this stream's caches outside capture
+                        for p in (0, 1):
+                            self._pre(st.bufs[(i, p)], src)
+                        self._body(st.bufs[(i, 0)])                # warm this stream's caches outside capture
                     s.synchronize()
                     for p in (0, 1):
                         g = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(g, stream=s):
-                            o = self._run(st.bufs[(i, p)])
+                            o = self._body(st.bufs[(i, p)])
                         st.graphs[(i, p)] = (g, o)
                 torch.cuda.synchronize(dev)
         except CineHipError:
@@ -430,51 +629,54 @@ class SlicePipeline:
             raise CineHipError(f"SlicePipeline: setting up {type(self.model).__name__} for inputs {src.key} failed: {type(e).__name__}: {e}") from e
         return st
 
-    def _staging(self, src: _Source):
-        """The next of the two pinned staging sets for pageable inputs (waits until the copy out of it has finished)."""
+    def _staging(self, items):
+        """The next of the two pinned staging sets for pageable inputs (waits until the copy out of it has finished): a view of the
+        destination's shape for every pageable item."""
         st = self._set
         if st.stage is None:
-            def pinned(shape, dtype):
-                return torch.empty(shape, dtype=dtype, pin_memory=True)
-            st.stage = [{"mk": pinned(src.mk.shape, torch.float32), "mask": pinned(src.mask_shape, torch.uint8),
-                         "sens": None if src.sens is None else pinned(src.sens.shape, torch.float32)} for _ in range(2)]
+            st.stage = [{}, {}]
             st.stage_ev = [None, None]
         r = st.stage_next
         st.stage_next ^= 1
         if st.stage_ev[r] is not None:
             st.stage_ev[r].synchronize()
-        return r, st.stage[r]
+        views = {}
+        for name, dst, _, kind in items:
+            if kind == "pageable":
+                nbytes = dst.numel() * dst.element_size()
+                buf = st.stage[r].get(name)
+                if buf is None or buf.numel() < nbytes:
+                    buf = st.stage[r][name] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                views[name] = buf[:nbytes].view(dst.dtype).view(dst.shape)
+        return r, views
 
-    def _copy_in(self, src: _Source, key, wait_done: bool):
+    def _copy_in(self, src, key, wait_done: bool):
         """The slice's inputs into buffer set `key` on the copy stream, after the set's previous reader; records the set's
         ready-event.  Returns what has to stay alive until the slice is done."""
         st = self._set
-        b = st.bufs[key]
         cs = self.copy_stream
         keep = []
-        items = [("mk", src.mk, src.mk_kind), ("mask", src.mask, src.mask_kind)]
-        if src.sens is not None:
-            items.append(("sens", src.sens, src.sens_kind))
+        items = src.items(st.bufs[key])
         stage = None
-        if any(kind == "pageable" for _, _, kind in items):
-            r, stage = self._staging(src)
-            for name, x, kind in items:
+        if any(kind == "pageable" for _, _, _, kind in items):
+            r, stage = self._staging(items)
+            for name, _, x, kind in items:
                 if kind == "pageable":
                     stage[name].copy_(x)                           # the host memcpy of a pageable input
-        if any(kind == "device" for _, _, kind in items):
+        if any(kind == "device" for _, _, _, kind in items):
             cs.wait_stream(torch.cuda.current_stream(self.device))
         if wait_done:
             cs.wait_event(st.done[key])
         with torch.cuda.stream(cs):
-            for name, x, kind in items:
+            for name, dst, x, kind in items:
                 if kind == "pageable":
-                    b[name].copy_(stage[name], non_blocking=True)
+                    dst.copy_(stage[name], non_blocking=True)
                 elif kind == "device":
-                    b[name].copy_(x.expand(b[name].shape) if name == "mask" else x, non_blocking=True)
+                    dst.copy_(x.expand(dst.shape) if name == "mask" else x, non_blocking=True)
                     x.record_stream(cs)
                     keep.append(x)
                 else:
-                    b[name].copy_(x, non_blocking=True)
+                    dst.copy_(x, non_blocking=True)
                     keep.append(x)
             st.ready[key].record(cs)
             if stage is not None:
@@ -483,12 +685,13 @@ class SlicePipeline:
                 st.stage_ev[r] = ev
         return keep
 
-    def _launch(self, key):
+    def _launch(self, key, src):
         """Slice on set `key`: on the slot's stream, wait for its inputs, replay (or launch), copy the outputs out, record done."""
         st = self._set
         s = self.streams[key[0]]
         with torch.cuda.stream(s):
             s.wait_event(st.ready[key])
+            self._pre(st.bufs[key], src)
             if self.graphs:
                 g, static = st.graphs[key]
                 g.replay()
@@ -498,7 +701,7 @@ class SlicePipeline:
                     outs = tuple(torch.empty_like(o).copy_(o, non_blocking=True) for o in static)
             else:
                 try:
-                    outs = self._run(st.bufs[key])
+                    outs = self._body(st.bufs[key])
                 except CineHipError:
                     raise
                 except Exception as e:

@@ -9,7 +9,18 @@ outputs returned as device tensors and as pinned host tensors (out="host").  One
 once); every region submits `slices` slices, takes the finished ones as it goes (results()), drains, and is timed from
 the first submit to the last result.  Compare `value_device_in` with bench.py's `value` and `value_pinned_in` with
 its `value_with_h2d` (run bench.py --full beside it).  `host_copy_GBps` is the host memcpy rate of one slice's
-k-space from a numpy array into a pinned buffer (what a pageable input costs inside submit)."""
+k-space from a numpy array into a pinned buffer (what a pageable input costs inside submit).
+
+    python tools/pipeline_rate.py --raw [--slots 10] [--slices 40] [--warmup 8] [--repeats 3] [--out profiles/raw_pipeline_rate.json]
+
+RAW k-space in, reconstruction out (``SlicePipeline.submit_raw``), config 2's model, three scans: 25 x 384 x 144 x 15 (the FFT line
+engines; crop 200 x 144), 25 x 416 x 208 x 30 (the windowed transform; crop 200 x 200) and the latter compressed 30 -> 15 coils with a
+given matrix.  Per scan, slices/s (median of --repeats regions, warm-up outside the clock) for pinned, numpy and device-resident
+raw, and beside them "today's way" in the same process: ``torch.as_tensor(raw).cuda()`` -> ``prepare_slice`` -> ``ops.apply_mask`` ->
+``submit``.  ``h2d_*``: the bytes one slice moves to the device and the rate that copy ALONE allows (pinned -> HBM on one stream,
+nothing else running); ``bound``: which of the two, that copy or the GPU (the device-resident rate), is the lower and so limits a
+pinned input, and ``pinned_over_limit`` how close the pinned rate comes to it.  Also the ingest kernel alone (hipEvent median) as a
+fraction of the device's copy rate measured in the same run.  Without --raw the output is unchanged."""
 import argparse
 import json
 import os
@@ -21,6 +32,8 @@ for p in (ROOT, os.path.join(ROOT, "deep-cine-cardiac-mri_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")        # before the first HIP call, as bench.py does
+if "--hw-queues" in sys.argv[1:-1]:                     # an explicit count (at most 32) overrides the environment's
+    os.environ["GPU_MAX_HW_QUEUES"] = str(min(32, int(sys.argv[sys.argv.index("--hw-queues") + 1])))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -42,13 +55,202 @@ def region(pipe, inputs, n):
     return time.perf_counter() - t0, got
 
 
+RAW_SCANS = (("line_384x144x15", (25, 384, 144, 15), None), ("window_416x208x30", (25, 416, 208, 30), None),
+             ("window_416x208x30_to_15", (25, 416, 208, 30), 15))
+FRAMES, FILTER, SCALING = 15, (0.7, 0.0, 0.3, 0.3), 1e6
+
+
+def _median(xs):
+    xs = sorted(xs)
+    return xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2])
+
+
+def _event_ms(fn, reps, warmup=3):
+    """hipEvent times of `reps` calls of fn on the current stream, after `warmup` calls."""
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
+def _stamp(commit):
+    """(commit, sha256 over the sources under csrc/): which code the numbers belong to."""
+    import hashlib
+    import subprocess
+    if commit is None:
+        try:
+            commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
+        except Exception:
+            commit = None
+    csrc = os.path.join(ROOT, "deep-cine-cardiac-mri_amd", "csrc")
+    h = hashlib.sha256()
+    for name in sorted(os.listdir(csrc)):
+        path = os.path.join(csrc, name)
+        if os.path.isfile(path):
+            h.update(name.encode()); h.update(open(path, "rb").read())
+    return commit, h.hexdigest()
+
+
+def raw_main(args):
+    import bench
+    from cine_hip import frontend as FE, ops, synth
+    from cine_hip.pipeline import SlicePipeline
+    cfg = bench.CONFIGS[2]()
+    dev = torch.device("cuda:0")
+    S, n, warm, reps = args.slots, args.slices or 40, args.warmup if args.warmup is not None else 8, args.repeats
+    net = cfg["hip"]().eval()
+    synth.fill_parameters_(net, cfg["wseed"], keep=cfg["keep"])
+    net = net.to(dev)
+    commit, csrc = _stamp(args.commit)
+    want_forms = set(args.forms.split(","))
+    doc = {"metric": "cine slices/sec from raw k-space through SlicePipeline.submit_raw", "config": 2, "name": cfg["name"], "slots": S,
+           "slices_per_region": n, "warmup_slices": warm, "regions": reps, "statistic": "median of the regions",
+           "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "device": torch.cuda.get_device_name(dev), "commit": commit,
+           "csrc_sha256": csrc, "torch_threads": torch.get_num_threads(), "scans": []}
+
+    # the device's copy rate (read + write bytes of a 1 GiB device-to-device copy), then the ingest kernel against it
+    src = torch.empty(1 << 28, dtype=torch.float32, device=dev).normal_()
+    dst = torch.empty_like(src)
+    copy_ms = _median(_event_ms(lambda: dst.copy_(src), 10))
+    doc["device_copy_TBps"] = 2 * src.numel() * 4 / copy_ms / 1e9
+    del src, dst
+    doc["ingest_kernel"] = []
+    for shape in ((15, 384, 144, 15), (15, 200, 200, 30)):
+        x = torch.empty(shape + (2,), dtype=torch.float32, device=dev).normal_()
+        out = torch.empty((shape[0], shape[3], shape[1], shape[2], 2), dtype=torch.float32, device=dev)
+        ms = _event_ms(lambda: ops.raw_ingest(x, shape[0], SCALING, out=out), 20)
+        tbps = 2 * x.numel() * 4 / _median(ms) / 1e9
+        doc["ingest_kernel"].append({"shape": list(shape), "median_ms": _median(ms), "min_ms": min(ms), "launches": len(ms), "TBps": tbps,
+                                     "frac_of_device_copy_rate": tbps / doc["device_copy_TBps"]})
+        del x, out
+
+    n_raws = 4                                                   # distinct scans cycled through (519 MB each on the host at 416 x 208 x 30)
+    for name, shape, V in RAW_SCANS:
+        t, nx, ny, c = shape
+        crop = (min(200, nx), min(200, ny))
+        rng = np.random.default_rng(nx + c)
+        raws = [(1e-6 * rng.standard_normal(shape + (2,), dtype=np.float32)).view(np.complex64)[..., 0] for _ in range(n_raws)]
+        masks = []
+        for j in range(n_raws):
+            m = (rng.uniform(size=(1, FRAMES, 1, crop[0], 1, 1)) < 0.25).astype(np.uint8)
+            m[:, :, :, crop[0] // 2 - 8 - j:crop[0] // 2 + 8 + j] = 1
+            masks.append(torch.from_numpy(m))
+        mats = [FE.coil_compression_matrix(torch.from_numpy(r[:FRAMES]).to(dev), V, FRAMES)[0] for r in raws] if V else [None] * n_raws
+        kw = dict(crop_shape=crop, n_frames=FRAMES, filter_size=FILTER, scaling=SCALING)
+        kept = [torch.from_numpy(r[:FRAMES]) for r in raws]
+        forms = {"pinned": [k.pin_memory() for k in kept], "numpy": raws, "device": [k.to(dev) for k in kept]}
+        dmasks = [m.to(dev) for m in masks]
+        row = {"scan": name, "raw_shape": list(shape), "crop": list(crop), "frames": FRAMES, "virtual_coils": V,
+               "h2d_bytes_per_slice": kept[0].numel() * 8, "h2d_bytes_per_slice_todays_way": raws[0].size * 8}
+
+        # the copy alone: the kept frames, pinned -> HBM, one stream, nothing else running
+        buf = [torch.empty_like(forms["device"][0]) for _ in range(2)]
+        cs = torch.cuda.Stream()
+        rates = []
+        for _ in range(reps + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with torch.cuda.stream(cs):
+                for k in range(12):
+                    buf[k & 1].copy_(forms["pinned"][k % n_raws], non_blocking=True)
+            torch.cuda.synchronize()
+            rates.append(12 / (time.perf_counter() - t0))
+        del buf
+        row["h2d_alone_slices_per_s"] = _median(rates[1:])
+        row["h2d_alone_GBps"] = row["h2d_alone_slices_per_s"] * row["h2d_bytes_per_slice"] / 1e9
+
+        def run_raw(pipe, inputs, count):
+            got = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(count):
+                j = k % n_raws
+                pipe.submit_raw(inputs[j], dmasks[j], coil_matrix=mats[j], **kw)
+                for _ in pipe.results():
+                    got += 1
+            for _ in pipe.drain():
+                got += 1
+            torch.cuda.synchronize()
+            assert got == count
+            return count / (time.perf_counter() - t0)
+
+        def run_today(pipe, count):
+            got = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(count):
+                j = k % n_raws
+                y = torch.as_tensor(raws[j]).cuda()
+                ksp, _ = FE.prepare_slice(y, crop, FRAMES, FILTER, SCALING, coil_matrix=mats[j])
+                pipe.submit(ops.apply_mask(ksp, dmasks[j])[None], dmasks[j])
+                for _ in pipe.results():
+                    got += 1
+            for _ in pipe.drain():
+                got += 1
+            torch.cuda.synchronize()
+            assert got == count
+            return count / (time.perf_counter() - t0)
+
+        with torch.no_grad():
+            want = net(FE.prepare_masked_slice(forms["device"][0], dmasks[0], crop, FRAMES, FILTER, SCALING, coil_matrix=mats[0]), dmasks[0]).cpu()
+        with SlicePipeline(net, slots=S) as pipe:
+            t_build = time.perf_counter()
+            pipe.submit_raw(forms["device"][0], dmasks[0], coil_matrix=mats[0], **kw)
+            (_, o0), = list(pipe.drain())
+            row["setup_s"] = time.perf_counter() - t_build
+            row["bit_identical_to_sequential"] = bool(torch.equal(o0.cpu(), want))
+            for form, inputs in forms.items():
+                if form not in want_forms:
+                    continue
+                run_raw(pipe, inputs, warm)
+                rs = [run_raw(pipe, inputs, n) for _ in range(reps)]
+                row[f"value_{form}_raw"], row[f"regions_{form}_raw"] = _median(rs), rs
+            assert pipe.set_builds == 1
+        if "today" in want_forms:
+            with SlicePipeline(net, slots=S) as pipe:
+                run_today(pipe, warm)
+                rs = [run_today(pipe, n) for _ in range(reps)]
+                row["value_todays_way"], row["regions_todays_way"] = _median(rs), rs
+        if "device" in want_forms and "pinned" in want_forms:
+            limit = min(row["h2d_alone_slices_per_s"], row["value_device_raw"])
+            row["bound"] = "host-to-device copy" if row["h2d_alone_slices_per_s"] < row["value_device_raw"] else "GPU"
+            row["limit_slices_per_s"] = limit
+            row["pinned_over_limit"] = row["value_pinned_raw"] / limit
+        if "today" in want_forms and "pinned" in want_forms:
+            row["pinned_over_todays_way"] = row["value_pinned_raw"] / row["value_todays_way"]
+        doc["scans"].append(row)
+        print(json.dumps(row), flush=True)
+        del forms, kept, raws, dmasks, mats
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+    print(json.dumps({k: v for k, v in doc.items() if k != "scans"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5))
     ap.add_argument("--slots", type=int, default=10)
-    ap.add_argument("--slices", type=int, default=300)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--slices", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--hw-queues", type=int, default=None, help="set GPU_MAX_HW_QUEUES to this (<= 32) instead of keeping the environment's")
+    ap.add_argument("--raw", action="store_true", help="raw k-space through submit_raw (see the module docstring)")
+    ap.add_argument("--forms", default="pinned,numpy,device,today", help="--raw: which of pinned, numpy, device, today to run (a trace of one form)")
+    ap.add_argument("--repeats", type=int, default=3, help="--raw: timed regions per input form")
+    ap.add_argument("--out", default=None, help="--raw: also write the whole result to this JSON file")
+    ap.add_argument("--commit", default=None, help="--raw: the commit to stamp the result with (default: git rev-parse HEAD)")
     args = ap.parse_args()
+    if args.raw:
+        return raw_main(args)
+    args.slices = 300 if args.slices is None else args.slices
+    args.warmup = 20 if args.warmup is None else args.warmup
     import bench
     from cine_hip import synth
     from cine_hip.pipeline import SlicePipeline
