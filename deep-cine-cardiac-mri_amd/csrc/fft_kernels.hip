@@ -1416,6 +1416,9 @@ extern "C" int cine_zero_filled_rss(const float* k, float* out, float* tmp, int 
     CINE_REQUIRE(k && out && tmp, CINE_EINVAL, "cine_zero_filled_rss: null pointer");
     CINE_REQUIRE(b > 0 && t > 0 && c > 0 && h > 0 && w > 0, CINE_EINVAL, "cine_zero_filled_rss: bad sizes");
     if (int e = check_n(w, "cine_zero_filled_rss(w)")) return e;
+    // every refusal of the second pass is decided here, before the first pass writes tmp (which may be k)
+    if (int e = check_n(h, "cine_zero_filled_rss(h)")) return e;
+    CINE_REQUIRE((long)b * t <= 65535, CINE_EUNSUPPORTED, "cine_zero_filled_rss: b*t > 65535");
     if (int e = cine_kspace_to_hybrid(k, tmp, (long)b * t * c, h, w, stream)) return e;
     RowArgs r{};
     r.in = reinterpret_cast<const cf*>(tmp);
@@ -1424,7 +1427,6 @@ extern "C" int cine_zero_filled_rss(const float* k, float* out, float* tmp, int 
     r.sens = nullptr;
     r.T = t; r.C = c; r.H = h;
     coil_tiling(c, w, r.rpw, r.cc);
-    CINE_REQUIRE((long)b * t <= 65535, CINE_EUNSUPPORTED, "cine_zero_filled_rss: b*t > 65535");
     return launch_row<PRE_NONE, RPOST_RSS>(r, dim3(ceil_div(h, r.rpw), b * t), true, as_stream(stream));
 }
 
@@ -1432,6 +1434,10 @@ extern "C" int cine_sens_reduce(const float* k, const float* sens, float* out, f
                                 int b, int t, int c, int h, int w, int magnitude, void* stream) {
     CINE_REQUIRE(k && sens && out && tmp, CINE_EINVAL, "cine_sens_reduce: null pointer");
     CINE_REQUIRE(b > 0 && t > 0 && c > 0 && h > 0 && w > 0, CINE_EINVAL, "cine_sens_reduce: bad sizes");
+    // every refusal of cine_hybrid_reduce is decided here, before cine_kspace_to_hybrid writes tmp (which may be k)
+    if (int e = check_n(h, "cine_sens_reduce(h)")) return e;
+    if (int e = check_n(w, "cine_sens_reduce(w)")) return e;
+    CINE_REQUIRE((long)b * t <= 65535, CINE_EUNSUPPORTED, "cine_sens_reduce: b*t > 65535");
     if (int e = cine_kspace_to_hybrid(k, tmp, (long)b * t * c, h, w, stream)) return e;
     return cine_hybrid_reduce(tmp, sens, out, b, t, c, h, w, magnitude, stream);
 }

@@ -432,6 +432,8 @@ extern "C" int cine_xfyf_unpack(const float* planes_xf, const float* planes_yf, 
 static int sens_prologue_impl(const float* k, float* out, int b, int t, int c, int h, int w, int row_lo, int row_hi, const int* win, void* stream) {
     CINE_REQUIRE(k && out, CINE_EINVAL, "cine_sens_prologue: null pointer");
     CINE_REQUIRE(b > 0 && b <= 65535 && t > 0 && c > 0 && h > 0 && w > 0, CINE_EINVAL, "cine_sens_prologue: bad sizes");
+    // what cine_fft2c would refuse is refused here, before the frame mean is written to out
+    CINE_REQUIRE(cine_fft_line_supported(h) && cine_fft_line_supported(w), CINE_EUNSUPPORTED, "cine_sens_prologue: FFT size %d x %d unsupported", h, w);
     { ProfScope prof(F_MISC, as_stream(stream));
     hipLaunchKernelGGL(time_mean_center_kernel, dim3(grid_for((long)c * h * w, 256), b), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const cf*>(k), reinterpret_cast<cf*>(out), t, c, h, w, row_lo, row_hi, win); }

@@ -13,6 +13,8 @@
  *   - all pointers are DEVICE pointers owned by the caller (except where noted), fp32,
  *     contiguous, in the reference's layouts: complex = trailing pair (re, im);
  *     k-space (b, t, coil, h, w, 2); image (b, t, h, w, 2); mask uint8 (b, t, 1, h, 1, 1).
+ *     Complex operands must be 8-byte aligned (a whole (re, im) pair is loaded at once); 16-byte alignment is only needed where an
+ *     entry point says so.
  *   - `stream` is the caller's hipStream_t passed as void* (NULL = default stream);
  *     every launch goes onto it, so the calls are hipGraph-capturable.
  *   - scratch comes from the caller: `ws`/`ws_bytes` with a matching *_ws_bytes() query.
@@ -187,7 +189,8 @@ int cine_sens_prologue(const float* k, float* out, int b, int t, int c, int h, i
 /* The same without a host read-back of the mask (the reference finds the window on the host, varnet.py:64-68): cine_acs_window finds the fully
  * sampled centre rows of a row mask on the device -- mask_rows: the 1-D pattern of frame 0, n >= h float32 entries, 0 = not sampled;
  * window[0..1] = {pad, pad + n_low} with left = the last unsampled row below h / 2 (-1: none), right = the first one at or above it (n: none),
- * n_low = right - left, pad = (h - n_low + 1) / 2 -- and cine_sens_prologue_win reads {row_lo, row_hi} from that device buffer. */
+ * n_low = right - left, pad = (h - n_low + 1) / 2; only the first h entries are read, and a mask with no unsampled row below or none at or
+ * above h / 2 (the reference raises there) gives {0, h} -- and cine_sens_prologue_win reads {row_lo, row_hi} from that device buffer. */
 int cine_acs_window(const float* mask_rows, int n, int h, int* window, void* stream);
 int cine_sens_prologue_win(const float* k, float* out, int b, int t, int c, int h, int w, const int* window, void* stream);
 

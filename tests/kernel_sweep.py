@@ -1,4 +1,4 @@
-"""Shared harness of the shape-by-shape kernel sweeps (test_grad_kernels.py, test_conv_fwd_kernels.py): seeded case lists, guarded
+"""Shared harness of the shape-by-shape kernel sweeps (test_grad_kernels.py, test_conv_fwd_kernels.py, test_transform_kernels.py): seeded case lists, guarded
 device outputs, exact-size workspaces, the error bar and the worst error / bar report.  A plain module, not a conftest: the test files
 import what they use."""
 import numpy as np
@@ -85,6 +85,30 @@ class Guarded:
 
     def intact(self):
         return bool((self.buf[:self.lo] == GUARD_VALUE).all()) and bool((self.buf[self.lo + self.n:] == GUARD_VALUE).all())
+
+
+GUARD_INT = 0x5A5A5A5A
+
+
+class GuardedInt:
+    """Guarded for an int32 output (cine_acs_window's window): `n` ints between GUARD ints of GUARD_INT on each side."""
+
+    def __init__(self, n, dev, fill=-1):
+        self.n = n
+        self.buf = torch.full((2 * GUARD + n,), GUARD_INT, dtype=torch.int32, device=dev)
+        self.t = self.buf[GUARD:GUARD + n]
+        self.t.fill_(fill)
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def intact(self):
+        return bool((self.buf[:GUARD] == GUARD_INT).all()) and bool((self.buf[GUARD + self.n:] == GUARD_INT).all())
+
+
+def same_bits(a, b):
+    """Bit equality of two float32 tensors (NaN-safe, and -0 differs from +0)."""
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
 
 def view_at(x, off, dev):
