@@ -1257,7 +1257,9 @@ extern "C" int cine_normal_op_cg_fused_t(float* x, float* r, float* p, const flo
     CINE_REQUIRE(rr_old_dev != rr_new_dev, CINE_EINVAL, "cine_normal_op_cg_fused: rr_old and rr_new must be different scalars");
     const long nb = cg_fused_blocks(b, t, c, h, w);
     CINE_REQUIRE(nb > 0 && nb <= 0x7fffffffL, CINE_EUNSUPPORTED, "cine_normal_op_cg_fused: needs h == 200 and more than %d coils", kDcCS);
+    CINE_REQUIRE((long)b * t <= 65535, CINE_EUNSUPPORTED, "cine_normal_op_cg_fused: b*t > 65535");
     CINE_REQUIRE(ws_cg_bytes >= cine_cg_fused_ws_bytes(b, t, c, h, w), CINE_EWORKSPACE, "cine_normal_op_cg_fused: workspace too small");
+    CINE_REQUIRE(ws_dc_bytes >= cine_image_dc_ws_bytes(b, t, c, h, w), CINE_EWORKSPACE, "cine_normal_op_cg_fused: operator workspace too small");
     float* pd_wg = reinterpret_cast<float*>(ws_cg);
     if (int e = image_dc_impl(p, sens, p, mask, lambda_dev, 1, 1.f, 0.f, 0.f, nullptr, b, t, c, h, w, 0, ws_dc, ws_dc_bytes, stream, nullptr, pd_wg, sens_tiled)) return e;
     const long ncf = (long)b * t * h * w;

@@ -480,7 +480,9 @@ int cine_normal_op_cg_fused_t(float* x, float* r, float* p, const float* sens, c
  * (cinenet.py:106-107: x is then the regulariser's output, start value and regularisation target at once).  Per iteration one operator kernel -- which forms the new direction p = r + beta p on load and
  * needs no direction pass -- and one update kernel (alpha, x, r, the partial sums of r.r).  Same arithmetic as cine_normal_op_cg_fused
  * iterated, except for the summation order of the first r.r.  h == 200 and more than 5 coils (else CINE_EUNSUPPORTED: iterate
- * cine_normal_op / cine_cg_step); sens_tiled: cine_sens_tile_pack's copy or NULL.  ws: cine_conj_grad_ws_bytes(). */
+ * cine_normal_op / cine_cg_step); sens_tiled: cine_sens_tile_pack's copy or NULL.  ws: cine_conj_grad_ws_bytes(), 8-byte aligned like any
+ * complex operand (the coil groups' complex sums lie at its base); the 16-byte {p, r} pairs inside are placed at the next 256-byte
+ * boundary by the call itself, whatever the base -- the size query includes those up to 255 bytes. */
 size_t cine_conj_grad_ws_bytes(int b, int t, int c, int h, int w);
 int cine_conj_grad(float* x, const float* rhs, int rhs_is_ref, const float* sens, const float* sens_tiled, const uint8_t* mask,
                    const float* lambda_dev, int iters, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);

@@ -1,5 +1,6 @@
-"""Shared harness of the shape-by-shape kernel sweeps (test_grad_kernels.py, test_conv_fwd_kernels.py, test_transform_kernels.py): seeded case lists, guarded
-device outputs, exact-size workspaces, the error bar and the worst error / bar report.  A plain module, not a conftest: the test files
+"""Shared harness of the shape-by-shape kernel sweeps (test_grad_kernels.py, test_conv_fwd_kernels.py, test_transform_kernels.py, test_cg_kernels.py):
+seeded case lists, guarded device outputs, exact-size workspaces, the error bar, the worst error / bar report and the operands of one call
+through the C ABI (Call, twice, at_offsets, refused).  A plain module, not a conftest: the test files
 import what they use."""
 import numpy as np
 import torch
@@ -117,16 +118,142 @@ def view_at(x, off, dev):
 
 
 class Workspace:
-    """Exactly `nbytes` of workspace, carved from a larger buffer whose tail holds a sentinel pattern."""
+    """Exactly `nbytes` of workspace, carved from a larger buffer whose tail holds a sentinel pattern.  past256: the base pointer lies that
+    many bytes past a 256-byte boundary (None: the allocation's own base), behind a head of the same pattern."""
 
-    def __init__(self, nbytes, dev):
+    def __init__(self, nbytes, dev, past256=None):
         self.nbytes = int(nbytes)
         self.tail = (torch.arange(WS_TAIL, dtype=torch.int64) * 37 % 251).to(torch.uint8).to(dev)
-        self.buf = torch.zeros(self.nbytes + WS_TAIL, dtype=torch.uint8, device=dev)
+        if past256 is None:
+            self.lo = 0
+            self.buf = torch.zeros(self.nbytes + WS_TAIL, dtype=torch.uint8, device=dev)
+        else:
+            self.whole = torch.zeros(512 + self.nbytes + WS_TAIL, dtype=torch.uint8, device=dev)
+            self.lo = (-self.whole.data_ptr()) % 256 + 256 + past256
+            self.whole[:self.lo] = self.tail[:self.lo]
+            self.buf = self.whole[self.lo:self.lo + self.nbytes + WS_TAIL]
+            assert self.buf.data_ptr() % 256 == past256
         self.buf[self.nbytes:] = self.tail
 
     def ptr(self):
         return self.buf.data_ptr()
 
     def intact(self):
-        return torch.equal(self.buf[self.nbytes:], self.tail)
+        return torch.equal(self.buf[self.nbytes:], self.tail) and (self.lo == 0 or torch.equal(self.whole[:self.lo], self.tail[:self.lo]))
+
+
+# ================================================================== one call through the C ABI (the GPU tests of the sweeps)
+NAN = float("nan")
+EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -3
+
+
+def L():
+    from cine_hip._lib import lib
+    return lib()
+
+
+def check(code, what):
+    from cine_hip._lib import check as _check
+    _check(code, what)
+
+
+def stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def unchanged(t, keep):
+    return same_bits(t, keep) if t.dtype == torch.float32 else torch.equal(t, keep)
+
+
+class Call:
+    """The operands of one call with every float pointer at storage offset `off` floats: inputs are kept to prove them unchanged, outputs
+    sit between guard floats and are prefilled with NaN, a workspace has exactly the size asked for."""
+
+    def __init__(self, dev, off):
+        self.dev, self.off, self.ins, self.outs, self.wss = dev, off, [], [], []
+
+    def inp(self, x):
+        if x is None:
+            return None
+        t = view_at(x.contiguous(), self.off, self.dev)
+        self.ins.append((t, t.clone()))
+        return t
+
+    def raw(self, x):
+        """uint8 masks, int32 windows, the one float of lambda_dev: at their allocation's base."""
+        t = x.contiguous().to(self.dev)
+        self.ins.append((t, t.clone()))
+        return t
+
+    def lam(self, v):
+        return None if v is None else self.raw(torch.tensor([v], dtype=torch.float32))
+
+    def out(self, shape, fill=None):
+        """A pure output (NaN prefill) or, with `fill`, an operand updated in place."""
+        g = Guarded(tuple(shape), self.off, self.dev)
+        if fill is None:
+            g.t.fill_(NAN)
+        else:
+            g.t.copy_(fill)
+        self.outs.append(g)
+        return g
+
+    def ws(self, nbytes, past256=None):
+        if not nbytes:
+            return None
+        w = Workspace(nbytes, self.dev, past256)
+        w.buf[:w.nbytes] = 0xFF                     # NaN bit patterns: the result must not depend on what the workspace held
+        self.wss.append(w)
+        return w
+
+    def finish(self, what):
+        torch.cuda.synchronize()
+        for g in self.outs:
+            assert g.intact(), f"{what}: write outside an output"
+        for w in self.wss:
+            assert w.intact(), f"{what}: write past the workspace"
+        for t, keep in self.ins:
+            assert unchanged(t, keep), f"{what}: an input changed"
+
+
+def twice(dev, off, body, what):
+    """body(Call) makes the call on fresh operands and returns its output tensors: twice, the same bits; returns them on the CPU."""
+    res = []
+    for _ in range(2):
+        k = Call(dev, off)
+        outs = body(k)
+        k.finish(what)
+        res.append([o.clone() for o in outs])
+    for a, b in zip(*res):
+        assert same_bits(a, b), f"{what}: a second call gives other bits"
+    return [o.cpu() for o in res[0]]
+
+
+def at_offsets(dev, offs, body, what):
+    """twice at every storage offset of offs; all give the bits of the first."""
+    res = [twice(dev, off, body, what) for off in offs]
+    for r in res[1:]:
+        for a, b in zip(res[0], r):
+            assert same_bits(a, b), f"{what}: other bits at a storage offset of {offs[1]} floats"
+    return res[0]
+
+
+def refused(call, want, k, what, name=None):
+    """call() returns `want`, leaves a message of its own -- it names the entry point (`name`, by default the first word of `what`) and
+    replaces the message of another entry point's refusal made just before -- and writes nothing: guards intact, every output and
+    in-place operand holds the bits it held (a pure output is still NaN), inputs unchanged."""
+    name = name or what.split()[0]
+    assert name.startswith("cine_") and name != "cine_scale", what
+    assert L().cine_scale(None, 1, 1.0, None) == EINVAL and L().cine_last_error().startswith(b"cine_scale")
+    before = [g.buf.clone() for g in k.outs]
+    code = call()
+    assert code == want, f"{what}: returned {code}, expected {want}"
+    msg = L().cine_last_error().decode(errors="replace")
+    assert msg.startswith(name), f"{what}: the message is not this call's: {msg!r}"
+    k.finish(what)
+    for g, keep in zip(k.outs, before):
+        assert same_bits(g.buf, keep), f"{what}: an output was written before the refusal"

@@ -8,7 +8,7 @@ Entry points
   C  cine_image_dc, cine_image_dc_t + cine_sens_tile_pack, cine_normal_op, cine_normal_op_t, cine_normal_op_pd,
      cine_image_dc_sens_grad + cine_coil_accum
 Out of scope, by decision: the conjugate-gradient solver entry points (cine_cg_*, cine_conj_grad*, cine_normal_op_cg_fused*, cine_dot,
-cine_axpby_*).  They have their own bit-identity and oracle tests (test_hip_parity.py) and an iterative solver needs another kind of bar.
+cine_axpby_*).  An iterative solver needs another kind of bar: they have a sweep of their own, test_cg_kernels.py.
 
 References: complex128 on the CPU from the header's definitions and the reference's formulas -- fftshift(fft(ifftshift(x), "ortho")) with
 torch.fft, the coil sums and products of varnet.py:181-194 / 281-282, softplus in float64.  The image-space operators (group C) are
@@ -35,9 +35,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden, rel_err, rnd
-from kernel_sweep import BAR, Guarded, GuardedInt, Workspace, Worst, cap_samples, case_id, hash_case, same_bits, sweep, view_at
+from kernel_sweep import (BAR, EINVAL, EUNSUPPORTED, EWORKSPACE, NAN, Call, GuardedInt, L as _L, Worst, at_offsets as _at_offsets, cap_samples, case_id,
+                          check as _check, hash_case, ptr as _p, refused as _refused, same_bits, stream as _stream, sweep, twice as _twice)
 
-NAN = float("nan")
 PIN = 1e-6                                      # float32 fixtures against a float64 restatement
 
 
@@ -626,7 +626,6 @@ def test_split_cases_cross_the_batch_split_with_another_mask():
 gpu = pytest.mark.gpu
 WORST = Worst()     # entry point -> (worst error / bar, case)
 _record = WORST.record
-EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -3
 
 
 @pytest.fixture(scope="module")
@@ -635,100 +634,6 @@ def dev():
     yield torch.device("cuda:0")
     if WORST:
         WORST.report()
-
-
-def _L():
-    from cine_hip._lib import lib
-    return lib()
-
-
-def _check(code, what):
-    from cine_hip._lib import check
-    check(code, what)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
-def _unchanged(t, keep):
-    return same_bits(t, keep) if t.dtype == torch.float32 else torch.equal(t, keep)
-
-
-class Call:
-    """The operands of one call with every float pointer at storage offset `off` floats: inputs are kept to prove them unchanged, outputs
-    sit between guard floats and are prefilled with NaN, a workspace has exactly the size asked for."""
-
-    def __init__(self, dev, off):
-        self.dev, self.off, self.ins, self.outs, self.wss = dev, off, [], [], []
-
-    def inp(self, x):
-        if x is None:
-            return None
-        t = view_at(x.contiguous(), self.off, self.dev)
-        self.ins.append((t, t.clone()))
-        return t
-
-    def raw(self, x):
-        """uint8 masks, int32 windows, the one float of lambda_dev: at their allocation's base."""
-        t = x.contiguous().to(self.dev)
-        self.ins.append((t, t.clone()))
-        return t
-
-    def lam(self, v):
-        return None if v is None else self.raw(torch.tensor([v], dtype=torch.float32))
-
-    def out(self, shape, fill=None):
-        g = Guarded(tuple(shape), self.off, self.dev)
-        if fill is None:
-            g.t.fill_(NAN)
-        else:
-            g.t.copy_(fill)
-        self.outs.append(g)
-        return g
-
-    def ws(self, nbytes):
-        if not nbytes:
-            return None
-        w = Workspace(nbytes, self.dev)
-        w.buf[:w.nbytes] = 0xFF                     # NaN bit patterns: the result must not depend on what the workspace held
-        self.wss.append(w)
-        return w
-
-    def finish(self, what):
-        torch.cuda.synchronize()
-        for g in self.outs:
-            assert g.intact(), f"{what}: write outside an output"
-        for w in self.wss:
-            assert w.intact(), f"{what}: write past the workspace"
-        for t, keep in self.ins:
-            assert _unchanged(t, keep), f"{what}: an input changed"
-
-
-def _twice(dev, off, body, what):
-    """body(Call) makes the call on fresh operands and returns its output tensors: twice, the same bits; returns them on the CPU."""
-    res = []
-    for _ in range(2):
-        k = Call(dev, off)
-        outs = body(k)
-        k.finish(what)
-        res.append([o.clone() for o in outs])
-    for a, b in zip(*res):
-        assert same_bits(a, b), f"{what}: a second call gives other bits"
-    return [o.cpu() for o in res[0]]
-
-
-def _at_offsets(dev, offs, body, what):
-    """_twice at every storage offset of offs; all give the bits of the first."""
-    res = [_twice(dev, off, body, what) for off in offs]
-    for r in res[1:]:
-        for a, b in zip(res[0], r):
-            assert same_bits(a, b), f"{what}: other bits at a storage offset of {offs[1]} floats"
-    return res[0]
 
 
 ALIGNED, BOTH = (0,), (0, 2)
@@ -1225,21 +1130,6 @@ def test_coil_accum(dev, case, accumulate, with_g):
 
 
 # ================================================================== refusals: decided on the host, before any launch
-def _refused(call, want, k, what):
-    """call() returns `want`, leaves a message of its own -- it names the entry point, the first word of `what`, and replaces the
-    message of another entry point's refusal made just before -- and writes nothing: guards intact, outputs still NaN, inputs unchanged."""
-    name = what.split()[0]
-    assert name.startswith("cine_") and name != "cine_scale", what
-    assert _L().cine_scale(None, 1, 1.0, None) == EINVAL and _L().cine_last_error().startswith(b"cine_scale")
-    code = call()
-    assert code == want, f"{what}: returned {code}, expected {want}"
-    msg = _L().cine_last_error().decode(errors="replace")
-    assert msg.startswith(name), f"{what}: the message is not this call's: {msg!r}"
-    k.finish(what)
-    for g in k.outs:
-        assert bool(torch.isnan(g.t).all()), f"{what}: an output was written before the refusal"
-
-
 @gpu
 def test_transform_refusals(dev):
     L, st = _L(), _stream()
