@@ -37,8 +37,13 @@ _SIGS = {
     "cine_normal_op": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "cine_image_dc": (c_int, [P, P, P, P, P, c_float, c_float, c_float, P, c_int, c_int, c_int, c_int, c_int, c_int,
                               P, c_size_t, P]),
+    "cine_image_dc_general_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "cine_image_dc_general": (c_int, [P, P, P, P, P, c_float, c_float, c_float, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      P, c_size_t, P]),
+    "cine_normal_op_general": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "cine_masked_kspace_to_hybrid": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "cine_apply_mask": (c_int, [P, P, P, c_long, c_int, c_int, c_int, P]),
+    "cine_apply_mask2d": (c_int, [P, P, P, c_long, c_int, c_int, c_int, P]),
     "cine_scale": (c_int, [P, c_long, c_float, P]),
     "cine_zero_filled_rss": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_image_metrics_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -1165,7 +1165,7 @@ class ConjGradFn(Function):
                 ctx.save_for_backward(x0, lam, mask, sens, rr, pd, *p_rec.unbind(0))
                 return x
         one = torch.ones(1, device=dev, dtype=torch.float32)
-        r = ops.axpby_dev(b, ops.h_operator(x0, sens, mask, lam), num=one, sign=-1.0)
+        r = ops.axpby_dev(b, ops.h_operator(x0, sens, mask, lam, literal=True), num=one, sign=-1.0)
         p = r.clone()
         x = x0.clone()
         # the step sizes stay on the device: rr[k] = r_k . r_k, pd[k] = p_k . H p_k  (alpha_k = rr[k] / pd[k], beta_k = rr[k + 1] / rr[k])
@@ -1181,7 +1181,7 @@ class ConjGradFn(Function):
             if fused:       # the inference path's four launches per iteration (operator with p.d partial sums, update, direction), p.d recorded
                 ops.normal_op_cg_step(x, r, p, sens, mask, lam, rr[k:k + 1], rr[k + 1:k + 2], pd_out=pd[k:k + 1])
                 continue
-            d = ops.h_operator(p, sens, mask, lam)
+            d = ops.h_operator(p, sens, mask, lam, literal=True)
             ops.dot(p, d, out=pd[k:k + 1])
             x = ops.axpby_dev(x, p, num=rr[k:k + 1], den=pd[k:k + 1])                   # x + alpha p
             r = ops.axpby_dev(r, d, num=rr[k:k + 1], den=pd[k:k + 1], sign=-1.0)        # r - alpha d
@@ -1203,7 +1203,7 @@ class ConjGradFn(Function):
         q = torch.zeros_like(gx)                                      # q_k = gr_{k+1} + gp_{k+1}: the gradient reaching r_{k+1}
         gp = torch.zeros_like(gx)
         for k in reversed(range(K)):
-            hg = ops.h_operator(q, sens, mask, lam)
+            hg = ops.h_operator(q, sens, mask, lam, literal=True)
             check(L.cine_cg_adjoint_step(gp.data_ptr(), q.data_ptr(), gx.data_ptr(), hg.data_ptr(), ps[k].data_ptr(), gx.numel(),
                                          rr[k:k + 1].data_ptr(), pd[k:k + 1].data_ptr(), rr[k + 1:k + 2].data_ptr(),
                                          part[k * nf:].data_ptr(), _stream()), "cine_cg_adjoint_step")
@@ -1212,7 +1212,7 @@ class ConjGradFn(Function):
         gx0 = None
         if need[0]:
             one = torch.ones(1, device=dev, dtype=torch.float32)
-            gx0 = ops.axpby_dev(gx, ops.h_operator(gb, sens, mask, lam), num=one, sign=-1.0)
+            gx0 = ops.axpby_dev(gx, ops.h_operator(gb, sens, mask, lam, literal=True), num=one, sign=-1.0)
         glam = None
         if need[2]:
             gv = torch.empty(1, device=dev, dtype=torch.float32)

@@ -258,8 +258,8 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
           read.  Sizes the FFT line engines take: ops.raw_ingest (scale, coils in front) -> ifft2c of the kept frames -> crop -> Gaussian
           filter; any other size: ops.raw_window_ifft2c -> filter, as in prepare_slice.  Then the forward transform of the crop with the
           reference's shift order (mri_data.py:291-292).
-    mask  the row mask on the crop grid, uint8 or bool on the GPU, (1, T | 1, 1, X, 1, 1) (or any shape with T X or X entries in that
-          order).  ``apply_mask=False`` hands the k-space on unmasked -- prospectively undersampled data, where the reference also
+    mask  the mask on the crop grid, uint8 or bool on the GPU: a row mask (1, T | 1, 1, X, 1, 1) (or any shape with T X or X entries in
+          that order), or one that varies along the second axis, (1, T | 1, 1, X, Y, 1) (cine_apply_mask2d).  ``apply_mask=False`` hands the k-space on unmasked -- prospectively undersampled data, where the reference also
           only passes the stored mask on (data/transforms.py:331-339); ``mask`` may then be None.
     coil_matrix  A (V, coil) complex64 ON THE GPU: compress_coils first, everything else on V virtual coils.  The per-slice
           ``virtual_coils=`` of prepare_slice is not offered here: its eigen-decomposition checks the Gram matrix on the host, which
@@ -302,10 +302,15 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
     if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool):
         raise CineHipError("prepare_masked_slice: mask must be a uint8 or bool GPU tensor")
     m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
-    if m.numel() == cx and n > 1:
+    if cy > 1 and m.dim() == 6 and tuple(m.shape[2:]) == (1, cx, cy, 1) and m.shape[0] == 1 and m.shape[1] in (1, n):
+        if m.shape[1] != n:
+            m = m.expand(1, n, 1, cx, cy, 1).contiguous()                    # one pattern for all frames
+        m = m.view(n, 1, cx, cy, 1)                                          # varies along y: one plane per frame
+    elif m.numel() == cx and n > 1:
         m = m.reshape(1, cx).expand(n, cx).contiguous()                      # one pattern for all frames
     elif m.numel() != n * cx:
-        raise ValueError(f"prepare_masked_slice: mask {tuple(mask.shape)} is not a row mask (1, {n} | 1, 1, {cx}, 1, 1)")
+        raise ValueError(f"prepare_masked_slice: mask {tuple(mask.shape)} is not a row mask (1, {n} | 1, 1, {cx}, 1, 1) "
+                         f"nor a mask (1, {n} | 1, 1, {cx}, {cy}, 1)")
     if out is None:
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
     ops.apply_mask(kk, m, out=out.view(n, c, cx, cy, 2))

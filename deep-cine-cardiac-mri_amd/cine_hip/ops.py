@@ -436,7 +436,8 @@ def as_mask_u8(mask: torch.Tensor, kspace: Optional[torch.Tensor] = None) -> tor
     (``apply_mask`` returns a float one, data/transforms.py:66-92; varnet.py:281-282 multiplies).  Converted once, outside any kernel
     (not during hipGraph capture).  With ``kspace`` (b, t, c, h, w, 2) the mask is also brought into one of the two layouts the
     models dispatch on: a mask that is constant along w -- (b|1, t|1, 1, h, 1, 1) -- becomes the (b, t, 1, h, 1, 1) ROW mask of
-    the fused kernels; one that varies along w becomes a GENERAL mask (b, t, 1, h, w, 1), served by the literal k-space chain."""
+    the fused kernels; one that varies along w becomes a GENERAL mask (b, t, 1, h, w, 1), served by the two-pass image-space operator
+    (``image_dc`` / ``normal_op`` dispatch on the layout) or, with ``GENERAL_MASK_FUSED`` off and in training, the literal k-space chain."""
     if mask.dtype != torch.uint8:
         _no_capture("a uint8 copy of the sampling mask")
         mask = (mask != 0).to(torch.uint8)
@@ -465,9 +466,41 @@ def is_general_mask(mask: torch.Tensor, kspace: torch.Tensor) -> bool:
     return mask.dim() == 6 and w > 1 and tuple(mask.shape) == (b, t, 1, h, w, 1)
 
 
+GENERAL_MASK_FUSED = _os.environ.get("CINE_GENERAL_MASK_FUSED", "1") == "1"    # A/B switch: False = the literal coil-wise k-space chain for masks that vary along w
+                                                                                # (soft_dc_blend, masked_residual_backward, h_operator's expand -> mask -> reduce); the training form
+
+
+def general_mask_fused(mask: torch.Tensor, kspace: torch.Tensor) -> bool:
+    """True where the inference branches take the image-space operator for a mask that varies along w."""
+    return GENERAL_MASK_FUSED and is_general_mask(mask, kspace)
+
+
+_GENERAL_WS = {}
+_GENERAL_WS_LOCK = threading.Lock()
+
+
+def _general_ws(nbytes: int, device: torch.device) -> torch.Tensor:
+    """The hybrid-space scratch of the general-mask operators: one buffer per (device, stream, size), so that the cascades of a forward
+    pass (and of every later one on that stream) share it.  A captured graph gets a buffer of its own pool instead, static over replays."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(nbytes, device=device, dtype=torch.uint8)
+    key = (device.index, _stream(), nbytes)
+    with _GENERAL_WS_LOCK:
+        ws = _GENERAL_WS.get(key)
+        if ws is None:
+            ws = _GENERAL_WS[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return ws
+
+
+def release_general_workspaces() -> None:
+    """Drop the cached scratch buffers of the general-mask operators."""
+    with _GENERAL_WS_LOCK:
+        _GENERAL_WS.clear()
+
+
 def soft_dc_blend(model_term: torch.Tensor, ref_kspace: torch.Tensor, mask: torch.Tensor, lambda_reg: torch.Tensor) -> torch.Tensor:
     """The data-consistency line of reference varnet.py:281-282 for a GENERAL mask, term by term on the coil-wise k-space
-    (torch elementwise kernels: the fused DC kernels read row masks).  Differentiable in model_term and lambda_reg."""
+    (torch elementwise kernels).  Differentiable in model_term and lambda_reg: the training form; inference takes ``image_dc``."""
     m = mask.to(model_term.dtype)
     v = torch.nn.functional.softplus(lambda_reg)
     return (1 - m) * model_term + m * (model_term + v * ref_kspace) / (1 + v)
@@ -502,14 +535,16 @@ def sens_tile_pack(sens: torch.Tensor) -> Optional[torch.Tensor]:
 def image_dc(img: torch.Tensor, sens: torch.Tensor, zf: Optional[torch.Tensor], mask: torch.Tensor,
              lambda_reg: Optional[torch.Tensor] = None, weights=(1.0, 0.0, 0.0), magnitude: bool = False,
              out: Optional[torch.Tensor] = None, sens_tiled: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """sens_reduce(DC(sens_expand(img))) of reference varnet.py:181-194, 281-282 on the coil-combined image (row masks):
-    sum_c conj(S_c) IFFT_h[wgt * FFT_h(S_c img)] + beta * zf.  ``lambda_reg``: soft-DC weights from softplus(lambda);
+    """sens_reduce(DC(sens_expand(img))) of reference varnet.py:181-194, 281-282 on the coil-combined image:
+    sum_c conj(S_c) IFFT_h[wgt * FFT_h(S_c img)] + beta * zf for a row mask (b, t, 1, h, 1, 1), the same with both line passes
+    (cine_image_dc_general) for a mask (b, t, 1, h, w, 1) that varies along w.  ``lambda_reg``: soft-DC weights from softplus(lambda);
     else ``weights`` = (w_sampled, w_unsampled, beta).  img (b,t,[1,]h,w,2) -> (b,t,1,h,w,2), or (b,t,h,w) magnitude."""
     _pair(img); _pair(sens)
     img = _dev(img, "image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
     b, _, c, h, w, _ = sens.shape
     t = img.shape[1]
-    if img.numel() != b * t * h * w * 2 or mask.numel() != b * t * h:
+    general = w > 1 and mask.dim() == 6 and tuple(mask.shape) == (b, t, 1, h, w, 1)
+    if img.numel() != b * t * h * w * 2 or (not general and mask.numel() != b * t * h):
         raise ValueError(f"image_dc: image {tuple(img.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
     if zf is not None:
         zf = _dev(zf, "zero-filled image")
@@ -519,6 +554,12 @@ def image_dc(img: torch.Tensor, sens: torch.Tensor, zf: Optional[torch.Tensor], 
     if out is None:
         out = torch.empty((b, t, h, w) if magnitude else (b, t, 1, h, w, 2), device=img.device, dtype=img.dtype)
     w1, w0, beta = (float(v) for v in weights)
+    if general:
+        nbytes = lib().cine_image_dc_general_ws_bytes(b, t, c, h, w)
+        ws = _general_ws(nbytes, img.device)
+        check(lib().cine_image_dc_general(img.data_ptr(), sens.data_ptr(), _p(zf), mask.data_ptr(), _p(lam), w1, w0, beta,
+                                          out.data_ptr(), b, t, c, h, w, int(magnitude), ws.data_ptr(), nbytes, _stream()), "cine_image_dc_general")
+        return out
     nbytes = lib().cine_image_dc_ws_bytes(b, t, c, h, w)
     ws = torch.empty(nbytes, device=img.device, dtype=torch.uint8) if nbytes else None
     check(lib().cine_image_dc_t(img.data_ptr(), sens.data_ptr(), _p(sens_tiled), _p(zf), mask.data_ptr(), _p(lam), w1, w0, beta,
@@ -528,15 +569,23 @@ def image_dc(img: torch.Tensor, sens: torch.Tensor, zf: Optional[torch.Tensor], 
 
 def normal_op(img: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_reg: torch.Tensor,
               sens_tiled: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """A^H M A img + softplus(lambda) img for a row mask (CineNet's H operator, reference cinenet.py:121-133) -> (b,t,1,h,w,2)."""
+    """A^H M A img + softplus(lambda) img (CineNet's H operator, reference cinenet.py:121-133) -> (b,t,1,h,w,2), for a row mask
+    (b, t, 1, h, 1, 1) or one that varies along w, (b, t, 1, h, w, 1) (cine_normal_op_general)."""
     _pair(img); _pair(sens)
     img = _dev(img, "image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
     lam = _dev(lambda_reg.detach(), "lambda_reg")
     b, _, c, h, w, _ = sens.shape
     t = img.shape[1]
-    if img.numel() != b * t * h * w * 2 or mask.numel() != b * t * h:
+    general = w > 1 and mask.dim() == 6 and tuple(mask.shape) == (b, t, 1, h, w, 1)
+    if img.numel() != b * t * h * w * 2 or (not general and mask.numel() != b * t * h):
         raise ValueError(f"normal_op: image {tuple(img.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
     out = torch.empty((b, t, 1, h, w, 2), device=img.device, dtype=img.dtype)
+    if general:
+        nbytes = lib().cine_image_dc_general_ws_bytes(b, t, c, h, w)
+        ws = _general_ws(nbytes, img.device)
+        check(lib().cine_normal_op_general(img.data_ptr(), sens.data_ptr(), mask.data_ptr(), lam.data_ptr(), out.data_ptr(), b, t, c, h, w,
+                                           ws.data_ptr(), nbytes, _stream()), "cine_normal_op_general")
+        return out
     nbytes = lib().cine_image_dc_ws_bytes(b, t, c, h, w)
     ws = torch.empty(nbytes, device=img.device, dtype=torch.uint8) if nbytes else None
     check(lib().cine_normal_op_t(img.data_ptr(), sens.data_ptr(), _p(sens_tiled), mask.data_ptr(), lam.data_ptr(), out.data_ptr(), b, t, c, h, w,
@@ -545,13 +594,16 @@ def normal_op(img: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_
 
 
 def h_operator(x: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_reg: torch.Tensor,
-               _hyb: Optional[torch.Tensor] = None, sens_tiled: Optional[torch.Tensor] = None) -> torch.Tensor:
+               _hyb: Optional[torch.Tensor] = None, sens_tiled: Optional[torch.Tensor] = None, literal: bool = False) -> torch.Tensor:
     """CineNet's H = A^H M A + softplus(lambda) I (reference cinenet.py:121-133) for either mask layout: the one-kernel image-space
-    operator for a (b, t, 1, h, 1, 1) row mask, the literal expand -> mask -> reduce chain for a mask that varies along w."""
+    operator for a (b, t, 1, h, 1, 1) row mask, its two-pass form for a mask that varies along w (``GENERAL_MASK_FUSED`` off or
+    ``literal``, the training form: the literal expand -> mask -> reduce chain)."""
     full = sens.expand(-1, x.shape[1], -1, -1, -1, -1)
     if is_row_mask(mask, full):
         return normal_op(x, sens, mask, lambda_reg, sens_tiled)
     if is_general_mask(mask, full):
+        if GENERAL_MASK_FUSED and not literal:
+            return normal_op(x, sens, mask, lambda_reg)
         k = sens_expand_dc(x, sens)
         k = k * mask.to(k.dtype) + 0.0                       # cinenet.py:129
         return axpby_dev(sens_reduce(k, sens, destroy_input=True), x, lambda_reg=lambda_reg)
@@ -735,16 +787,21 @@ def pad2d(x: torch.Tensor, left: int, right: int, top: int, bottom: int) -> torc
 
 # ------------------------------------------------------------------ the steps either side of the path
 def apply_mask(kspace: torch.Tensor, mask: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """kspace * mask + 0.0 (reference data/transforms.py:66-92) for a row mask; kspace (..., c, h, w, 2) with the mask's
-    (..., 1, h, 1, 1) leading dims, e.g. (b, t, c, h, w, 2) & (b, t, 1, h, 1, 1) or (t, c, h, w, 2) & (t, 1, h, 1, 1)."""
+    """kspace * mask + 0.0 (reference data/transforms.py:66-92); kspace (..., c, h, w, 2) with the mask's leading dims: a row mask
+    (..., 1, h, 1, 1), e.g. (b, t, c, h, w, 2) & (b, t, 1, h, 1, 1) or (t, c, h, w, 2) & (t, 1, h, 1, 1), or one that varies along w,
+    (..., 1, h, w, 1)."""
     _pair(kspace)
     kspace = _dev(kspace, "k-space"); mask = _dev(mask, "mask", torch.uint8)
     c, h, w = kspace.shape[-4], kspace.shape[-3], kspace.shape[-2]
     bt = kspace.numel() // (c * h * w * 2)
-    if mask.numel() != bt * h:
+    plane = w > 1 and mask.numel() == bt * h * w and mask.dim() >= 3 and tuple(mask.shape[-3:]) == (h, w, 1)
+    if not plane and mask.numel() != bt * h:
         raise ValueError(f"apply_mask: mask {tuple(mask.shape)} does not match k-space {tuple(kspace.shape)}")
     if out is None:
         out = torch.empty_like(kspace)
+    if plane:
+        check(lib().cine_apply_mask2d(kspace.data_ptr(), mask.data_ptr(), out.data_ptr(), bt, c, h, w, _stream()), "cine_apply_mask2d")
+        return out
     check(lib().cine_apply_mask(kspace.data_ptr(), mask.data_ptr(), out.data_ptr(), bt, c, h, w, _stream()), "cine_apply_mask")
     return out
 

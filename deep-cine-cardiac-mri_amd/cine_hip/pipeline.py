@@ -37,6 +37,8 @@ CineNet_RNN, optional for VarNet, and not accepted by the other models.
 The model is called as ``model(mk, mask)`` or ``model(mk, mask, sens)``, without ``acs=``: the ACS window is found on the
 device (``ops.acs_window_dev``) and a graph captured with one slice's mask gives any other slice's result.  That window is
 read from row masks only; a mask that varies along w with a model that runs its sensitivity network raises ``CineHipError``.
+With ``sens_maps`` such a mask is served like a row mask, by ``submit`` and ``submit_raw`` alike (the front-end masks with
+``cine_apply_mask2d``, the models run their image-space operators with both line passes, ``ops.GENERAL_MASK_FUSED``).
 
 Outputs (``results`` / ``drain``): ``(tag, out)`` in submission order; ``out`` is ``recon`` or, with ``zero_filled=True``,
 ``(recon, zero_filled)`` (reference run_inference.py:64-67, computed inside the same graph by ``cine_zero_filled_rss``).
@@ -321,9 +323,8 @@ class _RawSource:
         self.v = None if self.cmat is None else self.cmat.shape[0]
         self.mk_shape = (1, n, self.v or c, self.crop[0], self.crop[1], 2)
         self.mask, self.mask_kind, self.mask_shape = _check_mask(mask, self.mk_shape)
-        if self.mask_shape[4] > 1:
-            raise CineHipError("submit_raw: the front-end applies row masks (1, t|1, 1, X, 1, 1) only")
-        self.sens, self.sens_kind = _check_sens(pipe, sens_maps, self.mk_shape, False)
+        # a mask that varies along w: the rules of ``submit`` (the sensitivity network's ACS window needs a row mask)
+        self.sens, self.sens_kind = _check_sens(pipe, sens_maps, self.mk_shape, self.mask_shape[4] > 1)
         _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat)))
         self.raw_nbytes = x.numel() * 4
         self.key = raw_set_key((n, nx, ny, c), n, self.crop, self.filter, self.scaling, self.apply_mask, self.mask_shape,
@@ -435,7 +436,8 @@ class SlicePipeline:
                    filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True) -> SliceHandle:
         """Enqueue one slice from its RAW k-space (t, x, y, coil) -- complex64 or float32 pairs, in any of the four places ``submit`` takes
         its input from.  Only ``raw[:min(n_frames, t)]`` is copied to the device.  ``frontend.prepare_masked_slice`` and the model run on
-        the slot's stream inside the slot's graph; see the module docstring.  ``mask``: the row mask on the crop grid; ``sens_maps``
+        the slot's stream inside the slot's graph; see the module docstring.  ``mask``: the mask on the crop grid, a row mask or one that varies along w under the
+        rules of ``submit`` (the sensitivity network needs a row mask: pass ``sens_maps``); ``sens_maps``
         (1, 1, C, X, Y, 2) on the crop grid (on the V virtual coils with ``coil_matrix`` (V, coil))."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit_raw after close()")

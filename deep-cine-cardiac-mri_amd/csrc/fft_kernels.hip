@@ -8,7 +8,8 @@
 // Fusions (reference lines in include/cine_hip.h):
 //   row pass load  : S * img                (sens_expand, varnet.py:181-185)
 //   col pass store : soft / hard DC blend   (varnet.py:281-282, cinenet.py:129)
-//   row pass store : conj(S) * x, coil sum, optional magnitude (varnet.py:187-194, 150-151)
+//                    or per-point weights of a mask plane, for masks that vary along w (cine_image_dc_general)
+//   row pass store : conj(S) * x, coil sum, optional + beta * zf, optional magnitude (varnet.py:187-194, 150-151)
 // N == 200 uses the 10 x 20 Cooley-Tukey engine; any other N = 2^a 3^b 5^c <= 512 the mixed-radix Stockham engine
 // (radices 4 / 2 / 3 / 5, two tiles ping-pong); lengths with another prime factor, <= 400, a direct DFT.
 #include <algorithm>
@@ -30,9 +31,12 @@ constexpr int kMaxGenericN = 400;                  // direct DFT, O(n^2): any le
 constexpr int kMaxSmoothN = 512;                   // mixed radix: 2^a 3^b 5^c (two 512 x 9 tiles + twiddles = 78 KB of LDS, opted in per kernel)
 constexpr int kMaxOut = 4;                          // reduce outputs per thread
 
-enum { POST_NONE = 0, POST_DC = 1, POST_HARD = 2, POST_RESID = 3 };   // RESID: mask ? k - kref : 0 (xpdnet.py:128-131,295-298)
+enum { POST_NONE = 0, POST_DC = 1, POST_HARD = 2, POST_RESID = 3, POST_W2D = 4 };   // RESID: mask ? k - kref : 0 (xpdnet.py:128-131,295-298)
+                                                                                      // W2D: k * (mask(ky, kx) ? w1 : w0), the mask a full (h, w) plane per frame
 enum { PRE_NONE = 0, PRE_SMUL = 1 };
-enum { RPOST_NONE = 0, RPOST_REDUCE = 1, RPOST_REDUCE_ABS = 2, RPOST_RSS = 3 };   // RSS: sqrt(sum_c |x_c|^2) (coil_combine.py:21-34)
+enum { RPOST_NONE = 0, RPOST_REDUCE = 1, RPOST_REDUCE_ABS = 2, RPOST_RSS = 3,     // RSS: sqrt(sum_c |x_c|^2) (coil_combine.py:21-34)
+       RPOST_REDUCE_ZF = 4, RPOST_REDUCE_ZF_ABS = 5 };                           // REDUCE (_ABS) of sum + beta * zf
+constexpr bool rpost_zf(int post) { return post == RPOST_REDUCE_ZF || post == RPOST_REDUCE_ZF_ABS; }
 
 template <bool F200> __device__ __forceinline__ void load_twiddles(cf* tw, int n) {
     if (F200) {
@@ -96,7 +100,14 @@ struct ColArgs {
     const cf* kref; const uint8_t* mask; const float* lam;
     int coils;            // images per mask row-set (mask index = img / coils)
     const uint8_t* premask;   // optional: rows with premask == 0 enter the transform as zeros and are not read
+    float w1, w0;         // POST_W2D: weight of sampled / unsampled points (lam != null: the soft-DC pair 1 / (1 + softplus(*lam)), 1);
+                          // mask is then the chunk's first (H, W) plane, one plane per `coils` images
 };
+
+__device__ __forceinline__ void col_weights(const ColArgs& a, float& w1, float& w0) {
+    w1 = a.w1; w0 = a.w0;
+    if (a.lam) { w1 = 1.0f / (1.f + softplus1(*a.lam)); w0 = 1.f; }          // the expressions of imgdc_weights
+}
 
 template <bool F200, int DIR, int POST, int LINES>
 __global__ void col_pass_kernel(ColArgs a) {
@@ -125,7 +136,10 @@ __global__ void col_pass_kernel(ColArgs a) {
 
     float v = 0.f, inv1v = 1.f;
     if (POST == POST_DC) { v = softplus1(*a.lam); }
-    const uint8_t* mrow = (POST != POST_NONE) ? a.mask + (img / a.coils) * H : nullptr;
+    const uint8_t* mrow = (POST != POST_NONE && POST != POST_W2D) ? a.mask + (img / a.coils) * H : nullptr;
+    const uint8_t* mpl = (POST == POST_W2D) ? a.mask + (img / a.coils) * H * a.W : nullptr;
+    float ws1 = 1.f, ws0 = 1.f;                 // POST_W2D: weight of sampled / unsampled points
+    if (POST == POST_W2D) col_weights(a, ws1, ws0);
     const cf* kref = (POST == POST_DC || POST == POST_RESID) ? a.kref + img * H * a.W : nullptr;
     for (int e = tid; e < H * LINES; e += nt) {
         const int i = e / LINES, l = e % LINES, col = w0 + l;
@@ -141,6 +155,8 @@ __global__ void col_pass_kernel(ColArgs a) {
             if (!mrow[i]) val = mk(0.f, 0.f);
         } else if (POST == POST_RESID) {
             val = mrow[i] ? csub(val, kref[(long)i * a.W + col]) : mk(0.f, 0.f);
+        } else if (POST == POST_W2D) {
+            val = cscale(val, mpl[(long)i * a.W + col] ? ws1 : ws0);
         }
         out[(long)i * a.W + col] = val;
     }
@@ -156,7 +172,21 @@ struct RowArgs {
     // coil modes
     const cf* sens; const cf* img;
     int T, C, H, rpw, cc;  // rows per workgroup, coils per chunk
+    // RPOST_REDUCE_ZF (_ABS): + beta * zf behind the coil sum (zf (b, t, h, w) or null).  lam != null: beta from softplus(*lam) as in
+    // imgdc_weights (lam_beta 0: v / (1 + v), 1: v)
+    const cf* zf; const float* lam; int lam_beta; float beta;
 };
+
+__device__ __forceinline__ float row_beta(const RowArgs& a) {
+    if (!a.lam) return a.beta;
+    const float v = softplus1(*a.lam);
+    return a.lam_beta ? v : v * (1.0f / (1.f + v));
+}
+template <int POST> __device__ __forceinline__ void row_store_zf(const RowArgs& a, long o, cf s, float beta) {
+    if (a.zf) { const cf z = a.zf[o]; s.x = fmaf(beta, z.x, s.x); s.y = fmaf(beta, z.y, s.y); }
+    if (POST == RPOST_REDUCE_ZF_ABS) a.out_abs[o] = sqrtf(s.x * s.x + s.y * s.y);
+    else a.out[o] = s;
+}
 
 template <bool F200, int DIR, int PRE, int POST, int LINES>
 __global__ void row_pass_kernel(RowArgs a) {
@@ -254,6 +284,7 @@ __global__ void row_pass_kernel(RowArgs a) {
         __syncthreads();
     }
     if (POST != RPOST_NONE) {
+        const float zf_beta = rpost_zf(POST) ? row_beta(a) : 0.f;
 #pragma unroll
         for (int o = 0; o < kMaxOut; ++o) {
             const int e = tid + o * nt;
@@ -265,6 +296,8 @@ __global__ void row_pass_kernel(RowArgs a) {
                 a.out_abs[(long)bt * HW + (long)h * W + i] = sqrtf(acc[o].x * acc[o].x + acc[o].y * acc[o].y);
             else if (POST == RPOST_RSS)
                 a.out_abs[(long)bt * HW + (long)h * W + i] = sqrtf(acc[o].x);
+            else if (rpost_zf(POST))
+                row_store_zf<POST>(a, (long)bt * HW + (long)h * W + i, acc[o], zf_beta);
             else
                 a.out[(long)bt * HW + (long)h * W + i] = acc[o];
         }
@@ -309,9 +342,16 @@ __global__ __launch_bounds__(kFT, 3) void col200_kernel(ColArgs a) {
     cf rr[20];
     if (POST != POST_NONE) {
         const int g2 = tid / kFL;
-        const uint8_t* mrow = a.mask + (img / a.coils) * 200;
+        if (POST == POST_W2D) {
+            // this thread's 20 points of its own column: byte loads strided by W, the 16 lanes of a row on consecutive bytes
+            const uint8_t* mcol = a.mask + (img / a.coils) * 200 * a.W + min(w0 + tid % kFL, a.W - 1);
 #pragma unroll
-        for (int k2 = 0; k2 < 20; ++k2) mbits |= (mrow[rot10(k2, g2)] ? 1u : 0u) << k2;
+            for (int k2 = 0; k2 < 20; ++k2) mbits |= (mcol[rot10(k2, g2) * a.W] ? 1u : 0u) << k2;
+        } else {
+            const uint8_t* mrow = a.mask + (img / a.coils) * 200;
+#pragma unroll
+            for (int k2 = 0; k2 < 20; ++k2) mbits |= (mrow[rot10(k2, g2)] ? 1u : 0u) << k2;
+        }
         if (POST == POST_DC || POST == POST_RESID) {
             const cf* kref = a.kref + img * 200 * a.W;
             const int colc = min(w0 + tid % kFL, a.W - 1);
@@ -371,6 +411,11 @@ __global__ __launch_bounds__(kFT, 3) void col200_kernel(ColArgs a) {
         } else if (POST == POST_RESID) {
 #pragma unroll
             for (int k2 = 0; k2 < 20; ++k2) v[k2] = ((mbits >> k2) & 1u) ? csub(v[k2], rr[k2]) : mk(0.f, 0.f);
+        } else if (POST == POST_W2D) {
+            float ws1, ws0;
+            col_weights(a, ws1, ws0);
+#pragma unroll
+            for (int k2 = 0; k2 < 20; ++k2) v[k2] = cscale(v[k2], ((mbits >> k2) & 1u) ? ws1 : ws0);
         }
         if (!INV_AFTER) {
             if (col < a.W) {
@@ -498,6 +543,7 @@ __global__ __launch_bounds__(kFT, 3) void row200_reduce_kernel(RowArgs a) {
         }
         __syncthreads();
     }
+    const float zf_beta = rpost_zf(POST) ? row_beta(a) : 0.f;
 #pragma unroll
     for (int o = 0; o < kMaxOut; ++o) {
         const int e = tid + o * kFT;
@@ -509,6 +555,8 @@ __global__ __launch_bounds__(kFT, 3) void row200_reduce_kernel(RowArgs a) {
             a.out_abs[(long)bt * HW + (long)h * 200 + i] = sqrtf(acc[o].x * acc[o].x + acc[o].y * acc[o].y);
         else if (POST == RPOST_RSS)
             a.out_abs[(long)bt * HW + (long)h * 200 + i] = sqrtf(acc[o].x);
+        else if (rpost_zf(POST))
+            row_store_zf<POST>(a, (long)bt * HW + (long)h * 200 + i, acc[o], zf_beta);
         else
             a.out[(long)bt * HW + (long)h * 200 + i] = acc[o];
     }
@@ -1509,6 +1557,84 @@ extern "C" int cine_expand_dc_hybrid(const float* img, const float* sens, const 
                                      const float* lambda_dev, float* hyb, int b, int t, int c, int h, int w,
                                      int hard_mask, void* stream) {
     return expand_dc(img, sens, kref, mask, lambda_dev, hyb, b, t, c, h, w, hard_mask, true, stream, "cine_expand_dc_hybrid");
+}
+
+// ------------------------------------------------------------------ image-space data consistency, masks that vary along w
+// The identity above does not need a row mask: for any 0/1 mask m(ky, kx), with k_ref = m k_ref and zf = sens_reduce(m k_ref),
+//     sens_reduce(DC(sens_expand(x))) = sum_c conj(S_c) IFFT2[ wgt(ky, kx) * FFT2(S_c x) ] + v/(1+v) zf,   wgt = m ? 1/(1+v) : 1
+// Only the shortcut goes: the weights no longer commute with the transform along w, so every coil image takes both line passes.
+//   1  S x -> row FFT -> ws                                   (row200_expand_kernel / row_pass_kernel<PRE_SMUL>)
+//   2  column FFT -> wgt -> column IFFT, in place on ws       (col200_kernel<1, POST_W2D, true>; two col_pass_kernel launches for h != 200)
+//   3  row IFFT -> conj(S) -> coil sum -> + beta zf -> out    (row200_reduce_kernel / row_pass_kernel<.., RPOST_REDUCE_ZF>)
+// The coil-wise k-space exists only inside step 2's workgroups; k_ref is read once per forward pass (for zf), not once per cascade.
+extern "C" size_t cine_image_dc_general_ws_bytes(int b, int t, int c, int h, int w) {
+    if (b <= 0 || t <= 0 || c <= 0 || h <= 0 || w <= 0) return 0;
+    return (size_t)b * t * c * h * w * sizeof(cf);
+}
+
+static int image_dc_general_impl(const float* img, const float* sens, const float* zf, const uint8_t* mask,
+                                 const float* lambda_dev, int lam_beta, float w_sampled, float w_unsampled, float beta,
+                                 float* out, int b, int t, int c, int h, int w, int magnitude,
+                                 void* ws, size_t ws_bytes, void* stream, const char* what) {
+    CINE_REQUIRE(img && sens && mask && out && ws, CINE_EINVAL, "%s: null pointer", what);
+    CINE_REQUIRE(b > 0 && t > 0 && c > 0 && c <= 32768 && h > 0 && w > 0, CINE_EINVAL, "%s: bad sizes", what);
+    CINE_REQUIRE((long)b * t <= 65535, CINE_EUNSUPPORTED, "%s: b*t > 65535", what);
+    CINE_REQUIRE(img != out, CINE_EINVAL, "%s: out must not alias img", what);
+    if (int e = check_n(h, what)) return e;
+    if (int e = check_n(w, what)) return e;
+    const size_t need = cine_image_dc_general_ws_bytes(b, t, c, h, w);
+    CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
+    hipStream_t st = as_stream(stream);
+    cf* hyb = reinterpret_cast<cf*>(ws);
+    RowArgs r{};
+    r.out = hyb;
+    r.W = w; r.s_in = (w + 1) / 2; r.s_out = w / 2;
+    r.sens = reinterpret_cast<const cf*>(sens);
+    r.img = reinterpret_cast<const cf*>(img);
+    r.T = t; r.C = c; r.H = h;
+    coil_tiling(c, w, r.rpw, r.cc);
+    const dim3 rgrid(ceil_div(h, r.rpw), b * t);
+    if (int e = launch_row<PRE_SMUL, RPOST_NONE>(r, rgrid, false, st)) return e;
+    const long nimg = (long)b * t * c;
+    const long step = 32768 / c * c;
+    for (long i0 = 0; i0 < nimg; i0 += step) {
+        const long ni = (nimg - i0) < step ? (nimg - i0) : step;
+        ColArgs ca{};
+        ca.in = hyb + i0 * h * w; ca.out = hyb + i0 * h * w;
+        ca.H = h; ca.W = w; ca.s_in = (h + 1) / 2; ca.s_out = h / 2; ca.coils = c;
+        ca.mask = mask + (i0 / c) * h * w;
+        ca.lam = lam_beta ? nullptr : lambda_dev; ca.w1 = w_sampled; ca.w0 = w_unsampled;
+        if (h == 200) {
+            if (int e = launch_col<POST_W2D, true>(ca, ni, false, st)) return e;
+            diag_count(D_DC_MASK2D);
+        } else {
+            if (int e = launch_col<POST_W2D>(ca, ni, false, st)) return e;
+            diag_count(D_DC_MASK2D);
+            ColArgs ci = ca; ci.mask = nullptr; ci.lam = nullptr;
+            if (int e = launch_col<POST_NONE>(ci, ni, true, st)) return e;
+        }
+    }
+    r.in = hyb; r.img = nullptr;
+    r.out = reinterpret_cast<cf*>(out); r.out_abs = out;
+    r.zf = reinterpret_cast<const cf*>(zf); r.lam = lambda_dev; r.lam_beta = lam_beta; r.beta = beta;
+    return magnitude ? launch_row<PRE_NONE, RPOST_REDUCE_ZF_ABS>(r, rgrid, true, st)
+                     : launch_row<PRE_NONE, RPOST_REDUCE_ZF>(r, rgrid, true, st);
+}
+
+extern "C" int cine_image_dc_general(const float* img, const float* sens, const float* zf, const uint8_t* mask,
+                                     const float* lambda_dev, float w_sampled, float w_unsampled, float beta,
+                                     float* out, int b, int t, int c, int h, int w, int magnitude,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    return image_dc_general_impl(img, sens, zf, mask, lambda_dev, 0, w_sampled, w_unsampled, beta, out, b, t, c, h, w, magnitude,
+                                 ws, ws_bytes, stream, "cine_image_dc_general");
+}
+
+// CineNet's H operator (models/cinenet.py:121-133) for a mask that varies along w: A^H M A img + softplus(*lambda_dev) img
+extern "C" int cine_normal_op_general(const float* img, const float* sens, const uint8_t* mask, const float* lambda_dev,
+                                      float* out, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream) {
+    CINE_REQUIRE(lambda_dev, CINE_EINVAL, "cine_normal_op_general: null lambda");
+    return image_dc_general_impl(img, sens, img, mask, lambda_dev, 1, 1.f, 0.f, 0.f, out, b, t, c, h, w, 0, ws, ws_bytes, stream,
+                                 "cine_normal_op_general");
 }
 
 // Gradient of cine_image_dc's output with respect to the sensitivity maps, per frame: part (b, t, c, h, w) (see imgdc_sgrad_kernel).

@@ -1,5 +1,6 @@
 // metrics_kernels.hip -- the steps either side of the reconstruction path:
 //   cine_apply_mask      : data * mask + 0.0 for Cartesian row masks             (data/transforms.py:66-92)
+//   cine_apply_mask2d    : the same for masks that vary along w, one (h, w) plane per frame
 //   cine_scale           : x *= s (fft2c / ifft2c with norm=None / "forward")    (utils/fftc.py:59-110, run_inference.py:66)
 //   cine_image_metrics   : center crop -> SSIM (7x7 uniform window, sample covariance, K1 .01, K2 .03, mean over the
 //                          window-valid region and over frames), NMSE, PSNR, MSE (utils/evaluate.py:6-50 = skimage's
@@ -21,6 +22,19 @@ __global__ void apply_mask_kernel(const float2* k, const uint8_t* mask, float2* 
         const float2 v = src[e];
         const float mv = m[row] ? 1.f : 0.f;
         dst[e] = make_float2(v.x * mv + 0.0f, v.y * mv + 0.0f);      // "+ 0.0" turns -0 into +0 as the reference does (:91)
+    }
+}
+
+// the same for a mask that varies along w: one (h, w) plane per frame
+__global__ void apply_mask2d_kernel(const float2* k, const uint8_t* mask, float2* out, long hw, int c) {
+    const long img = blockIdx.y;
+    const uint8_t* m = mask + (img / c) * hw;
+    const float2* src = k + img * hw;
+    float2* dst = out + img * hw;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < hw; e += (long)gridDim.x * blockDim.x) {
+        const float2 v = src[e];
+        const float mv = m[e] ? 1.f : 0.f;
+        dst[e] = make_float2(v.x * mv + 0.0f, v.y * mv + 0.0f);
     }
 }
 
@@ -155,6 +169,17 @@ extern "C" int cine_apply_mask(const float* kspace, const uint8_t* mask, float* 
     hipLaunchKernelGGL(apply_mask_kernel, dim3(grid1(hw, 256, 64), (unsigned)(bt * c)), dim3(256), 0, st,
                        reinterpret_cast<const float2*>(kspace), mask, reinterpret_cast<float2*>(out), hw, h, w, c);
     return check_launch("apply_mask_kernel");
+}
+
+extern "C" int cine_apply_mask2d(const float* kspace, const uint8_t* mask, float* out, long bt, int c, int h, int w, void* stream) {
+    CINE_REQUIRE(kspace && mask && out, CINE_EINVAL, "cine_apply_mask2d: null pointer");
+    CINE_REQUIRE(bt > 0 && c > 0 && h > 0 && w > 0 && bt * c <= 65535, CINE_EINVAL, "cine_apply_mask2d: bad sizes");
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(F_MISC, st);
+    const long hw = (long)h * w;
+    hipLaunchKernelGGL(apply_mask2d_kernel, dim3(grid1(hw, 256, 64), (unsigned)(bt * c)), dim3(256), 0, st,
+                       reinterpret_cast<const float2*>(kspace), mask, reinterpret_cast<float2*>(out), hw, c);
+    return check_launch("apply_mask2d_kernel");
 }
 
 extern "C" int cine_scale(float* x, long n, float s, void* stream) {

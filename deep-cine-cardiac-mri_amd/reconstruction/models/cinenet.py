@@ -38,7 +38,8 @@ class CineNetBlock(nn.Module):
 
     def HOperator(self, x, mask, sens_maps, _hyb=None, _tiled=None):
         """A^H M A x + softplus(lambda) x  (reference cinenet.py:121-133).  With the reference's row mask the normal
-        operator is one image-space kernel (cine_image_dc with weights (1, 0, 0)): the mask commutes with the row FFT."""
+        operator is one image-space kernel (cine_image_dc with weights (1, 0, 0)): the mask commutes with the row FFT; with a mask
+        that varies along w it is the same operator with both line passes (cine_normal_op_general)."""
         return ops.h_operator(x, sens_maps, mask, self.lambda_reg, _hyb, _tiled)
 
     def ConjGrad(self, x, b, mask, sens_maps, CG_iters: int, _tiled=None, _inplace=False):
@@ -50,7 +51,8 @@ class CineNetBlock(nn.Module):
             out = ops.conj_grad(x if _inplace else x.clone(), b, sens_maps, mask, self.lambda_reg, CG_iters, _tiled)
             if out is not None:
                 return out
-        hyb = None if rowmask else torch.empty((bsz, t, sens_maps.shape[2], h, w, 2), device=x.device, dtype=x.dtype)
+        general = ops.general_mask_fused(mask, sens_maps.expand(-1, t, -1, -1, -1, -1))      # cine_normal_op_general: its scratch is the binding's
+        hyb = None if (rowmask or general) else torch.empty((bsz, t, sens_maps.shape[2], h, w, 2), device=x.device, dtype=x.dtype)
         r = ops.axpby_dev(b, self.HOperator(x, mask, sens_maps, hyb, _tiled), num=_one(x), sign=-1.0)
         p = r.clone()
         rr_old = ops.dot(r, r)

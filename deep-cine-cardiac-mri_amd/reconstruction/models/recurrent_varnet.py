@@ -56,16 +56,19 @@ class VarNet_RNN(CRNNBody):
         hyb = ops.kspace_to_hybrid(ref_kspace)
         img = ops.hybrid_reduce(hyb, sens_maps)                                   # (1, t, 1, h, w, 2)
         rowmask = ops.is_row_mask(mask, ref_kspace)
+        gfused = ops.general_mask_fused(mask, ref_kspace)
         if rowmask:                                                               # image-space DC (see VarNet.forward)
             ops.kspace_to_hybrid(ref_kspace, out=hyb, mask=mask)
             zf = ops.hybrid_reduce(hyb, sens_maps)
+        elif gfused:                                                              # the same with both line passes (cine_image_dc_general)
+            zf = ops.sens_reduce(ops.apply_mask(ref_kspace, mask), sens_maps, destroy_input=True)
         state = self.zero_state(t, b, h, w, img)
         tiled = ops.sens_tile_pack(sens_maps) if rowmask else None               # the maps as the DC kernel reads them fastest, once per forward
         for _ in range(self.num_cascades):
             planes, _ = ops.normunet_pack(img.view(t, h, w, 2), norm=False)      # (t, 2, h, w)
             out, state = self.body(planes.view(t, 1, 2, h, w), state, planes)
             new_img = ops.normunet_unpack(out, None, h, w).view(1, t, 1, h, w, 2)
-            if rowmask:
+            if rowmask or gfused:
                 img = ops.image_dc(new_img, sens_maps, zf, mask, self.lambda_reg, sens_tiled=tiled)      # :80-90 + next reduce
             elif ops.is_general_mask(mask, ref_kspace):      # varies along w: the DC line term by term (ops.soft_dc_blend), then the reduce
                 k = ops.soft_dc_blend(ops.sens_expand_dc(new_img, sens_maps), ref_kspace, mask, self.lambda_reg.detach())

@@ -83,24 +83,32 @@ class XPDNet_RNN(CRNNBody):
         image_buffer = ops.repeat_complex(ops.sens_reduce(ref_kspace, sens_maps), n)       # (1, t, 1, h, w, 2n)
         rowmask = ops.is_row_mask(mask, ref_kspace) and not self.k_buffer_mode
         general = ops.is_general_mask(mask, ref_kspace)          # varies along w (reference recurrent_xpdnet.py multiplies by any broadcastable mask)
+        gfused = general and ops.GENERAL_MASK_FUSED
+        if gfused and not self.k_buffer_mode:     # A^H m (m A x0 - k_ref) = A^H m A x0 - zf: the image-space operator with both line passes (cine_image_dc_general)
+            zf = ops.sens_reduce(ops.apply_mask(ref_kspace, mask), sens_maps, destroy_input=True)
         hyb = None if (rowmask or general) else torch.empty_like(ref_kspace)
         if rowmask:
             zf = ops.hybrid_reduce(ops.kspace_to_hybrid(ref_kspace, mask=mask), sens_maps)
         state = self.zero_state(t, b, h, w, image_buffer)
-        keep = [i for i in range(2 * (n + 1)) if i not in (n, 2 * n + 1)]                  # channels [:n] and [n+1:-1]
+        keep = self.__dict__.get("_keep_idx")                                              # channels [:n] and [n+1:-1], as a device index made
+        if keep is None or keep.device != ref_kspace.device:                               # once (a list index is a host copy: not capturable)
+            keep = self.__dict__["_keep_idx"] = torch.tensor([i for i in range(2 * (n + 1)) if i not in (n, 2 * n + 1)], device=ref_kspace.device)
         nd = self.k_buffer_size
         kbuf = ops.repeat_complex(ref_kspace, nd) if self.k_buffer_mode else None
         tiled = ops.sens_tile_pack(sens_maps) if rowmask else None
         for i in range(self.num_cascades):
             x0 = ops.extract_complex(image_buffer, 0, n)
             if self.k_buffer_mode:                                                          # dual buffer + KSpaceCNN
-                fwd = ops.sens_expand_dc(x0, sens_maps) * mask + 0.0 if general else ops.sens_expand_dc(x0, sens_maps, None, mask, None, hard_mask=True)
+                fwd = (ops.apply_mask(ops.sens_expand_dc(x0, sens_maps), mask) if gfused else ops.sens_expand_dc(x0, sens_maps) * mask + 0.0) if general else ops.sens_expand_dc(x0, sens_maps, None, mask, None, hard_mask=True)
                 cat_k = torch.cat([kbuf[..., :nd], fwd[..., :1], ref_kspace[..., :1],
                                    kbuf[..., nd:], fwd[..., 1:], ref_kspace[..., 1:]], dim=-1)
                 kbuf = self.kspace_net[i](cat_k).contiguous()
-                bwd = ops.sens_reduce(ops.extract_complex(kbuf, 0, nd) * mask + 0.0, sens_maps)
+                k0 = ops.extract_complex(kbuf, 0, nd)
+                bwd = ops.sens_reduce(ops.apply_mask(k0, mask, out=k0) if gfused else k0 * mask + 0.0, sens_maps)
             elif rowmask:
                 bwd = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0), sens_tiled=tiled)      # A^H M (A x0 - k_ref) (:110-163)
+            elif gfused:
+                bwd = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0))
             elif general:
                 bwd = ops.masked_residual_backward(x0, sens_maps, ref_kspace, mask)
             else:
@@ -108,6 +116,6 @@ class XPDNet_RNN(CRNNBody):
                 bwd = ops.hybrid_reduce(hyb, sens_maps)                                     # masked backward op (:142-163)
             cat = torch.cat([image_buffer[..., :n], bwd[..., :1], image_buffer[..., n:], bwd[..., 1:]], dim=-1)
             planes = ops.chanlast_to_planes(cat.view(t, h, w, 2 * (n + 1)))                 # (t, 2(n+1), h, w)
-            out, state = self.body(planes.view(t, 1, 2 * (n + 1), h, w), state, planes[:, keep].contiguous())
+            out, state = self.body(planes.view(t, 1, 2 * (n + 1), h, w), state, planes.index_select(1, keep))
             image_buffer = ops.planes_to_chanlast(out, h, w).view(1, t, 1, h, w, 2 * n)
         return ops.complex_abs(ops.extract_complex(image_buffer, 0, n).squeeze(2))

@@ -176,6 +176,17 @@ class VarNet(nn.Module):
     def _forward_infer(self, masked_kspace, mask, sens_maps, acs):
         if sens_maps is None:
             sens_maps = self.sens_net(masked_kspace, mask, acs)
+        if ops.general_mask_fused(mask, masked_kspace):
+            # a mask that varies along w: the same chain on the coil-combined image, each DC step with both line passes
+            # (cine_image_dc_general); k_ref is read here, once, for the zero-filled term
+            image = ops.sens_reduce(masked_kspace, sens_maps)
+            if len(self.cascades) == 0:
+                return ops.complex_abs(image.squeeze(2))
+            zf = ops.sens_reduce(ops.apply_mask(masked_kspace, mask), sens_maps, destroy_input=True)      # sens_reduce(mask * k_ref)
+            last = len(self.cascades) - 1
+            for i, cascade in enumerate(self.cascades):
+                image = ops.image_dc(cascade.regularise(image), sens_maps, zf, mask, cascade.lambda_reg, magnitude=(i == last))
+            return image
         if not ops.is_row_mask(mask, masked_kspace):
             # not the reference's (b, t, 1, h, 1, 1) row mask: the literal k-space chain of reference varnet.py:145-151
             kspace = masked_kspace.clone()

@@ -208,6 +208,9 @@ class XPDNet(nn.Module):
         image_buffer = ops.repeat_complex(image, n)                             # (:307)
         rowmask = ops.is_row_mask(mask, masked_kspace) and not self.k_buffer_mode
         general = ops.is_general_mask(mask, masked_kspace)      # varies along w (reference xpdnet.py:128-131 multiplies by any broadcastable mask)
+        gfused = general and ops.GENERAL_MASK_FUSED
+        if gfused and not self.k_buffer_mode:     # A^H m (m A x0 - k_ref) = A^H m A x0 - zf: the image-space operator with both line passes (cine_image_dc_general)
+            zf = ops.sens_reduce(ops.apply_mask(masked_kspace, mask), sens_maps, destroy_input=True)
         hyb = None if (rowmask or general) else torch.empty_like(masked_kspace)
         if rowmask:     # A^H M k_ref, constant over the cascades: the K + backward step becomes A^H M A x0 - zf in one kernel
             zf = ops.hybrid_reduce(ops.kspace_to_hybrid(masked_kspace, mask=mask), sens_maps)
@@ -218,14 +221,17 @@ class XPDNet(nn.Module):
             x0 = ops.extract_complex(image_buffer, 0, n)                        # channel 0 of the buffer (:128)
             if self.k_buffer_mode:
                 # dual buffer: the k-space net needs the whole k-space, so it is materialised (:385-403)
-                fwd = ops.sens_expand_dc(x0, sens_maps) * mask + 0.0 if general else ops.sens_expand_dc(x0, sens_maps, None, mask, None, hard_mask=True)
+                fwd = (ops.apply_mask(ops.sens_expand_dc(x0, sens_maps), mask) if gfused else ops.sens_expand_dc(x0, sens_maps) * mask + 0.0) if general else ops.sens_expand_dc(x0, sens_maps, None, mask, None, hard_mask=True)
                 cat = torch.cat([kbuf[..., :nd], fwd[..., :1], masked_kspace[..., :1],
                                  kbuf[..., nd:], fwd[..., 1:], masked_kspace[..., 1:]], dim=-1)
                 kbuf = self.kspace_net[i_domain // 2](cat).contiguous()
-                k0 = ops.extract_complex(kbuf, 0, nd) * mask + 0.0              # masked backward op (:161-167)
+                k0 = ops.extract_complex(kbuf, 0, nd)
+                k0 = ops.apply_mask(k0, mask, out=k0) if gfused else k0 * mask + 0.0      # masked backward op (:161-167)
                 backward_img = ops.sens_reduce(k0, sens_maps)
             elif rowmask:
                 backward_img = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0), sens_tiled=tiled)   # A^H M (A x0 - k_ref)
+            elif gfused:
+                backward_img = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0))
             elif general:
                 backward_img = ops.masked_residual_backward(x0, sens_maps, masked_kspace, mask)
             else:

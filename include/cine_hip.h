@@ -150,6 +150,25 @@ int cine_normal_op_t(const float* img, const float* sens, const float* sens_tile
 int cine_normal_op_pd(const float* img, const float* sens, const uint8_t* mask, const float* lambda_dev,
                       float* out, float* pd_part, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
 
+/* cine_image_dc for a sampling mask that varies along w (partial-echo readouts, 2-D variable density, k-t patterns with a readout
+ * cut-off: the reference's models accept (b|1, t|1, 1, h, w, 1), varnet.py:281-282).  The identity needs no row mask:
+ *     out = sum_c conj(S_c) IFFT2[ wgt(ky, kx) * FFT2(S_c img) ] + beta * zf,   wgt = mask ? w_sampled : w_unsampled
+ * equals sens_reduce(DC(sens_expand(img))) with zf = sens_reduce(mask * k_ref); only the weights no longer commute with the transform
+ * along w, so each coil image takes both line passes: coil expand + row FFT into ws, column FFT -> weights -> column IFFT in place
+ * (one kernel for h == 200), row IFFT + conj(S) + coil sum + beta * zf (+ magnitude) into out.  Same contract as cine_image_dc
+ * (lambda_dev, zf may be NULL, magnitude, out must not alias img) except mask: uint8 (b, t, h, w).  ws: cine_image_dc_general_ws_bytes()
+ * = the b*t*c*h*w complex hybrid-space coil images, always needed.  Both h and w may be any length cine_fft_line_supported() accepts
+ * (CINE_EUNSUPPORTED otherwise); c <= 32768.  Every argument is checked before the first launch. */
+size_t cine_image_dc_general_ws_bytes(int b, int t, int c, int h, int w);
+int cine_image_dc_general(const float* img, const float* sens, const float* zf, const uint8_t* mask,
+                          const float* lambda_dev, float w_sampled, float w_unsampled, float beta,
+                          float* out, int b, int t, int c, int h, int w, int magnitude,
+                          void* ws, size_t ws_bytes, void* stream);
+/* cine_normal_op for such a mask: out = A^H M A img + softplus(*lambda_dev) img (models/cinenet.py:121-133), mask uint8 (b, t, h, w).
+ * Shapes and workspace as cine_image_dc_general. */
+int cine_normal_op_general(const float* img, const float* sens, const uint8_t* mask, const float* lambda_dev,
+                           float* out, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
+
 /* cine_kspace_to_hybrid of (mask * k) without reading the rows the mask drops: the hybrid-space image of the
  * measured lines only (the zero-filled term zf above: cine_hybrid_reduce of it).  k, hyb (bt, c, h, w, 2); mask (bt, h). */
 int cine_masked_kspace_to_hybrid(const float* k, const uint8_t* mask, float* hyb, int bt, int c, int h, int w,
@@ -160,6 +179,10 @@ int cine_masked_kspace_to_hybrid(const float* k, const uint8_t* mask, float* hyb
 /* out = kspace * mask + 0.0 for a Cartesian row mask (reference data/transforms.py:66-92 `apply_mask`, :91).
  * kspace, out (bt, c, h, w, 2) (may alias); mask uint8 (bt, h). */
 int cine_apply_mask(const float* kspace, const uint8_t* mask, float* out, long bt, int c, int h, int w, void* stream);
+
+/* The same for a mask that varies along w: mask uint8 (bt, h, w), one plane per frame.  Bit-equal to the torch expression
+ * kspace * mask + 0.0 (-0.0 becomes +0.0); out may alias kspace. */
+int cine_apply_mask2d(const float* kspace, const uint8_t* mask, float* out, long bt, int c, int h, int w, void* stream);
 
 /* x[i] *= s, in place: the "backward" / "forward" normalisations of torch.fft on top of the ortho kernels
  * (reference utils/fftc.py:59-110 with norm=None, traintest_scripts/run_inference.py:66). */
@@ -827,7 +850,7 @@ int cine_profile_begin(void);
  * 7 the same in its three-pass volume form, 8 the coarse K-split kernel, 9 the streaming 1x1 kernel of cine_conv1x1_bias,
  * 10 the general kernel's two-set pair form, 11 the general kernel with vectorised staging, 12 the general kernel with element-wise
  * staging -- input-gradient launches on the general kernel count in 10 .. 12 too; 13 / 14 cine_pool3d_act on its float4 / scalar
- * kernel).  reset != 0 returns the count and zeroes it;
+ * kernel; 15 column-pass launches that weight by a mask plane: cine_image_dc_general / cine_normal_op_general).  reset != 0 returns the count and zeroes it;
  * -1 for an unknown counter. */
 long cine_diag_counter(int which, int reset);
 /* Diagnostics: a one-workgroup kernel that runs for `microseconds` (1 .. 100 000; clock-bounded AND iteration-bounded: it always ends).  The
