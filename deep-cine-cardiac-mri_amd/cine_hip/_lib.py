@@ -146,6 +146,11 @@ _SIGS = {
     "cine_combine_target": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_espirit_lag_kernels": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "cine_espirit_eig": (c_int, [P, P, P, c_int, c_long, c_int, c_float, P]),
+    "cine_espirit_gram_ws_bytes": (c_size_t, [c_int] * 5),
+    "cine_espirit_gram": (c_int, [P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
+    "cine_zgemm_f64": (c_int, [P, P, P, P, c_int, c_double, c_double, c_double, c_double, P]),
+    "cine_espirit_projector_ws_bytes": (c_size_t, [c_int]),
+    "cine_espirit_projector": (c_int, [P, c_int, c_double, c_int, P, P, P, P, c_size_t, P]),
     "cine_conv3x3_dgrad_packed_floats": (c_size_t, [c_int, c_int]),
     "cine_tconv2x2_dgrad_packed_floats": (c_size_t, [c_int, c_int]),
     "cine_conv1x1_dgrad_packed_floats": (c_size_t, [c_int, c_int]),

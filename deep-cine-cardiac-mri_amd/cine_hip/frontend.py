@@ -14,6 +14,9 @@
 ``espirit_maps``    what the reference gets from the BART toolbox (``bart ecalib -r N``, mri_data.py:296,
                     transforms.py:429): ESPIRiT sensitivity maps (Uecker et al., MRM 71:990-1001, 2014) with ecalib's
                     defaults -- 6 x 6 kernels, singular-value threshold 0.001, eigenvalue crop 0.8, first map.
+                    ``method="sign"`` takes the projector from a matrix sign function on the float64 matrix cores instead of an
+                    eigen-decomposition (``espirit_gram``, ``espirit_projector``): no host read, capturable, what ``SlicePipeline`` runs
+                    for ``sens_maps="espirit"`` on ``time_average`` of the slice.
 ``ecalib``          the same behind ecalib's array convention ((1, x, y, coil) complex in, (x, y, coil) out), so the
                     reference's two call sites change by one line.
 
@@ -317,10 +320,59 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
     return out
 
 
+def time_average(masked_kspace: torch.Tensor) -> torch.Tensor:
+    """masked k-space of one cine slice (t, coil, ny, nx, 2) -> its average over the frames (coil, ny, nx, 2), the input of the
+    calibration (data/transforms.py:426-427).  This is the form ``SlicePipeline`` computes for ``sens_maps="espirit"``."""
+    return masked_kspace.mean(dim=0)
+
+
+def espirit_projector(gram: torch.Tensor, thresh: float = 1e-3, sign_iters: int = 60) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """gram (n, n) complex128 Hermitian on the GPU -> (P (n, n, 2) float32, lam_max (1,) float64, residual (1,) float64): the projector
+    onto the eigenvectors with eigenvalue >= thresh^2 lam_max as 1/2 (I + sign(gram - thresh^2 lam_max I)), by Newton-Schulz steps on the
+    float64 matrix cores (cine_espirit_projector).  residual = max |X^2 - I| of the sign matrix handed out.  No host read."""
+    if not (isinstance(gram, torch.Tensor) and gram.is_cuda and gram.dtype == torch.complex128 and gram.dim() == 2
+            and gram.shape[0] == gram.shape[1] and gram.is_contiguous()):
+        raise CineHipError("espirit_projector: gram must be a contiguous square complex128 GPU tensor")
+    n = gram.shape[0]
+    dev = gram.device
+    proj = torch.empty((n, n, 2), device=dev, dtype=torch.float32)
+    lam = torch.empty(1, device=dev, dtype=torch.float64)
+    resid = torch.empty(1, device=dev, dtype=torch.float64)
+    nbytes = lib().cine_espirit_projector_ws_bytes(n)
+    ws = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    check(lib().cine_espirit_projector(gram.data_ptr(), n, float(thresh), int(sign_iters), proj.data_ptr(), lam.data_ptr(), resid.data_ptr(),
+                                       ws.data_ptr(), nbytes, ops._stream()), "cine_espirit_projector")
+    return proj, lam, resid
+
+
+def espirit_gram(kspace: torch.Tensor, r: int = 24, k: int = 6) -> torch.Tensor:
+    """kspace (coil, ny, nx, 2) float32 -> the Gram matrix (k k coil square, complex128) of the k x k patches of its central
+    min(r, ny) x min(r, nx) block, columns ordered (py, px, coil) (cine_espirit_gram)."""
+    kspace = ops._dev(kspace, "espirit_gram kspace")
+    c, ny, nx, _ = kspace.shape
+    n = k * k * c
+    gram = torch.empty((n, n), device=kspace.device, dtype=torch.complex128)
+    nbytes = lib().cine_espirit_gram_ws_bytes(c, ny, nx, int(r), int(k))
+    ws = torch.empty(max(nbytes, 16), device=kspace.device, dtype=torch.uint8)
+    check(lib().cine_espirit_gram(kspace.data_ptr(), gram.data_ptr(), ws.data_ptr(), nbytes, c, ny, nx, int(r), int(k), ops._stream()),
+          "cine_espirit_gram")
+    return gram
+
+
 def espirit_maps(kspace: torch.Tensor, r: int = 24, k: int = 6, thresh: float = 1e-3, crop: float = 0.8,
-                 iters: int = 100) -> Tuple[torch.Tensor, torch.Tensor]:
+                 iters: int = 100, *, method: str = "eigh", sign_iters: int = 60, return_residual: bool = False):
     """kspace (coil, ny, nx, 2) float32 (centered, ortho; e.g. the time average of a cine slice) ->
-    (maps (coil, ny, nx, 2), eigenvalue map (ny, nx)).  r: side of the central calibration region (ecalib -r)."""
+    (maps (coil, ny, nx, 2), eigenvalue map (ny, nx)).  r: side of the central calibration region (ecalib -r).
+    ``method="eigh"`` (the default): the Gram matrix and its eigen-decomposition are library calls in complex128
+    (torch.linalg.eigh checks its result on the host, and the kept eigenvectors are selected by a boolean index).
+    ``method="sign"``: cine_espirit_gram, then the projector as a matrix sign function (``espirit_projector``, ``sign_iters``
+    Newton-Schulz steps): no host read, every shape fixed by the input's shape, so ``torch.cuda.graph`` captures the call and replays it
+    on new data.  ``return_residual=True`` adds the device scalar max |X^2 - I| of the sign matrix ((1,) float64; "sign" only): above
+    1e-6 an eigenvalue of the Gram matrix sits at the threshold and ``sign_iters`` has to be raised."""
+    if method not in ("eigh", "sign"):
+        raise ValueError(f"espirit_maps: method must be 'eigh' or 'sign', got {method!r}")
+    if return_residual and method != "sign":
+        raise ValueError("espirit_maps: return_residual needs method='sign'")
     kspace = ops._dev(kspace, "espirit_maps kspace")
     c, ny, nx, _ = kspace.shape
     if c > 32:
@@ -328,6 +380,10 @@ def espirit_maps(kspace: torch.Tensor, r: int = 24, k: int = 6, thresh: float = 
     ry, rx = min(int(r), ny), min(int(r), nx)
     if ry < k or rx < k or ny < 2 * k - 1 or nx < 2 * k - 1:
         raise ValueError("calibration region / image smaller than the kernel")
+    if method == "sign":
+        proj, _, resid = espirit_projector(espirit_gram(kspace, r, k), thresh, sign_iters)
+        maps, lam = _maps_from_projector(proj, c, k, ny, nx, iters, crop)
+        return (maps, lam, resid) if return_residual else (maps, lam)
     y0, x0 = ny // 2 - ry // 2, nx // 2 - rx // 2
     acs = torch.view_as_complex(kspace)[:, y0:y0 + ry, x0:x0 + rx].to(torch.complex128)
     # rows = all k x k patches, columns ordered (py, px, coil)
@@ -340,17 +396,23 @@ def espirit_maps(kspace: torch.Tensor, r: int = 24, k: int = 6, thresh: float = 
     keep = ev >= (thresh * thresh) * ev[-1]                                  # sigma >= thresh * sigma_max
     v = vec[:, keep]
     proj = torch.view_as_real((v @ v.conj().transpose(0, 1)).to(torch.complex64)).contiguous()
-    kpad = torch.empty((c * c, ny, nx, 2), device=kspace.device, dtype=torch.float32)
+    return _maps_from_projector(proj, c, k, ny, nx, iters, crop)
+
+
+def _maps_from_projector(proj: torch.Tensor, c: int, k: int, ny: int, nx: int, iters: int, crop: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The image-space half of the calibration: lag kernels of the projector -> the c x c operator of every pixel -> its dominant
+    eigenpair."""
+    kpad = torch.empty((c * c, ny, nx, 2), device=proj.device, dtype=torch.float32)
     check(lib().cine_espirit_lag_kernels(proj.data_ptr(), kpad.data_ptr(), c, k, ny, nx, ops._stream()), "cine_espirit_lag_kernels")
     m = ops.fft2c(kpad, inverse=True)
-    maps = torch.empty((c, ny, nx, 2), device=kspace.device, dtype=torch.float32)
-    lam = torch.empty((ny, nx), device=kspace.device, dtype=torch.float32)
+    maps = torch.empty((c, ny, nx, 2), device=proj.device, dtype=torch.float32)
+    lam = torch.empty((ny, nx), device=proj.device, dtype=torch.float32)
     check(lib().cine_espirit_eig(m.data_ptr(), maps.data_ptr(), lam.data_ptr(), c, ny * nx, int(iters), float(crop), ops._stream()),
           "cine_espirit_eig")
     return maps, lam
 
 
-def ecalib(time_avg_kspace, *, r: int):
+def ecalib(time_avg_kspace, *, r: int, method: str = "eigh"):
     """``r`` is required: the reference's two call sites differ (`-r 200`, mri_data.py:296; `-r 15`, transforms.py:429).
     Stand-in for ``bart.bart(2, 'ecalib -r N', time_avg_kspace)[0][..., 0]`` at the reference's call sites
     (mri_data.py:295-297, transforms.py:427-430): (1, x, y, coil) complex (numpy or tensor) -> (x, y, coil) complex of
@@ -362,14 +424,14 @@ def ecalib(time_avg_kspace, *, r: int):
         raise ValueError("ecalib expects (1, x, y, coil)")
     dev = t.device if t.is_cuda else torch.device("cuda")
     k = torch.view_as_real(t[0].permute(2, 0, 1).contiguous().to(dev)).contiguous()
-    maps, _ = espirit_maps(k, r=r)
+    maps, _ = espirit_maps(k, r=r, method=method)
     out = torch.view_as_complex(maps).permute(1, 2, 0).contiguous()
     return out.cpu().numpy() if is_np else out.to(t.device)
 
 
 def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(200, 200), crop_target=(180, 180), n_slices: int = 15,
                     filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, ecalib_r: int = 200, virtual_coils: Optional[int] = None,
-                    coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24):
+                    coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, espirit_method: str = "eigh"):
     """``SliceDataset.__getitem__`` of the reference (data/mri_data.py:267-311) in one piece, on the device: scale -> IFFT2 -> crop +
     frame selection + Gaussian filter -> FFT2 (k-space of the filtered crop) -> sensitivity maps from the time-averaged k-space
     (ESPIRiT, where the reference shells out to ``bart ecalib -r 200``; pass ``sens`` (coil, X, Y) complex to use given maps) ->
@@ -378,7 +440,7 @@ def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(2
     Returns the reference's sample tuple (kspace (t, coil, X, Y) complex64, mask, target (t, cx, cy) float32, attrs, fname, dataslice)
     as numpy arrays, like the reference (the ``*DataTransform`` classes take it from there, data/transforms.py:300-352).
     ``virtual_coils`` / ``coil_matrix`` / ``cc_region``: as in prepare_slice; k-space, the calibration and ``sens`` are then on the V
-    virtual coils, so raw data with more than 32 coils calibrates whenever V <= 32."""
+    virtual coils, so raw data with more than 32 coils calibrates whenever V <= 32.  ``espirit_method``: ``espirit_maps``' ``method``."""
     import numpy as np
     if hasattr(source, "keys") and "y" in source:
         raw = np.asarray(source["y"])
@@ -394,7 +456,7 @@ def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(2
         raise ValueError(f"sens has {tuple(sens.shape)[0]} coils, the compressed data {kspace.shape[1]}")
     if sens is None:
         time_avg = torch.view_as_complex(kspace.mean(dim=0, keepdim=True).contiguous()).permute(0, 2, 3, 1)     # (1, X, Y, coil), :295
-        smaps = ecalib(time_avg, r=ecalib_r).permute(2, 0, 1).contiguous()                  # (coil, X, Y), :297-298
+        smaps = ecalib(time_avg, r=ecalib_r, method=espirit_method).permute(2, 0, 1).contiguous()                  # (coil, X, Y), :297-298
     else:
         smaps = torch.as_tensor(sens).to(torch.complex64).cuda()
     target = combine_target(filt, torch.view_as_real(smaps).contiguous(), crop_target)      # :302-303

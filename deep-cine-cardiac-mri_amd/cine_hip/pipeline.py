@@ -34,6 +34,18 @@ The mask follows the k-space's place; host masks may be any numeric 0 / 1 mask t
 (converted on the host), device masks must be uint8 or bool.  ``sens_maps`` (b, 1, c, h, w, 2) is required by CineNet /
 CineNet_RNN, optional for VarNet, and not accepted by the other models.
 
+``sens_maps="espirit"`` (the same three models): the maps are calibrated IN FLIGHT, per slice, as the reference does with
+``bart ecalib -r 15`` on the time-averaged masked k-space (data/transforms.py:425-432).  Inside the slot's graph, behind the front-end of
+a raw set and for every batch element, ``frontend.espirit_maps(frontend.time_average(mk[i]), r=ecalib_r, method="sign",
+sign_iters=sign_iters)`` writes a static (b, 1, c, h, w, 2) buffer that the model reads: the result is bit for bit
+``model(mk, mask, maps)`` with those maps computed eagerly.  The projector of the calibration comes from a matrix sign function
+(Newton-Schulz steps on the float64 matrix cores) instead of an eigen-decomposition, so nothing waits for the host.  The residual
+max |X^2 - I| of every slice's sign matrix is copied to pinned memory with the outputs; ``results`` / ``drain`` raise ``CineHipError``
+naming the slice's tag when it exceeds 1e-6 (an eigenvalue of the Gram matrix sits at the threshold: raise ``sign_iters``) -- no silent
+wrong maps.  ``("espirit", ecalib_r, kernel, thresh, crop, sign_iters)`` stands for the sens shape in the set key (``espirit_key``).
+With ``coil_matrix=`` the calibration runs on the V virtual coils.  A mask that varies along w is served with VarNet this way too
+(the sensitivity network is not run).
+
 The model is called as ``model(mk, mask)`` or ``model(mk, mask, sens)``, without ``acs=``: the ACS window is found on the
 device (``ops.acs_window_dev``) and a graph captured with one slice's mask gives any other slice's result.  That window is
 read from row masks only; a mask that varies along w with a model that runs its sensitivity network raises ``CineHipError``.
@@ -217,9 +229,31 @@ def _check_mask(mask, ks_shape):
     return (m, "pinned", want) if canonical else (m.contiguous(), "pageable", want)
 
 
+ESPIRIT_KERNEL, ESPIRIT_THRESH, ESPIRIT_CROP = 6, 1e-3, 0.8      # ecalib's defaults, as frontend.espirit_maps has them
+ESPIRIT_RESIDUAL_MAX = 1e-6     # max |X^2 - I| of the sign matrix above which the projector is not one at float32 resolution
+
+
+def espirit_key(ecalib_r: int = 15, sign_iters: int = 60):
+    """What stands for the sens shape in a set key when the maps are calibrated in flight (``sens_maps="espirit"``)."""
+    r, it = int(ecalib_r), int(sign_iters)
+    if r < ESPIRIT_KERNEL or it < 1:
+        raise CineHipError(f"sens_maps='espirit': ecalib_r must be at least the kernel size {ESPIRIT_KERNEL} and sign_iters at least 1, "
+                           f"got {ecalib_r!r}, {sign_iters!r}")
+    return ("espirit", r, ESPIRIT_KERNEL, ESPIRIT_THRESH, ESPIRIT_CROP, it)
+
+
 def _check_sens(pipe, sens_maps, ks_shape, general: bool):
-    """(float32 pairs or None, kind or None)."""
+    """(float32 pairs, "espirit" or None; kind or None)."""
     b, _, c, h, w, _ = ks_shape
+    if isinstance(sens_maps, str):
+        if sens_maps != "espirit":
+            raise CineHipError(f"sens_maps: {sens_maps!r} is not a tensor, None or 'espirit'")
+        if not pipe._takes_sens:
+            raise CineHipError(f"{type(pipe.model).__name__} takes no sens_maps")
+        if c > 32 or h < 2 * ESPIRIT_KERNEL - 1 or w < 2 * ESPIRIT_KERNEL - 1:
+            raise CineHipError(f"sens_maps='espirit': at most 32 coils and an image of at least {2 * ESPIRIT_KERNEL - 1} x "
+                               f"{2 * ESPIRIT_KERNEL - 1}, got {c} coils, {h} x {w}")
+        return "espirit", None
     if sens_maps is not None:
         if not pipe._takes_sens:
             raise CineHipError(f"{type(pipe.model).__name__} takes no sens_maps")
@@ -246,7 +280,7 @@ class _Source:
     raw = None                                      # no front-end in this set's graphs
     input_names = ("mk", "mask", "sens")
 
-    def __init__(self, pipe, masked_kspace, mask, sens_maps):
+    def __init__(self, pipe, masked_kspace, mask, sens_maps, ecalib_r=15, sign_iters=60):
         mk, self.mk_kind = _pairs(masked_kspace, "masked_kspace")
         if mk.dim() != 6:
             raise CineHipError(f"masked_kspace: shape {tuple(mk.shape)}; expected (b, t, c, h, w, 2) or complex (b, t, c, h, w)")
@@ -254,14 +288,19 @@ class _Source:
         self.mk_shape = tuple(mk.shape)
         self.mask, self.mask_kind, self.mask_shape = _check_mask(mask, mk.shape)
         self.sens, self.sens_kind = _check_sens(pipe, sens_maps, mk.shape, self.mask_shape[4] > 1)
+        self.espirit = None
+        if isinstance(self.sens, str):                                       # calibrated in flight: nothing to copy in
+            self.sens, self.espirit = None, espirit_key(ecalib_r, sign_iters)
         _same_device(pipe, (("masked_kspace", self.mk), ("mask", self.mask), ("sens_maps", self.sens)))
-        self.key = (tuple(mk.shape), self.mask_shape, None if self.sens is None else tuple(self.sens.shape))
+        self.key = (tuple(mk.shape), self.mask_shape, self.espirit or (None if self.sens is None else tuple(self.sens.shape)))
 
     def alloc(self, pipe):
         dev = pipe.device
-        return {"mk": torch.empty(self.mk_shape, device=dev, dtype=torch.float32),
-                "mask": torch.empty(self.mask_shape, device=dev, dtype=torch.uint8),
-                "sens": None if self.sens is None else torch.empty(self.sens.shape, device=dev, dtype=torch.float32)}
+        b = {"mk": torch.empty(self.mk_shape, device=dev, dtype=torch.float32),
+             "mask": torch.empty(self.mask_shape, device=dev, dtype=torch.uint8),
+             "sens": None if self.sens is None else torch.empty(self.sens.shape, device=dev, dtype=torch.float32)}
+        _alloc_espirit(b, self, dev)
+        return b
 
     def items(self, b):
         """(name, destination in buffer set b, source, kind) of every input the copy stream moves."""
@@ -271,13 +310,23 @@ class _Source:
         return it
 
 
+def _alloc_espirit(b, src, dev) -> None:
+    """The static maps the calibration writes and the model reads, and the residual of every batch element's sign iteration."""
+    if src.espirit is not None:
+        n, _, c, h, w, _ = src.mk_shape
+        b["sens"] = torch.empty((n, 1, c, h, w, 2), device=dev, dtype=torch.float32)
+        b["resid"] = torch.empty(n, device=dev, dtype=torch.float64)
+
+
 _CC_MAX_COILS, _CC_MAX_VIRTUAL = 128, 32            # the limits of cine_coil_compress (include/cine_hip.h)
 
 
-def raw_set_key(raw_shape, n_frames, crop_shape, filter_size, scaling, apply_mask, mask_shape, sens_shape, coil_matrix_shape=None):
+def raw_set_key(raw_shape, n_frames, crop_shape, filter_size, scaling, apply_mask, mask_shape, sens_shape, coil_matrix_shape=None,
+                espirit=None):
     """The key of the graph set that serves a ``submit_raw`` call, from shapes and settings alone: kind, kept raw shape, virtual coils,
     crop, filter, scaling, apply_mask, mask shape, sens shape.  With a coil matrix the raw coil count is NOT part of it: the compression
-    runs in front of the graph, so scans with different coil counts and one V share a set."""
+    runs in front of the graph, so scans with different coil counts and one V share a set.  ``espirit``: ``espirit_key(ecalib_r,
+    sign_iters)`` for ``sens_maps="espirit"``; it takes the place of the sens shape."""
     t, nx, ny, c = (int(v) for v in tuple(raw_shape)[:4])
     n = min(int(n_frames), t)
     if n < 1 or nx < 1 or ny < 1 or c < 1:
@@ -285,7 +334,8 @@ def raw_set_key(raw_shape, n_frames, crop_shape, filter_size, scaling, apply_mas
     kept = (n, nx, ny, c) if coil_matrix_shape is None else (n, nx, ny)
     v = None if coil_matrix_shape is None else int(tuple(coil_matrix_shape)[0])
     return ("raw", kept, v, (int(crop_shape[0]), int(crop_shape[1])), tuple(float(f) for f in filter_size), float(scaling),
-            bool(apply_mask), tuple(int(m) for m in mask_shape), None if sens_shape is None else tuple(int(m) for m in sens_shape))
+            bool(apply_mask), tuple(int(m) for m in mask_shape),
+            tuple(espirit) if espirit is not None else None if sens_shape is None else tuple(int(m) for m in sens_shape))
 
 
 class _RawSource:
@@ -293,7 +343,8 @@ class _RawSource:
     matrix, the front-end's settings, the set key."""
     input_names = ("raw", "mask", "sens", "cmat")
 
-    def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask):
+    def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask, ecalib_r=15,
+                 sign_iters=60):
         if not isinstance(raw, (np.ndarray, torch.Tensor)):
             raise CineHipError(f"raw: expected a torch tensor or a numpy array, got {type(raw).__name__}")
         if raw.ndim < 4 or raw.shape[0] < 1 or int(n_frames) < 1:
@@ -325,10 +376,13 @@ class _RawSource:
         self.mask, self.mask_kind, self.mask_shape = _check_mask(mask, self.mk_shape)
         # a mask that varies along w: the rules of ``submit`` (the sensitivity network's ACS window needs a row mask)
         self.sens, self.sens_kind = _check_sens(pipe, sens_maps, self.mk_shape, self.mask_shape[4] > 1)
+        self.espirit = None
+        if isinstance(self.sens, str):                                       # calibrated in flight, on the V virtual coils with a coil matrix
+            self.sens, self.espirit = None, espirit_key(ecalib_r, sign_iters)
         _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat)))
         self.raw_nbytes = x.numel() * 4
         self.key = raw_set_key((n, nx, ny, c), n, self.crop, self.filter, self.scaling, self.apply_mask, self.mask_shape,
-                               None if self.sens is None else self.sens.shape, None if self.cmat is None else self.cmat.shape)
+                               None if self.sens is None else self.sens.shape, None if self.cmat is None else self.cmat.shape, self.espirit)
 
     def alloc(self, pipe):
         """raw: a byte buffer (with a coil matrix it may be replaced by a larger one later: no graph holds its address).  cc: what the
@@ -342,6 +396,7 @@ class _RawSource:
              "mask": torch.empty(self.mask_shape, device=dev, dtype=torch.uint8),
              "sens": None if self.sens is None else torch.empty(self.sens.shape, device=dev, dtype=torch.float32)}
         b["front"] = b["cc"] if self.v is not None else self.raw_view(b)
+        _alloc_espirit(b, self, dev)
         return b
 
     def raw_view(self, b):
@@ -383,6 +438,7 @@ class _Set:
         self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front" in a raw set)
         self.raw = None         # the front-end's settings when the graphs start from raw data (the _RawSource that built the set)
         self.raw_bytes = 0      # capacity of each raw byte buffer
+        self.espirit = None     # espirit_key(...) when the graphs calibrate the maps themselves (sens_maps="espirit")
         self.graphs = {}        # (slot, parity) -> (graph, static outputs)
         self.ready = {}         # (slot, parity) -> event recorded on the copy stream behind the copy into the set
         self.done = {}          # (slot, parity) -> event recorded on the slot stream behind the output copy of the set's reader
@@ -419,29 +475,35 @@ class SlicePipeline:
         self.model, self.slots, self.device, self.graphs, self.out, self.zero_filled = model, slots, device, bool(graphs), out, bool(zero_filled)
         self._takes_sens, self._needs_sens = _forward_params(model)
         self._sched = SliceSchedule(slots)
-        self._recs = {}           # index -> [handle, outputs, inputs kept alive until the slice is done]
+        self._recs = {}           # index -> [handle, outputs, inputs kept alive until the slice is done, ESPIRiT residuals (pinned) or None]
         self._set = None
         self._closed = False
         self._builds = 0
         self.streams, self.copy_stream = pipeline_streams(device, slots)
 
     # ---- public ----------------------------------------------------------------------------------------------------------
-    def submit(self, masked_kspace, mask, sens_maps=None, tag=None) -> SliceHandle:
-        """Enqueue one slice.  Returns at once, unless 2 x slots slices are pending: then it waits for the oldest one."""
+    def submit(self, masked_kspace, mask, sens_maps=None, tag=None, *, ecalib_r: int = 15, sign_iters: int = 60) -> SliceHandle:
+        """Enqueue one slice.  Returns at once, unless 2 x slots slices are pending: then it waits for the oldest one.
+        ``sens_maps="espirit"``: the maps of every batch element are calibrated inside the slot's graph from the time average of its masked
+        k-space, ``frontend.espirit_maps(frontend.time_average(mk[i]), r=ecalib_r, method="sign", sign_iters=sign_iters)`` (the
+        reference's ``bart ecalib -r 15``, data/transforms.py:425-432)."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit after close()")
-        return self._submit(_Source(self, masked_kspace, mask, sens_maps), tag)
+        return self._submit(_Source(self, masked_kspace, mask, sens_maps, ecalib_r, sign_iters), tag)
 
     def submit_raw(self, raw, mask, sens_maps=None, tag=None, *, crop_shape=(200, 200), n_frames: int = 15,
-                   filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True) -> SliceHandle:
+                   filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True,
+                   ecalib_r: int = 15, sign_iters: int = 60) -> SliceHandle:
         """Enqueue one slice from its RAW k-space (t, x, y, coil) -- complex64 or float32 pairs, in any of the four places ``submit`` takes
         its input from.  Only ``raw[:min(n_frames, t)]`` is copied to the device.  ``frontend.prepare_masked_slice`` and the model run on
         the slot's stream inside the slot's graph; see the module docstring.  ``mask``: the mask on the crop grid, a row mask or one that varies along w under the
         rules of ``submit`` (the sensitivity network needs a row mask: pass ``sens_maps``); ``sens_maps``
-        (1, 1, C, X, Y, 2) on the crop grid (on the V virtual coils with ``coil_matrix`` (V, coil))."""
+        (1, 1, C, X, Y, 2) on the crop grid (on the V virtual coils with ``coil_matrix`` (V, coil)), or ``"espirit"``: calibrated in the
+        graph, behind the front-end, from the masked k-space it wrote (``ecalib_r``, ``sign_iters`` as in ``submit``)."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit_raw after close()")
-        return self._submit(_RawSource(self, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask), tag)
+        return self._submit(_RawSource(self, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask,
+                                       ecalib_r, sign_iters), tag)
 
     @property
     def set_builds(self) -> int:
@@ -467,11 +529,11 @@ class SlicePipeline:
             h = SliceHandle(step.index, step.index if tag is None else tag, step.slot, step.parity, ev_done)
             try:
                 keep = self._copy_in(src, key, wait_done=step.copy_after is not None)
-                outs = self._launch(key, src)
+                outs, resid = self._launch(key, src)
             except Exception:
-                self._recs[step.index] = [h, None, None]
+                self._recs[step.index] = [h, None, None, None]
                 raise
-            self._recs[step.index] = [h, outs, keep]
+            self._recs[step.index] = [h, outs, keep, resid]
             return h
 
     def results(self, block: bool = False):
@@ -489,9 +551,13 @@ class SlicePipeline:
                     return
                 self._sched.retire_oldest()
                 continue
-            h, outs, _ = self._recs.pop(k)
+            h, outs, _, resid = self._recs.pop(k)
             if outs is None:
                 continue                  # a submit that raised: nothing was launched for it
+            if resid is not None and not bool((resid <= ESPIRIT_RESIDUAL_MAX).all()):       # pinned host memory, the slice is done
+                raise CineHipError(f"SlicePipeline: slice {h.tag!r}: the in-flight ESPIRiT calibration did not converge (max |X^2 - I| = "
+                                   f"{float(resid.max()):.3e} > {ESPIRIT_RESIDUAL_MAX:g}): an eigenvalue of the calibration Gram matrix "
+                                   "sits at the threshold; raise sign_iters")
             if self.out == "device":
                 cur = torch.cuda.current_stream(self.device)
                 for o in outs:
@@ -557,6 +623,14 @@ class SlicePipeline:
         if r is not None:
             with torch.no_grad():
                 frontend.prepare_masked_slice(b["front"], b["mask"], r.crop, r.n, r.filter, r.scaling, None, r.apply_mask, out=b["mk"])
+        e = self._set.espirit
+        if e is not None:
+            with torch.no_grad():
+                for i in range(b["mk"].shape[0]):
+                    maps, _, resid = frontend.espirit_maps(frontend.time_average(b["mk"][i]), r=e[1], k=e[2], thresh=e[3], crop=e[4],
+                                                           method="sign", sign_iters=e[5], return_residual=True)
+                    b["sens"][i, 0].copy_(maps)
+                    b["resid"][i:i + 1].copy_(resid)
         return self._run(b)
 
     def _raw_memory(self, nbytes: int) -> None:
@@ -593,6 +667,7 @@ class SlicePipeline:
             if src.raw is not None:
                 self._raw_memory(src.raw_nbytes)
                 st.raw, st.raw_bytes = _settings_only(src), src.raw_nbytes     # the settings, not the first slice's data
+            st.espirit = src.espirit
             for i in range(S):
                 for p in (0, 1):
                     st.bufs[(i, p)] = src.alloc(self)
@@ -605,7 +680,7 @@ class SlicePipeline:
                 for key, b in st.bufs.items():
                     if key != (0, 0):
                         for name in src.input_names:
-                            if b[name] is not None:
+                            if b[name] is not None and not (name == "sens" and src.espirit is not None):
                                 b[name].copy_(b0[name])
             self.copy_stream.synchronize()
             if self.graphs:
@@ -710,5 +785,8 @@ class SlicePipeline:
                     raise CineHipError(f"SlicePipeline: eager forward failed: {type(e).__name__}: {e}") from e
                 if self.out == "host":
                     outs = tuple(torch.empty(o.shape, dtype=o.dtype, pin_memory=True).copy_(o, non_blocking=True) for o in outs)
+            resid = None
+            if st.espirit is not None:          # with the outputs, on the slot's stream: read by results() once the slice is done
+                resid = torch.empty(st.bufs[key]["resid"].shape, dtype=torch.float64, pin_memory=True).copy_(st.bufs[key]["resid"], non_blocking=True)
             st.done[key].record(s)
-        return outs
+        return outs, resid

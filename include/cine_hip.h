@@ -587,6 +587,30 @@ int cine_combine_target(const float* img, const float* sens, float* out, int t, 
  * maps (c, npix, 2) unit norm with coil 0 real and non-negative, zero where the eigenvalue < crop; lam (npix). */
 int cine_espirit_lag_kernels(const float* proj, float* kpad, int c, int kk, int ny, int nx, void* stream);
 int cine_espirit_eig(const float* m, float* maps, float* lam, int c, long npix, int iters, float crop, void* stream);
+/* The dense steps of that calibration without an eigensolver: a fixed launch sequence, no host read, capturable by a hipGraph.
+ * cine_espirit_gram: kavg (c, ny, nx) complex64 -> gram (n, n) complex128 row-major, n = kk kk c, the Gram matrix A^H A of the kk x kk
+ * patch matrix A of the central min(r, ny) x min(r, nx) block (origin ny / 2 - ry / 2, nx / 2 - rx / 2; columns ordered (py, px, coil)).
+ * Exact float32 products added in float64 in patch order: the full matrix, exactly Hermitian, bit-identical from call to call.  Any
+ * r >= 1; the block must hold one kernel (else CINE_EINVAL); c <= 32 and n <= 1152 (else CINE_EUNSUPPORTED, the limit is in the message);
+ * ws_bytes >= cine_espirit_gram_ws_bytes() (0 for shapes it refuses), gram and ws 16-byte aligned.
+ * cine_zgemm_f64: out = alpha a b + beta d for n x n row-major complex128 matrices (double pairs) on v_mfma_f64_16x16x4_f64, four real
+ * MFMAs per complex product, k ascending: deterministic.  Any 1 <= n <= 1152 (ragged tiles are handled inside); d is not read when
+ * beta == 0 (it may be NULL); out may be d, not a or b; 16-byte aligned.
+ * cine_espirit_projector: proj_f32 (n, n) complex64 = 1/2 (I + sign(gram - thresh^2 lam I)), the projector onto the eigenvectors of
+ * the Hermitian gram with eigenvalue >= thresh^2 lam_max, which is what cine_espirit_lag_kernels takes.  lam_dev: the largest eigenvalue
+ * (8 squarings of gram, renormalised by the Frobenius norm after each, then the Rayleigh quotient of the row sums).  The sign: `iters`
+ * Newton-Schulz steps X <- 1.5 X - 0.5 X X^2 from X_0 = (gram - thresh^2 lam I) / (1.0001 lam), two GEMMs each.  resid_dev:
+ * max |X^2 - I| of the X handed out, from one more GEMM behind the last step (NaN if the iteration left the finite numbers): above
+ * 1e-6 an eigenvalue sits at the threshold and `iters` is too small.  iters >= 1, thresh > 0, non-null distinct pointers (else
+ * CINE_EINVAL); n <= 1152 (else CINE_EUNSUPPORTED); ws_bytes >= cine_espirit_projector_ws_bytes(n) (else CINE_EWORKSPACE).
+ * All three: every argument is checked before the first launch; no allocation, no synchronisation, no atomics. */
+size_t cine_espirit_gram_ws_bytes(int c, int ny, int nx, int r, int kk);
+int cine_espirit_gram(const float* kavg, double* gram, void* ws, size_t ws_bytes, int c, int ny, int nx, int r, int kk, void* stream);
+int cine_zgemm_f64(const double* a, const double* b, const double* d, double* out, int n, double alpha_re, double alpha_im,
+                   double beta_re, double beta_im, void* stream);
+size_t cine_espirit_projector_ws_bytes(int n);
+int cine_espirit_projector(const double* gram, int n, double thresh, int iters, float* proj_f32, double* lam_dev, double* resid_dev,
+                           void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * small element-wise helpers                   reference: reconstruction/utils/math.py
