@@ -1156,7 +1156,7 @@ class ConjGradFn(Function):
     def forward(ctx, x0, b, lam, mask, sens, iters):
         x0 = ops._dev(x0, "CG start value"); b = ops._dev(b, "CG right-hand side")
         dev = x0.device
-        if CG_SOLVER_IN_TRAINING and iters >= 1 and ops.is_row_mask(mask, sens.expand(-1, x0.shape[1], -1, -1, -1, -1)):
+        if CG_SOLVER_IN_TRAINING and iters >= 1 and ops.mask_layout(mask, sens, x0.shape[1]) == "row":
             # the whole solve in one C call (2 + 2 * iters launches), the directions and step sizes recorded by its own kernels
             x = x0.clone()
             rec = ops.conj_grad_rec(x, b, sens, mask, lam, iters)
@@ -1173,7 +1173,7 @@ class ConjGradFn(Function):
         pd = torch.empty(max(iters, 1), device=dev, dtype=torch.float32)
         ops.dot(r, r, out=rr[0:1])
         bsz, t = x0.shape[0], x0.shape[1]
-        fused = ops.is_row_mask(mask, sens.expand(-1, t, -1, -1, -1, -1)) and \
+        fused = ops.mask_layout(mask, sens, t) == "row" and \
             lib().cine_image_dc_ws_bytes(bsz, t, sens.shape[2], sens.shape[3], sens.shape[4]) > 0
         ps = []
         for k in range(iters):

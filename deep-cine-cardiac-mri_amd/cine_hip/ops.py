@@ -454,16 +454,23 @@ def as_mask_u8(mask: torch.Tensor, kspace: Optional[torch.Tensor] = None) -> tor
     return mask
 
 
+def mask_layout(mask: torch.Tensor, like: torch.Tensor, t: Optional[int] = None) -> Optional[str]:
+    """"row" for the reference's mask layout (b, t, 1, h, 1, 1) (data/transforms.py:341-343), "general" for a mask that varies along w,
+    (b, t, 1, h, w, 1) with w > 1 -- the two layouts ``as_mask_u8(mask, kspace)`` returns -- and None for any other.  ``like`` gives the
+    shape: the k-space (b, t, c, h, w, 2), or the maps (b, 1, c, h, w, 2) together with ``t``."""
+    b, h, w = like.shape[0], like.shape[3], like.shape[4]
+    want = (b, like.shape[1] if t is None else t, 1, h)
+    if mask.dim() != 6 or tuple(mask.shape[:4]) != want:
+        return None
+    return "row" if tuple(mask.shape[4:]) == (1, 1) else "general" if w > 1 and tuple(mask.shape[4:]) == (w, 1) else None
+
+
 def is_row_mask(mask: torch.Tensor, kspace: torch.Tensor) -> bool:
-    """True for the reference's mask layout (b, t, 1, h, 1, 1) (data/transforms.py:341-343)."""
-    b, t, _, h, _, _ = kspace.shape
-    return mask.dim() == 6 and tuple(mask.shape) == (b, t, 1, h, 1, 1)
+    return mask_layout(mask, kspace) == "row"
 
 
 def is_general_mask(mask: torch.Tensor, kspace: torch.Tensor) -> bool:
-    """True for a mask that varies along w: (b, t, 1, h, w, 1) (what ``as_mask_u8(mask, kspace)`` returns for one)."""
-    b, t, _, h, w, _ = kspace.shape
-    return mask.dim() == 6 and w > 1 and tuple(mask.shape) == (b, t, 1, h, w, 1)
+    return mask_layout(mask, kspace) == "general"
 
 
 GENERAL_MASK_FUSED = _os.environ.get("CINE_GENERAL_MASK_FUSED", "1") == "1"    # A/B switch: False = the literal coil-wise k-space chain for masks that vary along w
@@ -598,10 +605,10 @@ def h_operator(x: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_r
     """CineNet's H = A^H M A + softplus(lambda) I (reference cinenet.py:121-133) for either mask layout: the one-kernel image-space
     operator for a (b, t, 1, h, 1, 1) row mask, its two-pass form for a mask that varies along w (``GENERAL_MASK_FUSED`` off or
     ``literal``, the training form: the literal expand -> mask -> reduce chain)."""
-    full = sens.expand(-1, x.shape[1], -1, -1, -1, -1)
-    if is_row_mask(mask, full):
+    layout = mask_layout(mask, sens, x.shape[1])
+    if layout == "row":
         return normal_op(x, sens, mask, lambda_reg, sens_tiled)
-    if is_general_mask(mask, full):
+    if layout == "general":
         if GENERAL_MASK_FUSED and not literal:
             return normal_op(x, sens, mask, lambda_reg)
         k = sens_expand_dc(x, sens)

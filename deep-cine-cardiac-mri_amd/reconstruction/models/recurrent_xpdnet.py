@@ -4,6 +4,7 @@ from torch import nn
 
 from cine_hip import autograd as ag
 from cine_hip import ops
+from cine_hip.dc import Acquisition
 from .denoisers.kspace_net import KSpaceCNN
 from .recurrent_common import BCRNNlayer, CRNNBody, CRNNcell  # noqa: F401
 from .xpdnet import BackwardOperator, ForwardOperator, SensitivityModel
@@ -39,81 +40,38 @@ class XPDNet_RNN(CRNNBody):
 
     def _forward_train(self, ref_kspace, mask, acs):
         """The chain of ``_forward_infer`` as an autograd graph: sensitivity network, K step + masked backward operator (image space for the
-        primal-only model; forward / k-space net / backward Functions with the dual buffer), CRNN body on the buffer planes."""
-        n, nd = self.i_buffer_size, self.k_buffer_size
+        primal-only model; forward / k-space net / backward Functions with the dual buffer: cine_hip/dc.py), CRNN body on the buffer planes."""
+        n = self.i_buffer_size
         b, t, _, h, w, _ = ref_kspace.shape
-        general = ops.is_general_mask(mask, ref_kspace)          # varies along w: the literal k-space chain
-        if b != 1 or not (general or ops.is_row_mask(mask, ref_kspace)):
+        if b != 1:
             raise NotImplementedError("training through the HIP path: batch 1")
-        mf = mask.to(ref_kspace.dtype) if general else None
-        pick = lambda buf, k: torch.stack((buf[..., 0], buf[..., k]), dim=-1)
-        sens_maps = self.sens_net(ref_kspace, mask, acs)
-        image_buffer = ag.CoilReduceFn.apply(ref_kspace, sens_maps, None).repeat_interleave(n, dim=-1)     # (1, t, 1, h, w, 2n)
-        if self.k_buffer_mode:
-            kbuf = ref_kspace.repeat_interleave(nd, dim=-1)
-        elif not general:
-            zf = ag.CoilReduceFn.apply(ref_kspace, sens_maps, mask)
+        pick = lambda buf: torch.stack((buf[..., 0], buf[..., n]), dim=-1)
+        acq = Acquisition(ref_kspace, mask, self.sens_net(ref_kspace, mask, acs), train=True)
+        image_buffer = acq.image().repeat_interleave(n, dim=-1)                                            # (1, t, 1, h, w, 2n)
+        kbuf = acq.k_buffer(self.k_buffer_size) if self.k_buffer_mode else None
         state = self.zero_state(t, b, h, w, image_buffer)
         for i in range(self.num_cascades):
-            x0 = pick(image_buffer, n)
-            if self.k_buffer_mode:
-                fwd = ag.SensExpandFn.apply(x0, sens_maps, None) * mf if general else ag.SensExpandFn.apply(x0, sens_maps, mask)
-                cat_k = torch.cat([kbuf[..., :nd], fwd[..., :1], ref_kspace[..., :1], kbuf[..., nd:], fwd[..., 1:], ref_kspace[..., 1:]], dim=-1)
-                kbuf = self.kspace_net[i](cat_k)
-                if general:
-                    bwd = ag.SensReduceFn.apply((pick(kbuf, nd) * mf).contiguous(), sens_maps, None)
-                else:
-                    bwd = ag.SensReduceFn.apply(pick(kbuf, nd).contiguous(), sens_maps, mask)
-            elif general:
-                bwd = ag.masked_residual_backward(x0, sens_maps, ref_kspace, mask)
-            else:
-                bwd = ag.ImageDcFixedFn.apply(x0, sens_maps, zf, mask, 1.0, 0.0, -1.0)
+            bwd, kbuf = acq.k_step(pick(image_buffer), kbuf, self.kspace_net[i])
             cat = torch.cat([image_buffer[..., :n], bwd[..., :1], image_buffer[..., n:], bwd[..., 1:]], dim=-1)
             planes = cat.view(t, h, w, 2 * (n + 1)).permute(0, 3, 1, 2).contiguous()                       # (t, 2(n+1), h, w)
             out, state = self.body_train(planes.view(t, 1, 2 * (n + 1), h, w), state, torch.cat([planes[:, :n], planes[:, n + 1:2 * n + 1]], dim=1))
             image_buffer = out.permute(0, 2, 3, 1).reshape(1, t, 1, h, w, 2 * n)
-        return ag.AbsFn.apply(pick(image_buffer, n).squeeze(2))
+        return ag.AbsFn.apply(pick(image_buffer).squeeze(2))
 
     def _forward_infer(self, ref_kspace, mask, acs):
         n = self.i_buffer_size
         b, t, _, h, w, _ = ref_kspace.shape
         if b != 1:
             raise NotImplementedError("the CRNN models assume batch 1, like the reference")
-        sens_maps = self.sens_net(ref_kspace, mask, acs)
-        image_buffer = ops.repeat_complex(ops.sens_reduce(ref_kspace, sens_maps), n)       # (1, t, 1, h, w, 2n)
-        rowmask = ops.is_row_mask(mask, ref_kspace) and not self.k_buffer_mode
-        general = ops.is_general_mask(mask, ref_kspace)          # varies along w (reference recurrent_xpdnet.py multiplies by any broadcastable mask)
-        gfused = general and ops.GENERAL_MASK_FUSED
-        if gfused and not self.k_buffer_mode:     # A^H m (m A x0 - k_ref) = A^H m A x0 - zf: the image-space operator with both line passes (cine_image_dc_general)
-            zf = ops.sens_reduce(ops.apply_mask(ref_kspace, mask), sens_maps, destroy_input=True)
-        hyb = None if (rowmask or general) else torch.empty_like(ref_kspace)
-        if rowmask:
-            zf = ops.hybrid_reduce(ops.kspace_to_hybrid(ref_kspace, mask=mask), sens_maps)
+        acq = Acquisition(ref_kspace, mask, self.sens_net(ref_kspace, mask, acs))
+        image_buffer = ops.repeat_complex(acq.image(), n)                                  # (1, t, 1, h, w, 2n)
         state = self.zero_state(t, b, h, w, image_buffer)
         keep = self.__dict__.get("_keep_idx")                                              # channels [:n] and [n+1:-1], as a device index made
         if keep is None or keep.device != ref_kspace.device:                               # once (a list index is a host copy: not capturable)
             keep = self.__dict__["_keep_idx"] = torch.tensor([i for i in range(2 * (n + 1)) if i not in (n, 2 * n + 1)], device=ref_kspace.device)
-        nd = self.k_buffer_size
-        kbuf = ops.repeat_complex(ref_kspace, nd) if self.k_buffer_mode else None
-        tiled = ops.sens_tile_pack(sens_maps) if rowmask else None
+        kbuf = acq.k_buffer(self.k_buffer_size) if self.k_buffer_mode else None            # dual buffer + KSpaceCNN
         for i in range(self.num_cascades):
-            x0 = ops.extract_complex(image_buffer, 0, n)
-            if self.k_buffer_mode:                                                          # dual buffer + KSpaceCNN
-                fwd = (ops.apply_mask(ops.sens_expand_dc(x0, sens_maps), mask) if gfused else ops.sens_expand_dc(x0, sens_maps) * mask + 0.0) if general else ops.sens_expand_dc(x0, sens_maps, None, mask, None, hard_mask=True)
-                cat_k = torch.cat([kbuf[..., :nd], fwd[..., :1], ref_kspace[..., :1],
-                                   kbuf[..., nd:], fwd[..., 1:], ref_kspace[..., 1:]], dim=-1)
-                kbuf = self.kspace_net[i](cat_k).contiguous()
-                k0 = ops.extract_complex(kbuf, 0, nd)
-                bwd = ops.sens_reduce(ops.apply_mask(k0, mask, out=k0) if gfused else k0 * mask + 0.0, sens_maps)
-            elif rowmask:
-                bwd = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0), sens_tiled=tiled)      # A^H M (A x0 - k_ref) (:110-163)
-            elif gfused:
-                bwd = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0))
-            elif general:
-                bwd = ops.masked_residual_backward(x0, sens_maps, ref_kspace, mask)
-            else:
-                ops.expand_resid_hybrid(x0, sens_maps, ref_kspace, mask, out=hyb)           # K step (:110-140)
-                bwd = ops.hybrid_reduce(hyb, sens_maps)                                     # masked backward op (:142-163)
+            bwd, kbuf = acq.k_step(ops.extract_complex(image_buffer, 0, n), kbuf, self.kspace_net[i])      # (:110-163)
             cat = torch.cat([image_buffer[..., :n], bwd[..., :1], image_buffer[..., n:], bwd[..., 1:]], dim=-1)
             planes = ops.chanlast_to_planes(cat.view(t, h, w, 2 * (n + 1)))                 # (t, 2(n+1), h, w)
             out, state = self.body(planes.view(t, 1, 2 * (n + 1), h, w), state, planes.index_select(1, keep))

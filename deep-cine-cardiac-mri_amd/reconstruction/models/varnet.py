@@ -29,6 +29,7 @@ from torch import nn
 
 from cine_hip import autograd as ag
 from cine_hip import ops
+from cine_hip.dc import Acquisition
 from .denoisers.norm_unet import NormUnet, NormUnet3D
 
 
@@ -116,13 +117,13 @@ class VarNetBlock(nn.Module):
             return self.model(image_combined.permute(0, 2, 1, 3, 4, 5)).permute(0, 2, 1, 3, 4, 5).contiguous()
         raise ValueError(f"unknown dynamic_type {self.dynamic_type!r}")
 
-    def forward(self, current_kspace, ref_kspace, mask, sens_maps, _destroy_current: bool = False):
-        image = ops.sens_reduce(current_kspace, sens_maps, destroy_input=_destroy_current)
-        model_out = self.regularise(image)
-        out = current_kspace if _destroy_current else None
-        if ops.is_general_mask(mask, ref_kspace):          # varies along w: the DC line of reference varnet.py:281-282 term by term
-            return ops.soft_dc_blend(ops.sens_expand_dc(model_out, sens_maps, out=out), ref_kspace, mask, self.lambda_reg.detach())
-        return ops.sens_expand_dc(model_out, sens_maps, ref_kspace, mask, self.lambda_reg, out=out)
+    def forward(self, current_kspace, ref_kspace, mask, sens_maps):
+        """One cascade on the coil-wise k-space, the reference's interface (varnet.py:280-282); ``VarNet.forward`` chains the cascades on
+        the coil-combined image instead (``Acquisition.soft_dc``)."""
+        model_out = self.regularise(ops.sens_reduce(current_kspace, sens_maps))
+        if mask.shape[-2] > 1:                             # varies along w: the DC line term by term
+            return ops.soft_dc_blend(ops.sens_expand_dc(model_out, sens_maps), ref_kspace, mask, self.lambda_reg.detach())
+        return ops.sens_expand_dc(model_out, sens_maps, ref_kspace, mask, self.lambda_reg)
 
 
 class VarNet(nn.Module):
@@ -154,58 +155,24 @@ class VarNet(nn.Module):
 
     def _forward_train(self, masked_kspace, mask, sens_maps, acs):
         """The image-space cascade chain of ``_forward_infer`` as an autograd graph (reference varnet.py:143-151)."""
-        if sens_maps is None:
-            sens_maps = self.sens_net(masked_kspace, mask, acs)
-        if not ops.is_row_mask(mask, masked_kspace):
-            # a mask that varies along w: the literal k-space chain of reference varnet.py:145-151 as an autograd graph -- coil
-            # operators through their HIP kernels and adjoints (SensReduceFn / SensExpandFn), the DC line in torch elementwise ops
-            kspace = masked_kspace
-            for cascade in self.cascades:
-                image = ag.SensReduceFn.apply(kspace, sens_maps, None)
-                model_term = ag.SensExpandFn.apply(cascade.regularise(image), sens_maps, None)
-                kspace = ops.soft_dc_blend(model_term, masked_kspace, mask, cascade.lambda_reg)
-            return ag.AbsFn.apply(ag.SensReduceFn.apply(kspace, sens_maps, None).squeeze(2))
-        image = ag.CoilReduceFn.apply(masked_kspace, sens_maps, None)          # first cascade's sens_reduce(masked_kspace)
-        if len(self.cascades) == 0:
-            return ag.AbsFn.apply(image.squeeze(2))
-        zf = ag.CoilReduceFn.apply(masked_kspace, sens_maps, mask)             # sens_reduce(mask * k_ref)
-        for cascade in self.cascades:
-            image = ag.ImageDcFn.apply(cascade.regularise(image), sens_maps, zf, mask, cascade.lambda_reg)
-        return ag.AbsFn.apply(image.squeeze(2))
+        return self._cascade_chain(masked_kspace, mask, sens_maps, acs, True)
 
     def _forward_infer(self, masked_kspace, mask, sens_maps, acs):
+        return self._cascade_chain(masked_kspace, mask, sens_maps, acs, False)
+
+    def _cascade_chain(self, masked_kspace, mask, sens_maps, acs, train):
+        # Cascade chain on the coil-combined image.  The k-space between two cascades (reference varnet.py:147-148) is consumed only by
+        # the next sens_reduce, so each step is reduce(DC(expand(x))); with a row mask the DC commutes with the transform along w and
+        #   reduce(DC(expand(x))) = sum_c conj(S_c) IFFT_h[(m ? 1/(1+v) : 1) FFT_h(S_c x)] + v/(1+v) reduce(m k_ref)
+        # (cine_image_dc): per cascade the FFT+DC step reads x, S and the constant zero-filled term instead of making three passes over
+        # the 72 MB coil-wise k-space.  Which kernels serve which mask layout: cine_hip/dc.py.
         if sens_maps is None:
             sens_maps = self.sens_net(masked_kspace, mask, acs)
-        if ops.general_mask_fused(mask, masked_kspace):
-            # a mask that varies along w: the same chain on the coil-combined image, each DC step with both line passes
-            # (cine_image_dc_general); k_ref is read here, once, for the zero-filled term
-            image = ops.sens_reduce(masked_kspace, sens_maps)
-            if len(self.cascades) == 0:
-                return ops.complex_abs(image.squeeze(2))
-            zf = ops.sens_reduce(ops.apply_mask(masked_kspace, mask), sens_maps, destroy_input=True)      # sens_reduce(mask * k_ref)
-            last = len(self.cascades) - 1
-            for i, cascade in enumerate(self.cascades):
-                image = ops.image_dc(cascade.regularise(image), sens_maps, zf, mask, cascade.lambda_reg, magnitude=(i == last))
-            return image
-        if not ops.is_row_mask(mask, masked_kspace):
-            # not the reference's (b, t, 1, h, 1, 1) row mask: the literal k-space chain of reference varnet.py:145-151
-            kspace = masked_kspace.clone()
-            for cascade in self.cascades:
-                kspace = cascade(kspace, masked_kspace, mask, sens_maps, _destroy_current=True)
-            return ops.sens_reduce(kspace, sens_maps, magnitude=True, destroy_input=True)
-        # Cascade chain on the coil-combined image.  The k-space between two cascades (reference varnet.py:147-148) is
-        # consumed only by the next sens_reduce, and with a row mask the DC commutes with the transform along w, so
-        #   reduce(DC(expand(x))) = sum_c conj(S_c) IFFT_h[(m ? 1/(1+v) : 1) FFT_h(S_c x)] + v/(1+v) reduce(m k_ref)
-        # (cine_image_dc): per cascade the FFT+DC step reads x, S and the constant zero-filled term instead of making
-        # three passes over the 72 MB coil-wise k-space.
-        hyb = ops.kspace_to_hybrid(masked_kspace)
-        image = ops.hybrid_reduce(hyb, sens_maps)                      # first cascade's sens_reduce(masked_kspace)
-        if len(self.cascades) == 0:
-            return ops.complex_abs(image.squeeze(2))
-        ops.kspace_to_hybrid(masked_kspace, out=hyb, mask=mask)
-        zf = ops.hybrid_reduce(hyb, sens_maps)                         # sens_reduce(mask * k_ref)
-        last = len(self.cascades) - 1
-        tiled = ops.sens_tile_pack(sens_maps)          # the maps in the order the DC kernel reads fastest: once per forward, for every cascade
+        acq = Acquisition(masked_kspace, mask, sens_maps, train)
+        image = acq.image()                                # first cascade's sens_reduce(masked_kspace)
+        last = None if train else len(self.cascades) - 1   # the last DC step of the inference chain writes the magnitude itself
         for i, cascade in enumerate(self.cascades):
-            image = ops.image_dc(cascade.regularise(image), sens_maps, zf, mask, cascade.lambda_reg, magnitude=(i == last), sens_tiled=tiled)
-        return image
+            image = acq.soft_dc(cascade.regularise(image), cascade.lambda_reg, magnitude=(i == last))
+        if train:
+            return ag.AbsFn.apply(image.squeeze(2))
+        return image if self.cascades else ops.complex_abs(image.squeeze(2))

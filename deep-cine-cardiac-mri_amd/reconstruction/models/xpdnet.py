@@ -19,6 +19,7 @@ from torch import nn
 
 from cine_hip import autograd as ag
 from cine_hip import ops
+from cine_hip.dc import Acquisition
 from .denoisers.unet import Unet
 from .denoisers.mwcnn import MWCNN
 from .denoisers.kspace_net import KSpaceCNN
@@ -171,71 +172,25 @@ class XPDNet(nn.Module):
         """The chain of ``_forward_infer`` (reference xpdnet.py:301-326) as an autograd graph.  Primal-only: the K step + masked backward
         operator is one image-space Function; with the KSpaceCNN dual net the k-space buffer is a learned quantity and the forward / backward
         operators are Functions with k-space gradients (FFT2 is unitary: each adjoint is the other operator)."""
-        n, nd = self.i_buffer_size, self.k_buffer_size
-        general = ops.is_general_mask(mask, masked_kspace)      # varies along w: the literal k-space chain (reference xpdnet.py:128-131 multiplies by any mask)
-        if self.dynamic_type not in ['XF', 'XT', '2D'] or not (general or ops.is_row_mask(mask, masked_kspace)):
+        if self.dynamic_type not in ['XF', 'XT', '2D']:
             raise NotImplementedError("training through the HIP path: dynamic_type XF / XT / 2D")
-        mf = mask.to(masked_kspace.dtype) if general else None
-        pick = lambda buf, k: torch.stack((buf[..., 0], buf[..., k]), dim=-1)
-        sens_maps = self.sens_net(masked_kspace, mask, acs)
-        image = ag.CoilReduceFn.apply(masked_kspace, sens_maps, None)           # unmasked backward op (:303)
-        image_buffer = image.repeat_interleave(n, dim=-1)                        # (:307): [re x n, im x n]
-        if self.k_buffer_mode:
-            kbuf = masked_kspace.repeat_interleave(nd, dim=-1)                   # (:306)
-        elif not general:
-            zf = ag.CoilReduceFn.apply(masked_kspace, sens_maps, mask)          # A^H M k_ref
+        n = self.i_buffer_size
+        pick = lambda buf: torch.stack((buf[..., 0], buf[..., n]), dim=-1)        # channel 0 of the buffer (:128)
+        acq = Acquisition(masked_kspace, mask, self.sens_net(masked_kspace, mask, acs), train=True)
+        image_buffer = acq.image().repeat_interleave(n, dim=-1)                   # unmasked backward op (:303), (:307): [re x n, im x n]
+        kbuf = acq.k_buffer(self.k_buffer_size) if self.k_buffer_mode else None   # (:306)
         for i_domain in range(1, len(self.domain_sequence), 2):
-            x0 = pick(image_buffer, n)                                           # channel 0 of the buffer (:128)
-            if self.k_buffer_mode:
-                fwd = ag.SensExpandFn.apply(x0, sens_maps, None) * mf if general else ag.SensExpandFn.apply(x0, sens_maps, mask)      # M A x0 (:385-403)
-                cat = torch.cat([kbuf[..., :nd], fwd[..., :1], masked_kspace[..., :1], kbuf[..., nd:], fwd[..., 1:], masked_kspace[..., 1:]], dim=-1)
-                kbuf = self.kspace_net[i_domain // 2](cat)
-                if general:
-                    backward_img = ag.SensReduceFn.apply((pick(kbuf, nd) * mf).contiguous(), sens_maps, None)
-                else:
-                    backward_img = ag.SensReduceFn.apply(pick(kbuf, nd).contiguous(), sens_maps, mask)  # masked backward op (:161-167)
-            elif general:
-                backward_img = ag.masked_residual_backward(x0, sens_maps, masked_kspace, mask)          # A^H m (m A x0 - k_ref), literally
-            else:
-                backward_img = ag.ImageDcFixedFn.apply(x0, sens_maps, zf, mask, 1.0, 0.0, -1.0)         # A^H M (A x0 - k_ref)
+            backward_img, kbuf = acq.k_step(pick(image_buffer), kbuf, self.kspace_net[i_domain // 2])
             image_buffer = self.cascades[i_domain].regularise(i_domain, image_buffer, backward_img)
-        return ag.AbsFn.apply(pick(image_buffer, n).squeeze(2))                   # (:321-326)
+        return ag.AbsFn.apply(pick(image_buffer).squeeze(2))                      # (:321-326)
 
     def _forward_infer(self, masked_kspace, mask, acs):
         n = self.i_buffer_size
-        sens_maps = self.sens_net(masked_kspace, mask, acs)
-        image = ops.sens_reduce(masked_kspace, sens_maps)                       # unmasked backward op (:303)
-        image_buffer = ops.repeat_complex(image, n)                             # (:307)
-        rowmask = ops.is_row_mask(mask, masked_kspace) and not self.k_buffer_mode
-        general = ops.is_general_mask(mask, masked_kspace)      # varies along w (reference xpdnet.py:128-131 multiplies by any broadcastable mask)
-        gfused = general and ops.GENERAL_MASK_FUSED
-        if gfused and not self.k_buffer_mode:     # A^H m (m A x0 - k_ref) = A^H m A x0 - zf: the image-space operator with both line passes (cine_image_dc_general)
-            zf = ops.sens_reduce(ops.apply_mask(masked_kspace, mask), sens_maps, destroy_input=True)
-        hyb = None if (rowmask or general) else torch.empty_like(masked_kspace)
-        if rowmask:     # A^H M k_ref, constant over the cascades: the K + backward step becomes A^H M A x0 - zf in one kernel
-            zf = ops.hybrid_reduce(ops.kspace_to_hybrid(masked_kspace, mask=mask), sens_maps)
-        nd = self.k_buffer_size
-        kbuf = ops.repeat_complex(masked_kspace, nd) if self.k_buffer_mode else None          # (:306)
-        tiled = ops.sens_tile_pack(sens_maps) if rowmask else None              # the maps as the DC kernel reads them fastest, once per forward
-        for i_domain in range(1, len(self.domain_sequence), 2):                 # each 'K' then 'I' pair (:310-319)
-            x0 = ops.extract_complex(image_buffer, 0, n)                        # channel 0 of the buffer (:128)
-            if self.k_buffer_mode:
-                # dual buffer: the k-space net needs the whole k-space, so it is materialised (:385-403)
-                fwd = (ops.apply_mask(ops.sens_expand_dc(x0, sens_maps), mask) if gfused else ops.sens_expand_dc(x0, sens_maps) * mask + 0.0) if general else ops.sens_expand_dc(x0, sens_maps, None, mask, None, hard_mask=True)
-                cat = torch.cat([kbuf[..., :nd], fwd[..., :1], masked_kspace[..., :1],
-                                 kbuf[..., nd:], fwd[..., 1:], masked_kspace[..., 1:]], dim=-1)
-                kbuf = self.kspace_net[i_domain // 2](cat).contiguous()
-                k0 = ops.extract_complex(kbuf, 0, nd)
-                k0 = ops.apply_mask(k0, mask, out=k0) if gfused else k0 * mask + 0.0      # masked backward op (:161-167)
-                backward_img = ops.sens_reduce(k0, sens_maps)
-            elif rowmask:
-                backward_img = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0), sens_tiled=tiled)   # A^H M (A x0 - k_ref)
-            elif gfused:
-                backward_img = ops.image_dc(x0, sens_maps, zf, mask, weights=(1.0, 0.0, -1.0))
-            elif general:
-                backward_img = ops.masked_residual_backward(x0, sens_maps, masked_kspace, mask)
-            else:
-                ops.expand_resid_hybrid(x0, sens_maps, masked_kspace, mask, out=hyb)    # K: M A x0 - k_ref
-                backward_img = ops.hybrid_reduce(hyb, sens_maps)                # I: masked backward op
+        acq = Acquisition(masked_kspace, mask, self.sens_net(masked_kspace, mask, acs))
+        image_buffer = ops.repeat_complex(acq.image(), n)                         # unmasked backward op (:303), (:307)
+        kbuf = acq.k_buffer(self.k_buffer_size) if self.k_buffer_mode else None   # (:306)
+        for i_domain in range(1, len(self.domain_sequence), 2):                   # each 'K' then 'I' pair (:310-319)
+            x0 = ops.extract_complex(image_buffer, 0, n)                          # channel 0 of the buffer (:128)
+            backward_img, kbuf = acq.k_step(x0, kbuf, self.kspace_net[i_domain // 2])
             image_buffer = self.cascades[i_domain].regularise(i_domain, image_buffer, backward_img)
         return ops.complex_abs(ops.extract_complex(image_buffer, 0, n).squeeze(2))      # (:321-326)

@@ -105,6 +105,47 @@ def test_the_switch_and_the_layout_predicates():
     assert ops.as_mask_u8(general, ks) is general
 
 
+def test_as_mask_u8_returns_the_row_layout_or_the_general_layout_and_nothing_else(monkeypatch):
+    """What lets the models' data consistency (cine_hip/dc.py) dispatch on two layouts only: for every mask that broadcasts as
+    (b|1, t|1, 1, h, w|1, 1), of every accepted dtype, the result is exactly (b, t, 1, h, 1, 1) or -- only with w > 1 -- (b, t, 1, h, w, 1);
+    any other shape raises."""
+    import itertools
+    from cine_hip import ops
+    from cine_hip.dc import Acquisition
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)      # (as_mask_u8 asks before it converts; the question needs a device)
+    for (b, t, h, w), dtype in itertools.product(((1, 3, 8, 6), (2, 3, 8, 6), (2, 1, 5, 1), (1, 1, 1, 1), (3, 2, 4, 2)),
+                                                 (torch.uint8, torch.bool, torch.int32, torch.int64, torch.float16, torch.float32, torch.float64)):
+        ks = torch.zeros(b, t, 2, h, w, 2)
+        for mb, mt, mw in itertools.product({1, b}, {1, t}, {1, w}):
+            g = torch.Generator().manual_seed(mb * 100 + mt * 10 + mw)
+            src = torch.rand(mb, mt, 1, h, mw, 1, generator=g) < 0.5
+            out = ops.as_mask_u8(src.to(dtype) * (3 if dtype not in (torch.bool, torch.uint8) else 1), ks)      # any non-zero value samples
+            assert out.dtype == torch.uint8 and out.is_contiguous() and torch.equal(out, src.expand(b, t, 1, h, mw, 1).to(torch.uint8))
+            row, general = ops.is_row_mask(out, ks), ops.is_general_mask(out, ks)
+            assert row != general, (tuple(src.shape), tuple(out.shape))
+            assert row == (mw == 1) and ops.mask_layout(out, ks) == ("row" if row else "general")
+            assert tuple(out.shape) == ((b, t, 1, h, 1, 1) if row else (b, t, 1, h, w, 1)) and (row or w > 1)
+            assert ops.mask_layout(out, ks[:, :1], t) == ops.mask_layout(out, ks)                     # the shape from the maps and t
+            acq = Acquisition(ks, out, ks[:, :1])
+            assert acq.row == row and acq.fused and not Acquisition(ks, out, ks[:, :1], train=True).fused
+    b, t, h, w = 2, 3, 8, 6
+    ks = torch.zeros(b, t, 2, h, w, 2)
+    for shape in ((b, t, 1, h, w), (b, t, 1, h, w, 2), (b, t, 2, h, w, 1), (b, t, 1, h - 1, w, 1), (b, t, 1, 1, w, 1), (b, t, 1, h, w - 1, 1),
+                  (b, t, 1, h, 2, 1), (3, t, 1, h, w, 1), (b, 2, 1, h, 1, 1), (b, t, h, 1, 1, 1), (h,), (b, t, 1, h, 1, 1, 1)):
+        with pytest.raises(ValueError, match="does not broadcast"):
+            ops.as_mask_u8(torch.zeros(shape, dtype=torch.uint8), ks)
+        assert ops.mask_layout(torch.zeros(shape, dtype=torch.uint8), ks) is None
+    with pytest.raises(ValueError, match="neither layout"):
+        Acquisition(ks, torch.zeros(1, t, 1, h, 1, 1, dtype=torch.uint8), ks[:, :1])               # not passed through as_mask_u8
+    old = ops.GENERAL_MASK_FUSED
+    try:        # read when the object is built, not when the module is imported
+        ops.GENERAL_MASK_FUSED = False
+        general = torch.zeros(b, t, 1, h, w, 1, dtype=torch.uint8)
+        assert not Acquisition(ks, general, ks[:, :1]).fused and Acquisition(ks, torch.zeros(b, t, 1, h, 1, 1, dtype=torch.uint8), ks[:, :1]).fused
+    finally:
+        ops.GENERAL_MASK_FUSED = old
+
+
 class _Stand:
     """The attributes of a SlicePipeline that input validation reads."""
 
