@@ -384,7 +384,7 @@ extern "C" int cine_xfyf_pack(const float* img, float* planes_xf, float* planes_
                               float* mean_img, int b, int t, int h, int w, int xf, int norm, void* ws, size_t ws_bytes, void* stream) {
     CINE_REQUIRE(img && planes_xf && planes_yf && mean_img && ws && (!norm || (stats_xf && stats_yf)), CINE_EINVAL,
                  "cine_xfyf_pack: null pointer");
-    CINE_REQUIRE(b > 0 && t > 1 && h > 0 && w > 0, CINE_EINVAL, "cine_xfyf_pack: bad sizes");
+    CINE_REQUIRE(b > 0 && b <= 65535 && t > 1 && h > 0 && w > 0, CINE_EINVAL, "cine_xfyf_pack: bad sizes");   // b rides on grid.y
     CINE_REQUIRE(t <= 64, CINE_EUNSUPPORTED, "cine_xfyf_pack: %d frames > 64", t);
     CINE_REQUIRE(ws_bytes >= cine_xfyf_ws_bytes(b, t, h, w), CINE_EWORKSPACE, "cine_xfyf_pack: workspace too small");
     hipStream_t st = as_stream(stream);
@@ -858,6 +858,7 @@ __global__ void normunet3d_unpack_kernel(const float* planes, const float* stats
 extern "C" int cine_normunet3d_pack(const float* x, float* planes, float* stats, int n, int t, int h, int w, int norm, void* stream) {
     CINE_REQUIRE(x && planes && (stats || !norm), CINE_EINVAL, "cine_normunet3d_pack: null pointer");
     CINE_REQUIRE(n > 0 && t > 0 && h > 0 && w > 0 && (long)t * h * w > 1, CINE_EINVAL, "cine_normunet3d_pack: bad sizes");
+    CINE_REQUIRE(norm || n <= 65535, CINE_EINVAL, "cine_normunet3d_pack: bad sizes (the plain repack carries n on grid.y)");
     int tp, pt, hp, ph, wp, pw;
     pad_split(t, tp, pt, norm != 0); pad_split(h, hp, ph, norm != 0); pad_split(w, wp, pw, norm != 0);
     ProfScope prof(F_PACK, as_stream(stream));

@@ -244,7 +244,7 @@ int cine_normunet_unpack(const float* planes, const float* stats, float* y, int 
  * group norm, pad.  img (b, t, h, w, 2).
  *   planes_xf (b*h, 2, pad16(w), pad16(t)), planes_yf (b*w, 2, pad16(h), pad16(t)),
  *   stats_xf (b*h, 2, 2), stats_yf (b*w, 2, 2), mean_img (b, h, w, 2).
- * ws: cine_xfyf_ws_bytes(b, t, h, w). */
+ * ws: cine_xfyf_ws_bytes(b, t, h, w).  2 <= t <= 64 (more frames: CINE_EUNSUPPORTED), b <= 65535; cine_xfyf_unpack also h <= 65535. */
 size_t cine_xfyf_ws_bytes(int b, int t, int h, int w);
 int cine_xfyf_pack(const float* img, float* planes_xf, float* planes_yf, float* stats_xf, float* stats_yf,
                    float* mean_img, int b, int t, int h, int w, int xf, int norm, void* ws, size_t ws_bytes, void* stream);
@@ -448,12 +448,18 @@ int cine_mwcnn_forward2(const float* x, float* y, const void* const* weights, co
 int cine_mwcnn_pad(int size, int n_scales, int* left, int* right);
 /* I-step front half (:424-471): buf (b,t,1,h,w,2n) + backward-op image `extra` (b,t,1,h,w,2) as complex
  * channel n, temporal mean subtract, (xf) ifftshift(fft(fftshift(.))) over t, rotation into
- * planes_xf (b*h, 2(n+1), pad(w), pad(t)) / planes_yf (b*w, 2(n+1), pad(h), pad(t)); mean (b,h,w,n+1,2). */
+ * planes_xf (b*h, 2(n+1), pad(w), pad(t)) / planes_yf (b*w, 2(n+1), pad(h), pad(t)); mean (b,h,w,n+1,2).
+ * Limits: 2 <= t <= 64, 1 <= n_primal <= 15, b <= 65535, and one tile of 32 pixels x (n_primal + 1) channels x t frames plus the t
+ * twiddles must fit 64 KiB of LDS: (32 t (n_primal + 1) + t) * 8 bytes <= 65536, i.e. t (n_primal + 1) <= 254 (255 with t <= 32; the
+ * largest tile is t = 17, n_primal = 14 at 65 416 bytes), else CINE_EUNSUPPORTED.  The adjoint cine_xpd_pack_bwd keeps two such tiles and
+ * accepts HALF of that: t (n_primal + 1) <= 127 -- a shape that runs in inference can be refused in training. */
 size_t cine_xpd_ws_bytes(int b, int t, int h, int w, int n_primal);
 int cine_xpd_pack(const float* buf, const float* extra, float* planes_xf, float* planes_yf, float* mean,
                   int b, int t, int h, int w, int n_primal, int n_scales, int xf, void* ws, size_t ws_bytes, void* stream);
 /* I-step back half (:485-509) on the MWCNN outputs (2n channels): unpad, un-rotate, average, inverse
- * temporal transform, add the temporal mean of channels 0..n-1.  out (b,t,1,h,w,2n). */
+ * temporal transform, add the temporal mean of channels 0..n-1.  out (b,t,1,h,w,2n).
+ * Limits: 2 <= t <= 64, b, h <= 65535, (32 t n_primal + t) * 8 bytes <= 65536 (t n_primal <= 254, 255 with t <= 32), else
+ * CINE_EUNSUPPORTED; cine_xpd_unpack_bwd has the same tile and also asks for n_primal <= 15. */
 int cine_xpd_unpack(const float* planes_xf, const float* planes_yf, const float* mean, float* out,
                     int b, int t, int h, int w, int n_primal, int n_scales, int xf, void* stream);
 /* 2-D mode repacks (:442-444): channel-last (n, h, w, c) <-> zero-padded planes (n, c, pad(h), pad(w)). */
@@ -825,7 +831,10 @@ int cine_in_lrelu_bwd(const float* r, const float* part, int np, const float* g,
 /* Adjoints of cine_xpd_unpack / cine_xpd_pack (models/xpdnet.py:424-509): gout (b, t, 1, h, w, 2n) -> the gradients of the two MWCNNs' output
  * planes (2n channels, zero on the pad frames) and gmean (b, h, w, n + 1, 2) (the temporal mean of channels < n is added back, :504-509); then
  * from the gradients of the MWCNNs' input planes (2 (n + 1) channels) -> gbuf (b, t, 1, h, w, 2n) and gextra (b, t, 1, h, w, 2) (the
- * backward-operator image).  XPDNet's temporal transforms (:466, :500) are unitary: each adjoint is the inverse with the same shifts. */
+ * backward-operator image).  XPDNet's temporal transforms (:466, :500) are unitary: each adjoint is the inverse with the same shifts.
+ * LDS limits (CINE_EUNSUPPORTED above them): cine_xpd_unpack_bwd as cine_xpd_unpack, (32 t n_primal + t) * 8 <= 65536 bytes;
+ * cine_xpd_pack_bwd (64 t (n_primal + 1) + t) * 8 <= 65536 bytes, i.e. t (n_primal + 1) <= 127, half of what cine_xpd_pack accepts (the
+ * largest tile is t = 9, n_primal = 13 at 64 584 bytes). */
 int cine_xpd_unpack_bwd(const float* gout, float* gplanes_xf, float* gplanes_yf, float* gmean,
                         int b, int t, int h, int w, int n_primal, int n_scales, int xf, void* stream);
 int cine_xpd_pack_bwd(const float* gplanes_xf, const float* gplanes_yf, const float* gmean, float* gbuf, float* gextra,
