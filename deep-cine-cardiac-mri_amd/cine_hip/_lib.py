@@ -206,6 +206,8 @@ _SIGS = {
     "cine_xfyf_unpack_bwd": (c_int, [P] * 10 + [c_int] * 5 + [P, c_size_t, P]),
     "cine_xfyf_pack_bwd": (c_int, [P] * 10 + [c_int] * 5 + [P, c_size_t, P]),
     "cine_image_dc_sens_grad": (c_int, [P, P, P, P, P, c_float, c_float, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "cine_image_dc_general_sens_grad_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "cine_image_dc_general_sens_grad": (c_int, [P, P, P, P, P, c_float, c_float, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "cine_coil_accum": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_rss_normalise_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "cine_complex_abs_bwd": (c_int, [P, P, P, c_long, P]),

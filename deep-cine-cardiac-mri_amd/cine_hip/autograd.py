@@ -348,10 +348,31 @@ def mwcnn(x: torch.Tensor, w, w2=None, split: int = 0) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ coil operators
+def _image_dc_sens_grad(m, gout, sens, mask, lam, w1, w0):
+    """The maps' gradient of ``ops.image_dc`` (b, 1, c, h, w, 2): per frame conj(g) T(S_c m) + T(S_c g) conj(m), the frames added by
+    cine_coil_accum.  Row mask: cine_image_dc_sens_grad (one column pass); mask that varies along w: cine_image_dc_general_sens_grad, both
+    line passes through the scratch buffer ``ops.image_dc`` uses for such a mask."""
+    b, _, c, h, w, _ = sens.shape
+    t = m.shape[1]
+    sens = ops._dev(sens, "sens_maps")
+    part = torch.empty((b, t, c, h, w, 2), device=m.device, dtype=m.dtype)
+    if ops.mask_layout(mask, sens, t) == "general":
+        nbytes = lib().cine_image_dc_general_sens_grad_ws_bytes(b, t, c, h, w)
+        ws = ops._general_ws(nbytes, m.device)
+        check(lib().cine_image_dc_general_sens_grad(m.data_ptr(), gout.data_ptr(), sens.data_ptr(), mask.data_ptr(), _p(lam), w1, w0,
+                                                    part.data_ptr(), b, t, c, h, w, ws.data_ptr(), nbytes, _stream()),
+              "cine_image_dc_general_sens_grad")
+    else:
+        check(lib().cine_image_dc_sens_grad(m.data_ptr(), gout.data_ptr(), sens.data_ptr(), mask.data_ptr(), _p(lam), w1, w0,
+                                            part.data_ptr(), b, t, c, h, w, _stream()), "cine_image_dc_sens_grad")
+    return coil_accum(None, part)
+
+
 @_masked
 class ImageDcFn(Function):
     """cine_image_dc with the soft-DC weights of softplus(lambda) (varnet.py:181-194, 281-282):
-    out = sum_c conj(S_c) T(S_c m) + v / (1 + v) zf,  T = IFFT_h [mask ? 1 / (1 + v) : 1] FFT_h."""
+    out = sum_c conj(S_c) T(S_c m) + v / (1 + v) zf,  T = IFFT_h [mask ? 1 / (1 + v) : 1] FFT_h for a row mask,
+    IFFT2 [mask(ky, kx) ? 1 / (1 + v) : 1] FFT2 for one that varies along w (``ops.image_dc`` dispatches on the layout)."""
 
     @staticmethod
     def forward(ctx, m, sens, zf, mask, lam):
@@ -368,13 +389,7 @@ class ImageDcFn(Function):
         t = m.shape[1]
         need = ctx.needs_input_grad
         gm = ops.image_dc(gout, sens, None, mask, lam).view(m.shape) if need[0] else None      # T is Hermitian
-        gs = None
-        if need[1]:
-            part = torch.empty((b, t, c, h, w, 2), device=m.device, dtype=m.dtype)
-            check(lib().cine_image_dc_sens_grad(m.data_ptr(), gout.data_ptr(), ops._dev(sens, "sens_maps").data_ptr(), mask.data_ptr(),
-                                                lam.detach().data_ptr(), 0.0, 0.0, part.data_ptr(), b, t, c, h, w, _stream()),
-                  "cine_image_dc_sens_grad")
-            gs = coil_accum(None, part)
+        gs = _image_dc_sens_grad(m, gout, sens, mask, lam.detach(), 0.0, 0.0) if need[1] else None
         gzf = None
         if need[2]:
             gzf = torch.empty_like(zf)
@@ -394,7 +409,7 @@ class ImageDcFn(Function):
 @_masked
 class ImageDcFixedFn(Function):
     """cine_image_dc with fixed weights: sum_c conj(S_c) IFFT_h[(mask ? w1 : w0) FFT_h(S_c m)] + beta zf -- XPDNet's K step + masked backward
-    operator A^H M (A x - k_ref) is (1, 0, -1) (xpdnet.py:128-131, 161-167, 295-298)."""
+    operator A^H M (A x - k_ref) is (1, 0, -1) (xpdnet.py:128-131, 161-167, 295-298).  Either mask layout, as ImageDcFn."""
 
     @staticmethod
     def forward(ctx, m, sens, zf, mask, w1, w0, beta):
@@ -413,12 +428,7 @@ class ImageDcFixedFn(Function):
         t = m.shape[1]
         need = ctx.needs_input_grad
         gm = ops.image_dc(gout, sens, None, mask, None, weights=(w1, w0, 0.0)).view(m.shape) if need[0] else None
-        gs = None
-        if need[1]:
-            part = torch.empty((b, t, c, h, w, 2), device=m.device, dtype=m.dtype)
-            check(lib().cine_image_dc_sens_grad(m.data_ptr(), gout.data_ptr(), ops._dev(sens, "sens_maps").data_ptr(), mask.data_ptr(), None,
-                                                w1, w0, part.data_ptr(), b, t, c, h, w, _stream()), "cine_image_dc_sens_grad")
-            gs = coil_accum(None, part)
+        gs = _image_dc_sens_grad(m, gout, sens, mask, None, w1, w0) if need[1] else None
         gzf = (gout * beta) if need[2] else None
         return gm, gs, gzf, None, None, None, None
 
@@ -976,8 +986,10 @@ class CoilReduceFn(Function):
 
     @staticmethod
     def forward(ctx, kspace, sens, mask):
-        hyb = ops.kspace_to_hybrid(kspace, mask=mask)
-        out = ops.hybrid_reduce(hyb, sens)
+        if mask is not None and ops.is_general_mask(mask, kspace):          # the masked hybrid-space kernel skips ROWS: a mask plane is applied point by point
+            out = ops.sens_reduce(ops.apply_mask(kspace, mask), sens, destroy_input=True)
+        else:
+            out = ops.hybrid_reduce(ops.kspace_to_hybrid(kspace, mask=mask), sens)
         ctx.save_for_backward(kspace, mask if mask is not None else torch.empty(0))
         ctx.has_mask = mask is not None
         return out
@@ -1140,13 +1152,21 @@ class AxpbyLamFn(Function):
 CG_SOLVER_IN_TRAINING = __import__("os").environ.get("CINE_CG_SOLVER_TRAIN", "1") == "1"      # diagnostics (this binding): False = iterate cine_normal_op_cg_fused from Python
 
 
+def _cg_h(v, sens, mask, lam, literal):
+    """ConjGradFn's operator: ``ops.h_operator(..., literal=True)`` (cine_normal_op for a row mask, the literal chain for one that varies
+    along w), or, where forward chose the image-space operator for such a mask, ``ops.h_operator(..., literal=False)``'s branch called
+    directly (cine_normal_op_general), so that a switch flipped before backward cannot change the operator."""
+    return ops.h_operator(v, sens, mask, lam, literal=True) if literal else ops.normal_op(v, sens, mask, lam)
+
+
 @_masked
 class ConjGradFn(Function):
     """CineNetBlock.ConjGrad (cinenet.py:136-171): K iterations of conjugate gradients on H x = b, H = A^H M A + softplus(lambda) I,
     from the start value x0.  The reference takes alpha and beta out of the graph (``.item()``, :159-169), so the iteration it
     differentiates is LINEAR in (x0, b) with the recorded step sizes; H is self-adjoint, so the adjoint recurrence is K + 1 more
-    applications of the same operator (ops.h_operator: the image-space kernel cine_normal_op for row masks, the literal
-    expand -> mask -> reduce chain for masks that vary along w), run backwards:
+    applications of the same operator (ops.h_operator: the image-space kernel cine_normal_op for row masks; for masks that vary along w the
+    literal expand -> mask -> reduce chain, or with ops.GENERAL_MASK_FUSED and ops.GENERAL_MASK_FUSED_TRAIN cine_normal_op_general -- chosen
+    once in forward and kept on ctx, because backward runs on autograd's thread, possibly after the switches moved), run backwards:
         gp_k = beta_k gp_{k+1} + alpha_k gx - alpha_k H(gr_{k+1} + gp_{k+1}),   gr_k = gr_{k+1} + gp_{k+1}
         gb = gr_0 + gp_0,  gx0 = gx - H(gb),  d/d v = -sum_k alpha_k <gr_{k+1} + gp_{k+1}, p_k> - <gb, x0>.
     Forward: the inference path's fused iteration (cine_normal_op_pd + cine_cg_step_pd2, four launches) with p_k kept and the scalars
@@ -1156,7 +1176,9 @@ class ConjGradFn(Function):
     def forward(ctx, x0, b, lam, mask, sens, iters):
         x0 = ops._dev(x0, "CG start value"); b = ops._dev(b, "CG right-hand side")
         dev = x0.device
-        if CG_SOLVER_IN_TRAINING and iters >= 1 and ops.mask_layout(mask, sens, x0.shape[1]) == "row":
+        layout = ops.mask_layout(mask, sens, x0.shape[1])
+        literal = ctx.literal = not ops.general_mask_fused_train(mask, sens, x0.shape[1])
+        if CG_SOLVER_IN_TRAINING and iters >= 1 and layout == "row":
             # the whole solve in one C call (2 + 2 * iters launches), the directions and step sizes recorded by its own kernels
             x = x0.clone()
             rec = ops.conj_grad_rec(x, b, sens, mask, lam, iters)
@@ -1165,7 +1187,7 @@ class ConjGradFn(Function):
                 ctx.save_for_backward(x0, lam, mask, sens, rr, pd, *p_rec.unbind(0))
                 return x
         one = torch.ones(1, device=dev, dtype=torch.float32)
-        r = ops.axpby_dev(b, ops.h_operator(x0, sens, mask, lam, literal=True), num=one, sign=-1.0)
+        r = ops.axpby_dev(b, _cg_h(x0, sens, mask, lam, literal), num=one, sign=-1.0)
         p = r.clone()
         x = x0.clone()
         # the step sizes stay on the device: rr[k] = r_k . r_k, pd[k] = p_k . H p_k  (alpha_k = rr[k] / pd[k], beta_k = rr[k + 1] / rr[k])
@@ -1173,7 +1195,7 @@ class ConjGradFn(Function):
         pd = torch.empty(max(iters, 1), device=dev, dtype=torch.float32)
         ops.dot(r, r, out=rr[0:1])
         bsz, t = x0.shape[0], x0.shape[1]
-        fused = ops.mask_layout(mask, sens, t) == "row" and \
+        fused = layout == "row" and \
             lib().cine_image_dc_ws_bytes(bsz, t, sens.shape[2], sens.shape[3], sens.shape[4]) > 0
         ps = []
         for k in range(iters):
@@ -1181,7 +1203,7 @@ class ConjGradFn(Function):
             if fused:       # the inference path's four launches per iteration (operator with p.d partial sums, update, direction), p.d recorded
                 ops.normal_op_cg_step(x, r, p, sens, mask, lam, rr[k:k + 1], rr[k + 1:k + 2], pd_out=pd[k:k + 1])
                 continue
-            d = ops.h_operator(p, sens, mask, lam, literal=True)
+            d = _cg_h(p, sens, mask, lam, literal)
             ops.dot(p, d, out=pd[k:k + 1])
             x = ops.axpby_dev(x, p, num=rr[k:k + 1], den=pd[k:k + 1])                   # x + alpha p
             r = ops.axpby_dev(r, d, num=rr[k:k + 1], den=pd[k:k + 1], sign=-1.0)        # r - alpha d
@@ -1203,7 +1225,7 @@ class ConjGradFn(Function):
         q = torch.zeros_like(gx)                                      # q_k = gr_{k+1} + gp_{k+1}: the gradient reaching r_{k+1}
         gp = torch.zeros_like(gx)
         for k in reversed(range(K)):
-            hg = ops.h_operator(q, sens, mask, lam, literal=True)
+            hg = _cg_h(q, sens, mask, lam, ctx.literal)
             check(L.cine_cg_adjoint_step(gp.data_ptr(), q.data_ptr(), gx.data_ptr(), hg.data_ptr(), ps[k].data_ptr(), gx.numel(),
                                          rr[k:k + 1].data_ptr(), pd[k:k + 1].data_ptr(), rr[k + 1:k + 2].data_ptr(),
                                          part[k * nf:].data_ptr(), _stream()), "cine_cg_adjoint_step")
@@ -1212,7 +1234,7 @@ class ConjGradFn(Function):
         gx0 = None
         if need[0]:
             one = torch.ones(1, device=dev, dtype=torch.float32)
-            gx0 = ops.axpby_dev(gx, ops.h_operator(gb, sens, mask, lam, literal=True), num=one, sign=-1.0)
+            gx0 = ops.axpby_dev(gx, _cg_h(gb, sens, mask, lam, ctx.literal), num=one, sign=-1.0)
         glam = None
         if need[2]:
             gv = torch.empty(1, device=dev, dtype=torch.float32)

@@ -2,8 +2,9 @@
 
 ``Acquisition(ref_kspace, mask, sens_maps, train)`` is built once at the top of a model's forward, from the mask that ``ops.as_mask_u8``
 returned.  It decides there, once: the layout (row mask (b, t, 1, h, 1, 1), or general mask (b, t, 1, h, w, 1) that varies along w), whether
-the image-space operator applies (``fused``: always for a row mask; for a general one what ``ops.GENERAL_MASK_FUSED`` says at that moment),
-and whether the methods build an autograd graph (``train``).  What is constant over the cascades -- A^H M k_ref, the tile-packed maps, the
+the image-space operator applies (``fused``: in inference always for a row mask, for a general one what ``ops.GENERAL_MASK_FUSED`` says at
+that moment; in training only for a general mask with ``ops.GENERAL_MASK_FUSED`` and ``ops.GENERAL_MASK_FUSED_TRAIN`` both on -- a row mask
+takes its autograd functions in the ``train`` branches), and whether the methods build an autograd graph (``train``).  What is constant over the cascades -- A^H M k_ref, the tile-packed maps, the
 float mask of the literal chain -- is made on first use and kept.
 
   method                 row mask                       general mask, fused              general mask, literal           training (row / general)
@@ -15,6 +16,10 @@ float mask of the literal chain -- is made on first use and kept.
   residual_backward()    image_dc (1, 0, -1), tiled     image_dc (1, 0, -1)              ops.masked_residual_backward    ImageDcFixedFn / ag.masked_residual_backward
   forward_masked()       sens_expand_dc hard_mask       sens_expand_dc, apply_mask       sens_expand_dc, * mask + 0.0    SensExpandFn with the mask / SensExpandFn, * mask
   backward_masked()      * mask + 0.0, sens_reduce      apply_mask, sens_reduce          * mask + 0.0, sens_reduce       SensReduceFn with the mask / * mask, SensReduceFn
+
+Training with a general mask and both switches on (``train and fused``) takes the row-mask column of the training forms: zero_filled() is
+CoilReduceFn with the mask plane, soft_dc() ImageDcFn, residual_backward() ImageDcFixedFn (1, 0, -1) -- images saved for backward, no
+coil-wise k-space.  forward_masked() / backward_masked() stay literal there: the dual net's k-space CNN needs the k-space itself.
 """
 from typing import Optional
 
@@ -31,7 +36,7 @@ class Acquisition:
             raise ValueError(f"mask {tuple(mask.shape)} is in neither layout for k-space {tuple(ref_kspace.shape)}: pass it through ops.as_mask_u8")
         self.kspace, self.mask, self.sens, self.train = ref_kspace, mask, sens_maps, train
         self.row = layout == "row"
-        self.fused = not train and (self.row or ops.GENERAL_MASK_FUSED)
+        self.fused = ops.general_mask_fused_train(mask, ref_kspace) if train else (self.row or ops.GENERAL_MASK_FUSED)
         self._hyb = self._zf = self._tiled = self._mf = None
 
     @property
@@ -70,25 +75,25 @@ class Acquisition:
 
     def soft_dc(self, img: torch.Tensor, lambda_reg: torch.Tensor, magnitude: bool = False) -> torch.Tensor:
         """reduce(DC(expand(img))): the soft data consistency of reference varnet.py:281-282 and the next cascade's sens_reduce."""
+        if self.train:
+            if self.row or self.fused:
+                return ag.ImageDcFn.apply(img, self.sens, self.zero_filled(), self.mask, lambda_reg)
+            k = ops.soft_dc_blend(ag.SensExpandFn.apply(img, self.sens, None), self.kspace, self.mask, lambda_reg)
+            return ag.SensReduceFn.apply(k.contiguous(), self.sens, None)
         if self.fused:
             return ops.image_dc(img, self.sens, self.zero_filled(), self.mask, lambda_reg, magnitude=magnitude, sens_tiled=self.tiled)
-        if not self.train:
-            k = ops.soft_dc_blend(ops.sens_expand_dc(img, self.sens), self.kspace, self.mask, lambda_reg.detach())
-            return ops.sens_reduce(k, self.sens, magnitude=magnitude, destroy_input=True)
-        if self.row:
-            return ag.ImageDcFn.apply(img, self.sens, self.zero_filled(), self.mask, lambda_reg)
-        k = ops.soft_dc_blend(ag.SensExpandFn.apply(img, self.sens, None), self.kspace, self.mask, lambda_reg)
-        return ag.SensReduceFn.apply(k.contiguous(), self.sens, None)
+        k = ops.soft_dc_blend(ops.sens_expand_dc(img, self.sens), self.kspace, self.mask, lambda_reg.detach())
+        return ops.sens_reduce(k, self.sens, magnitude=magnitude, destroy_input=True)
 
     def residual_backward(self, x0: torch.Tensor) -> torch.Tensor:
         """A^H M (M A x0 - k_ref): XPDNet's K step and masked backward operator (reference xpdnet.py:128-131, 161-167) without the k-space."""
+        if self.train:
+            if self.row or self.fused:
+                return ag.ImageDcFixedFn.apply(x0, self.sens, self.zero_filled(), self.mask, 1.0, 0.0, -1.0)
+            return ag.masked_residual_backward(x0, self.sens, self.kspace, self.mask)
         if self.fused:
             return ops.image_dc(x0, self.sens, self.zero_filled(), self.mask, weights=(1.0, 0.0, -1.0), sens_tiled=self.tiled)
-        if not self.train:
-            return ops.masked_residual_backward(x0, self.sens, self.kspace, self.mask)
-        if self.row:
-            return ag.ImageDcFixedFn.apply(x0, self.sens, self.zero_filled(), self.mask, 1.0, 0.0, -1.0)
-        return ag.masked_residual_backward(x0, self.sens, self.kspace, self.mask)
+        return ops.masked_residual_backward(x0, self.sens, self.kspace, self.mask)
 
     def forward_masked(self, x0: torch.Tensor) -> torch.Tensor:
         """M A x0 as coil-wise k-space (b, t, c, h, w, 2): the masked forward operator (reference xpdnet.py:104-131)."""

@@ -475,11 +475,19 @@ def is_general_mask(mask: torch.Tensor, kspace: torch.Tensor) -> bool:
 
 GENERAL_MASK_FUSED = _os.environ.get("CINE_GENERAL_MASK_FUSED", "1") == "1"    # A/B switch: False = the literal coil-wise k-space chain for masks that vary along w
                                                                                 # (soft_dc_blend, masked_residual_backward, h_operator's expand -> mask -> reduce); the training form
+GENERAL_MASK_FUSED_TRAIN = _os.environ.get("CINE_GENERAL_MASK_FUSED_TRAIN", "0") == "1"    # training takes the image-space operators for such masks too (ImageDcFn, ImageDcFixedFn,
+                                                                                            # ConjGradFn on normal_op); needs GENERAL_MASK_FUSED as well.  Off: training keeps the literal chain
 
 
 def general_mask_fused(mask: torch.Tensor, kspace: torch.Tensor) -> bool:
     """True where the inference branches take the image-space operator for a mask that varies along w."""
     return GENERAL_MASK_FUSED and is_general_mask(mask, kspace)
+
+
+def general_mask_fused_train(mask: torch.Tensor, like: torch.Tensor, t: Optional[int] = None) -> bool:
+    """True where the training branches (``dc.Acquisition``, ``autograd.ConjGradFn``) take the image-space operator for a mask that varies
+    along w: both switches on.  ``like``, ``t``: as ``mask_layout``."""
+    return GENERAL_MASK_FUSED and GENERAL_MASK_FUSED_TRAIN and mask_layout(mask, like, t) == "general"
 
 
 _GENERAL_WS = {}
@@ -604,7 +612,7 @@ def h_operator(x: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_r
                _hyb: Optional[torch.Tensor] = None, sens_tiled: Optional[torch.Tensor] = None, literal: bool = False) -> torch.Tensor:
     """CineNet's H = A^H M A + softplus(lambda) I (reference cinenet.py:121-133) for either mask layout: the one-kernel image-space
     operator for a (b, t, 1, h, 1, 1) row mask, its two-pass form for a mask that varies along w (``GENERAL_MASK_FUSED`` off or
-    ``literal``, the training form: the literal expand -> mask -> reduce chain)."""
+    ``literal``, the training form unless ``GENERAL_MASK_FUSED_TRAIN``: the literal expand -> mask -> reduce chain)."""
     layout = mask_layout(mask, sens, x.shape[1])
     if layout == "row":
         return normal_op(x, sens, mask, lambda_reg, sens_tiled)

@@ -45,7 +45,7 @@ void set_error(const char* fmt, ...);   // api.cpp (thread-local buffer)
 enum Diag { D_WGRAD_PLANE = 0, D_WGRAD_GENERAL, D_UNET_BRANCHED, D_CRNN_SWEEP_C,
             D_CONV_PLANE, D_TCONV_PLANE, D_CONV_WIDE, D_CONV_WIDE_V3, D_CONV_COARSE, D_CONV1X1_STREAM, D_CONV_PAIR,
             D_CONV_GENERAL_VEC, D_CONV_GENERAL_ELEM, D_POOL3D_VEC, D_POOL3D_SCALAR,
-            D_DC_MASK2D,          // column-pass launches that weight by a mask plane (cine_image_dc_general / cine_normal_op_general)
+            D_DC_MASK2D,          // column-pass launches that weight by a mask plane (cine_image_dc_general / cine_normal_op_general / cine_image_dc_general_sens_grad)
             D_COUNT };
 void diag_count(int which);
 

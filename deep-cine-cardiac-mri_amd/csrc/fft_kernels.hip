@@ -35,8 +35,10 @@ enum { POST_NONE = 0, POST_DC = 1, POST_HARD = 2, POST_RESID = 3, POST_W2D = 4 }
                                                                                       // W2D: k * (mask(ky, kx) ? w1 : w0), the mask a full (h, w) plane per frame
 enum { PRE_NONE = 0, PRE_SMUL = 1 };
 enum { RPOST_NONE = 0, RPOST_REDUCE = 1, RPOST_REDUCE_ABS = 2, RPOST_RSS = 3,     // RSS: sqrt(sum_c |x_c|^2) (coil_combine.py:21-34)
-       RPOST_REDUCE_ZF = 4, RPOST_REDUCE_ZF_ABS = 5 };                           // REDUCE (_ABS) of sum + beta * zf
+       RPOST_REDUCE_ZF = 4, RPOST_REDUCE_ZF_ABS = 5,                             // REDUCE (_ABS) of sum + beta * zf
+       RPOST_MULC = 6, RPOST_MULC_ACC = 7 };                                     // no coil sum: out[bt, c] (+)= x_c * conj(img[bt]) (the maps' gradient)
 constexpr bool rpost_zf(int post) { return post == RPOST_REDUCE_ZF || post == RPOST_REDUCE_ZF_ABS; }
+constexpr bool rpost_mulc(int post) { return post == RPOST_MULC || post == RPOST_MULC_ACC; }
 
 template <bool F200> __device__ __forceinline__ void load_twiddles(cf* tw, int n) {
     if (F200) {
@@ -170,7 +172,7 @@ struct RowArgs {
     int W;
     int s_in, s_out;
     // coil modes
-    const cf* sens; const cf* img;
+    const cf* sens; const cf* img;      // img: PRE_SMUL's image; RPOST_MULC (_ACC)'s conjugated factor (b, t, h, w)
     int T, C, H, rpw, cc;  // rows per workgroup, coils per chunk
     // RPOST_REDUCE_ZF (_ABS): + beta * zf behind the coil sum (zf (b, t, h, w) or null).  lam != null: beta from softplus(*lam) as in
     // imgdc_weights (lam_beta 0: v / (1 + v), 1: v)
@@ -181,6 +183,12 @@ __device__ __forceinline__ float row_beta(const RowArgs& a) {
     if (!a.lam) return a.beta;
     const float v = softplus1(*a.lam);
     return a.lam_beta ? v : v * (1.0f / (1.f + v));
+}
+// RPOST_MULC (_ACC): x * conj(o) into (onto) the coil image's own point; every point has one owner, so the read-modify-write needs no atomics
+template <int POST> __device__ __forceinline__ void row_store_mulc(cf* dst, cf x, cf o) {
+    cf m = cmulc(x, o);
+    if (POST == RPOST_MULC_ACC) { const cf p = *dst; m.x += p.x; m.y += p.y; }
+    *dst = m;
 }
 template <int POST> __device__ __forceinline__ void row_store_zf(const RowArgs& a, long o, cf s, float beta) {
     if (a.zf) { const cf z = a.zf[o]; s.x = fmaf(beta, z.x, s.x); s.y = fmaf(beta, z.y, s.y); }
@@ -251,14 +259,17 @@ __global__ void row_pass_kernel(RowArgs a) {
         }
         __syncthreads();
         cf* res = run_lines<F200, DIR, LINES>(t0, t1, W, tw);
-        if (POST == RPOST_NONE) {
+        if (POST == RPOST_NONE || rpost_mulc(POST)) {
             for (int e = tid; e < LINES * W; e += nt) {
                 const int l = e / W, i = e - l * W;
                 const int cl = l / a.rpw, r = l - cl * a.rpw;
                 const int h = h0 + r;
                 if (cl >= nc || h >= a.H) continue;
                 int k = i - a.s_out; if (k < 0) k += W;
-                a.out[((long)bt * a.C + c0 + cl) * HW + (long)h * W + i] = res[res_pos<F200>(k) * LP + l];
+                cf* dst = a.out + ((long)bt * a.C + c0 + cl) * HW + (long)h * W + i;
+                const cf x = res[res_pos<F200>(k) * LP + l];
+                if (rpost_mulc(POST)) row_store_mulc<POST>(dst, x, a.img[(long)bt * HW + (long)h * W + i]);
+                else *dst = x;
             }
         } else {
 #pragma unroll
@@ -283,7 +294,7 @@ __global__ void row_pass_kernel(RowArgs a) {
         }
         __syncthreads();
     }
-    if (POST != RPOST_NONE) {
+    if (POST != RPOST_NONE && !rpost_mulc(POST)) {
         const float zf_beta = rpost_zf(POST) ? row_beta(a) : 0.f;
 #pragma unroll
         for (int o = 0; o < kMaxOut; ++o) {
@@ -451,6 +462,7 @@ __global__ __launch_bounds__(kFT, 3) void col200_kernel(ColArgs a) {
 
 // Row pass along w (W == 200), inverse, fused with conj(S) multiply + coil sum (+ magnitude):
 //   global -> r10^-1 -> LDS -> r20^-1 -> LDS -> sum_c conj(S) x -> global
+// RPOST_MULC (_ACC) keeps the coils apart instead: x_c * conj(img) into (onto) each coil image of `out`.
 template <int POST>
 __global__ __launch_bounds__(kFT, 3) void row200_reduce_kernel(RowArgs a) {
     constexpr int LP = kLP200r;
@@ -468,7 +480,7 @@ __global__ __launch_bounds__(kFT, 3) void row200_reduce_kernel(RowArgs a) {
         // sensitivities of this thread's first output pixel, fetched up front (up to kSPre coils)
         constexpr int kSPre = 16;
         cf spre[kSPre];
-        if (POST != RPOST_RSS) {
+        if (POST != RPOST_RSS && !rpost_mulc(POST)) {
             const int rr0 = tid / 200, i0 = tid - rr0 * 200;
             const cf* sb = a.sens + ((long)b * a.C + c0) * HW + (long)min(h0 + rr0, a.H - 1) * 200 + i0;
 #pragma unroll
@@ -515,6 +527,12 @@ __global__ __launch_bounds__(kFT, 3) void row200_reduce_kernel(RowArgs a) {
                 acc[o] = s_acc;
                 continue;
             }
+            if (rpost_mulc(POST)) {
+                const cf oth = a.img[(long)bt * HW + (long)h * 200 + i];
+                cf* dst = a.out + ((long)bt * a.C + c0) * HW + (long)h * 200 + i;
+                for (int cl = 0; cl < nc; ++cl) row_store_mulc<POST>(dst + (long)cl * HW, t[p + cl * a.rpw + rr], oth);
+                continue;
+            }
             const cf* sbase = a.sens + ((long)b * a.C + c0) * HW + (long)h * 200 + i;
             int cg0 = 0;
             if (o == 0) {                                   // first output: sensitivities already in registers
@@ -543,6 +561,7 @@ __global__ __launch_bounds__(kFT, 3) void row200_reduce_kernel(RowArgs a) {
         }
         __syncthreads();
     }
+    if (rpost_mulc(POST)) return;
     const float zf_beta = rpost_zf(POST) ? row_beta(a) : 0.f;
 #pragma unroll
     for (int o = 0; o < kMaxOut; ++o) {
@@ -1572,6 +1591,42 @@ extern "C" size_t cine_image_dc_general_ws_bytes(int b, int t, int c, int h, int
     return (size_t)b * t * c * h * w * sizeof(cf);
 }
 
+// Steps 1 and 2 for one operand: hyb = column IFFT[ wgt * column FFT( row FFT(S x) ) ], the coil images of T(S x) but for the row IFFT.
+// Fills `r` and `rgrid` for the row IFFT that follows.
+static int general_expand_weight(const float* img, const float* sens, const uint8_t* mask, const float* lam, float w_sampled, float w_unsampled,
+                                 cf* hyb, int b, int t, int c, int h, int w, RowArgs& r, dim3& rgrid, hipStream_t st) {
+    r = RowArgs{};
+    r.out = hyb;
+    r.W = w; r.s_in = (w + 1) / 2; r.s_out = w / 2;
+    r.sens = reinterpret_cast<const cf*>(sens);
+    r.img = reinterpret_cast<const cf*>(img);
+    r.T = t; r.C = c; r.H = h;
+    coil_tiling(c, w, r.rpw, r.cc);
+    rgrid = dim3(ceil_div(h, r.rpw), b * t);
+    if (int e = launch_row<PRE_SMUL, RPOST_NONE>(r, rgrid, false, st)) return e;
+    const long nimg = (long)b * t * c;
+    const long step = 32768 / c * c;
+    for (long i0 = 0; i0 < nimg; i0 += step) {
+        const long ni = (nimg - i0) < step ? (nimg - i0) : step;
+        ColArgs ca{};
+        ca.in = hyb + i0 * h * w; ca.out = hyb + i0 * h * w;
+        ca.H = h; ca.W = w; ca.s_in = (h + 1) / 2; ca.s_out = h / 2; ca.coils = c;
+        ca.mask = mask + (i0 / c) * h * w;
+        ca.lam = lam; ca.w1 = w_sampled; ca.w0 = w_unsampled;
+        if (h == 200) {
+            if (int e = launch_col<POST_W2D, true>(ca, ni, false, st)) return e;
+            diag_count(D_DC_MASK2D);
+        } else {
+            if (int e = launch_col<POST_W2D>(ca, ni, false, st)) return e;
+            diag_count(D_DC_MASK2D);
+            ColArgs ci = ca; ci.mask = nullptr; ci.lam = nullptr;
+            if (int e = launch_col<POST_NONE>(ci, ni, true, st)) return e;
+        }
+    }
+    r.in = hyb; r.img = nullptr; r.sens = nullptr;
+    return CINE_OK;
+}
+
 static int image_dc_general_impl(const float* img, const float* sens, const float* zf, const uint8_t* mask,
                                  const float* lambda_dev, int lam_beta, float w_sampled, float w_unsampled, float beta,
                                  float* out, int b, int t, int c, int h, int w, int magnitude,
@@ -1585,36 +1640,10 @@ static int image_dc_general_impl(const float* img, const float* sens, const floa
     const size_t need = cine_image_dc_general_ws_bytes(b, t, c, h, w);
     CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
     hipStream_t st = as_stream(stream);
-    cf* hyb = reinterpret_cast<cf*>(ws);
-    RowArgs r{};
-    r.out = hyb;
-    r.W = w; r.s_in = (w + 1) / 2; r.s_out = w / 2;
+    RowArgs r; dim3 rgrid;
+    if (int e = general_expand_weight(img, sens, mask, lam_beta ? nullptr : lambda_dev, w_sampled, w_unsampled, reinterpret_cast<cf*>(ws),
+                                      b, t, c, h, w, r, rgrid, st)) return e;
     r.sens = reinterpret_cast<const cf*>(sens);
-    r.img = reinterpret_cast<const cf*>(img);
-    r.T = t; r.C = c; r.H = h;
-    coil_tiling(c, w, r.rpw, r.cc);
-    const dim3 rgrid(ceil_div(h, r.rpw), b * t);
-    if (int e = launch_row<PRE_SMUL, RPOST_NONE>(r, rgrid, false, st)) return e;
-    const long nimg = (long)b * t * c;
-    const long step = 32768 / c * c;
-    for (long i0 = 0; i0 < nimg; i0 += step) {
-        const long ni = (nimg - i0) < step ? (nimg - i0) : step;
-        ColArgs ca{};
-        ca.in = hyb + i0 * h * w; ca.out = hyb + i0 * h * w;
-        ca.H = h; ca.W = w; ca.s_in = (h + 1) / 2; ca.s_out = h / 2; ca.coils = c;
-        ca.mask = mask + (i0 / c) * h * w;
-        ca.lam = lam_beta ? nullptr : lambda_dev; ca.w1 = w_sampled; ca.w0 = w_unsampled;
-        if (h == 200) {
-            if (int e = launch_col<POST_W2D, true>(ca, ni, false, st)) return e;
-            diag_count(D_DC_MASK2D);
-        } else {
-            if (int e = launch_col<POST_W2D>(ca, ni, false, st)) return e;
-            diag_count(D_DC_MASK2D);
-            ColArgs ci = ca; ci.mask = nullptr; ci.lam = nullptr;
-            if (int e = launch_col<POST_NONE>(ci, ni, true, st)) return e;
-        }
-    }
-    r.in = hyb; r.img = nullptr;
     r.out = reinterpret_cast<cf*>(out); r.out_abs = out;
     r.zf = reinterpret_cast<const cf*>(zf); r.lam = lambda_dev; r.lam_beta = lam_beta; r.beta = beta;
     return magnitude ? launch_row<PRE_NONE, RPOST_REDUCE_ZF_ABS>(r, rgrid, true, st)
@@ -1659,4 +1688,38 @@ extern "C" int cine_image_dc_sens_grad(const float* img, const float* gout, cons
         hipLaunchKernelGGL(imgdc_sgrad_kernel<false>, grid, dim3(kThreadsGen), lds, st, a);
     }
     return check_launch("imgdc_sgrad_kernel");
+}
+
+// The same gradient for a mask that varies along w: T = IFFT2 [mask(ky, kx) ? w1 : w0] FFT2, so each operand takes the three stages of
+// cine_image_dc_general.  The operands go ONE AFTER THE OTHER through the same b*t*c*h*w workspace (the size cine_image_dc_general needs, so a
+// training step holds one such buffer, not two): the row IFFT of the first writes conj(g) T(S_c img) into `part`, the row IFFT of the second
+// adds T(S_c g) conj(img) onto it.
+extern "C" size_t cine_image_dc_general_sens_grad_ws_bytes(int b, int t, int c, int h, int w) {
+    return cine_image_dc_general_ws_bytes(b, t, c, h, w);
+}
+
+extern "C" int cine_image_dc_general_sens_grad(const float* img, const float* gout, const float* sens, const uint8_t* mask,
+                                               const float* lambda_dev, float w_sampled, float w_unsampled,
+                                               float* part, int b, int t, int c, int h, int w,
+                                               void* ws, size_t ws_bytes, void* stream) {
+    const char* what = "cine_image_dc_general_sens_grad";
+    CINE_REQUIRE(img && gout && sens && mask && part && ws, CINE_EINVAL, "%s: null pointer", what);
+    CINE_REQUIRE(b > 0 && t > 0 && c > 0 && c <= 32768 && h > 0 && w > 0, CINE_EINVAL, "%s: bad sizes", what);
+    CINE_REQUIRE((long)b * t <= 65535, CINE_EUNSUPPORTED, "%s: b*t > 65535", what);
+    CINE_REQUIRE(part != img && part != gout && part != sens && (const void*)part != ws, CINE_EINVAL,
+                 "%s: part must not alias img, gout, sens or ws", what);
+    if (int e = check_n(h, what)) return e;
+    if (int e = check_n(w, what)) return e;
+    const size_t need = cine_image_dc_general_sens_grad_ws_bytes(b, t, c, h, w);
+    CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
+    hipStream_t st = as_stream(stream);
+    RowArgs r; dim3 rgrid;
+    if (int e = general_expand_weight(img, sens, mask, lambda_dev, w_sampled, w_unsampled, reinterpret_cast<cf*>(ws), b, t, c, h, w, r, rgrid, st))
+        return e;
+    r.out = reinterpret_cast<cf*>(part); r.img = reinterpret_cast<const cf*>(gout);
+    if (int e = launch_row<PRE_NONE, RPOST_MULC>(r, rgrid, true, st)) return e;
+    if (int e = general_expand_weight(gout, sens, mask, lambda_dev, w_sampled, w_unsampled, reinterpret_cast<cf*>(ws), b, t, c, h, w, r, rgrid, st))
+        return e;
+    r.out = reinterpret_cast<cf*>(part); r.img = reinterpret_cast<const cf*>(img);
+    return launch_row<PRE_NONE, RPOST_MULC_ACC>(r, rgrid, true, st);
 }

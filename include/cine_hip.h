@@ -846,6 +846,19 @@ int cine_xpd_pack_bwd(const float* gplanes_xf, const float* gplanes_yf, const fl
 int cine_image_dc_sens_grad(const float* img, const float* gout, const float* sens, const uint8_t* mask,
                             const float* lambda_dev, float w_sampled, float w_unsampled,
                             float* part, int b, int t, int c, int h, int w, void* stream);
+/* The same for a sampling mask that varies along w (cine_image_dc_general; mask uint8 (b, t, h, w)): part (b, t, c, h, w) =
+ * conj(g) T(S_c img) + T(S_c g) conj(img) with T = IFFT2 [mask(ky, kx) ? w_sampled : w_unsampled] FFT2 (lambda_dev != NULL: the soft-DC
+ * pair); add the frames with cine_coil_accum(NULL, part, ...).  The two operands take the three stages of cine_image_dc_general one after
+ * the other through ONE workspace of cine_image_dc_general_sens_grad_ws_bytes() = b*t*c*h*w complex values (what cine_image_dc_general
+ * needs: the callers share the buffer); the row IFFT of the first writes part, that of the second adds onto it.  h, w: any length
+ * cine_fft_line_supported() accepts (CINE_EUNSUPPORTED otherwise); c <= 32768 (CINE_EINVAL), b*t <= 65535 (CINE_EUNSUPPORTED); part must not
+ * alias img, gout, sens or ws (CINE_EINVAL); a short workspace is CINE_EWORKSPACE.  Every argument is checked before the first launch; no
+ * allocation, no synchronisation, capturable. */
+size_t cine_image_dc_general_sens_grad_ws_bytes(int b, int t, int c, int h, int w);
+int cine_image_dc_general_sens_grad(const float* img, const float* gout, const float* sens, const uint8_t* mask,
+                                    const float* lambda_dev, float w_sampled, float w_unsampled,
+                                    float* part, int b, int t, int c, int h, int w,
+                                    void* ws, size_t ws_bytes, void* stream);
 /* gs (b, c, h, w, 2) (+)= sum_t conj(g[b, t]) z[b, t, c]: gradient of sens_reduce's coil sum sum_c conj(S_c) z_c (varnet.py:187-194)
  * with respect to S; z (b, t, c, h, w, 2) are the coil images.  g == NULL: gs (+)= sum_t z.  accumulate == 0 overwrites gs. */
 int cine_coil_accum(const float* g, const float* z, float* gs, int b, int t, int c, int h, int w, int accumulate, void* stream);
@@ -883,7 +896,8 @@ int cine_profile_begin(void);
  * 7 the same in its three-pass volume form, 8 the coarse K-split kernel, 9 the streaming 1x1 kernel of cine_conv1x1_bias,
  * 10 the general kernel's two-set pair form, 11 the general kernel with vectorised staging, 12 the general kernel with element-wise
  * staging -- input-gradient launches on the general kernel count in 10 .. 12 too; 13 / 14 cine_pool3d_act on its float4 / scalar
- * kernel; 15 column-pass launches that weight by a mask plane: cine_image_dc_general / cine_normal_op_general).  reset != 0 returns the count and zeroes it;
+ * kernel; 15 column-pass launches that weight by a mask plane: cine_image_dc_general / cine_normal_op_general /
+ * cine_image_dc_general_sens_grad).  reset != 0 returns the count and zeroes it;
  * -1 for an unknown counter. */
 long cine_diag_counter(int which, int reset);
 /* Diagnostics: a one-workgroup kernel that runs for `microseconds` (1 .. 100 000; clock-bounded AND iteration-bounded: it always ends).  The
