@@ -208,6 +208,9 @@ _SIGS = {
     "cine_image_dc_sens_grad": (c_int, [P, P, P, P, P, c_float, c_float, P, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_image_dc_general_sens_grad_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "cine_image_dc_general_sens_grad": (c_int, [P, P, P, P, P, c_float, c_float, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "cine_kspace_loss_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "cine_kspace_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "cine_kspace_loss_grad": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
     "cine_coil_accum": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "cine_rss_normalise_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "cine_complex_abs_bwd": (c_int, [P, P, P, c_long, P]),

@@ -1273,6 +1273,29 @@ class SsimLossFn(Function):
         return gx, None, None, None, None
 
 
+@_masked
+class KspaceLossFn(Function):
+    """The self-supervised k-space loss on held-out samples (cine_kspace_loss; ``cine_hip.selfsup``): image (b, t, [1,] h, w, 2), maps, measured
+    k-space and loss mask -> scalar.  Saves its inputs and the 32-byte loss record; the backward recomputes the coil-wise k-space inside its
+    kernels (cine_kspace_loss_grad).  Gradients for the image, and for the maps when they require them."""
+
+    @staticmethod
+    def forward(ctx, image, sens, kspace, mask):
+        rec = ops.kspace_loss_forward(image, sens, kspace, mask)
+        ctx.save_for_backward(image, sens, kspace, mask, rec)
+        return rec[4].clone()
+
+    @staticmethod
+    def backward(ctx, gloss):
+        image, sens, kspace, mask, rec = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not (need[0] or need[1]):
+            return None, None, None, None
+        gl = ops._dev(gloss.reshape(1).to(torch.float32), "k-space loss upstream gradient")
+        gimg, part = ops.kspace_loss_backward(image, sens, kspace, mask, rec, gl, want_image=need[0], want_sens=need[1])
+        return gimg, (coil_accum(None, part) if need[1] else None), None, None
+
+
 def masked_residual_backward(x0, sens, kref, mask):
     """``ops.masked_residual_backward`` as an autograd graph: the coil operators through their HIP kernels and adjoints (SensExpandFn / SensReduceFn),
     the two mask products and the subtraction in torch elementwise ops (differentiable in x0 and the maps)."""

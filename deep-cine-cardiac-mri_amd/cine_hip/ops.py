@@ -465,6 +465,14 @@ def mask_layout(mask: torch.Tensor, like: torch.Tensor, t: Optional[int] = None)
     return "row" if tuple(mask.shape[4:]) == (1, 1) else "general" if w > 1 and tuple(mask.shape[4:]) == (w, 1) else None
 
 
+def complex_output(output: str) -> bool:
+    """The ``output`` keyword of the six model families' ``forward``: "magnitude" (the default: (b, t, h, w), what the reference returns) or
+    "complex" (the (b, t, h, w, 2) image in front of the final magnitude, what a k-space loss needs: ``cine_hip.selfsup``)."""
+    if output not in ("magnitude", "complex"):
+        raise ValueError(f"output={output!r}: expected 'magnitude' or 'complex'")
+    return output == "complex"
+
+
 def is_row_mask(mask: torch.Tensor, kspace: torch.Tensor) -> bool:
     return mask_layout(mask, kspace) == "row"
 
@@ -530,6 +538,52 @@ def masked_residual_backward(x0: torch.Tensor, sens: torch.Tensor, kref: torch.T
     k = sens_expand_dc(x0, sens)                 # A x0, (b, t, c, h, w, 2)
     k = (k * m - kref) * m
     return sens_reduce(k, sens, destroy_input=True)
+
+
+D_KSPACE_LOSS = 32      # cine_diag_counter: column-pass launches of cine_kspace_loss / cine_kspace_loss_grad
+KSPACE_LOSS_REC = 8     # floats of the loss record: sum r^2, sum |r|_1, sum y^2, sum |y|_1, L, a, b, 0
+
+
+def _kspace_loss_args(image, sens, kspace, loss_mask):
+    _pair(image); _pair(sens); _pair(kspace)
+    image = _dev(image, "image"); sens = _dev(sens, "sens_maps"); kspace = _dev(kspace, "k-space")
+    b, t, c, h, w, _ = kspace.shape
+    if image.numel() != b * t * h * w * 2 or tuple(sens.shape) != (b, 1, c, h, w, 2):
+        raise ValueError(f"kspace_loss: image {tuple(image.shape)} / sens_maps {tuple(sens.shape)} do not match k-space {tuple(kspace.shape)}")
+    mask = _dev(loss_mask, "loss mask", torch.uint8)
+    layout = mask_layout(mask, kspace)
+    if layout is None:
+        raise ValueError(f"kspace_loss: loss mask {tuple(mask.shape)} is in neither layout for k-space {tuple(kspace.shape)}: pass it through ops.as_mask_u8")
+    if tuple(mask.shape[4:]) != (w, 1):              # one kernel path: a row mask is expanded to planes (b*t*h*w bytes)
+        _no_capture("a plane copy of the loss mask")
+        mask = mask.expand(b, t, 1, h, w, 1).contiguous()
+    nbytes = lib().cine_kspace_loss_ws_bytes(b, t, c, h, w)
+    return image, sens, kspace, mask, (b, t, c, h, w), nbytes
+
+
+def kspace_loss_forward(image: torch.Tensor, sens: torch.Tensor, kspace: torch.Tensor, loss_mask: torch.Tensor) -> torch.Tensor:
+    """cine_kspace_loss: the record (``KSPACE_LOSS_REC`` floats on the device; element 4 is the loss) of the normalised l1-l2 k-space loss of
+    ``image`` (b, t, [1,] h, w, 2) against ``kspace`` (b, t, c, h, w, 2) on the points of ``loss_mask`` (either layout of ``as_mask_u8``)."""
+    image, sens, kspace, mask, (b, t, c, h, w), nbytes = _kspace_loss_args(image, sens, kspace, loss_mask)
+    ws = _general_ws(nbytes, image.device)
+    rec = torch.empty(KSPACE_LOSS_REC, device=image.device, dtype=torch.float32)
+    check(lib().cine_kspace_loss(image.data_ptr(), sens.data_ptr(), kspace.data_ptr(), mask.data_ptr(), rec.data_ptr(), b, t, c, h, w,
+                                 ws.data_ptr(), nbytes, _stream()), "cine_kspace_loss")
+    return rec
+
+
+def kspace_loss_backward(image: torch.Tensor, sens: torch.Tensor, kspace: torch.Tensor, loss_mask: torch.Tensor, rec: torch.Tensor,
+                         gloss: torch.Tensor, want_image: bool = True, want_sens: bool = False):
+    """cine_kspace_loss_grad -> (image gradient in ``image``'s shape or None, the maps' gradient per frame (b, t, c, h, w, 2) or None)."""
+    shape = image.shape
+    image, sens, kspace, mask, (b, t, c, h, w), nbytes = _kspace_loss_args(image, sens, kspace, loss_mask)
+    rec = _dev(rec, "loss record"); gloss = _dev(gloss, "loss gradient")
+    ws = _general_ws(nbytes, image.device)
+    gimg = torch.empty(shape, device=image.device, dtype=image.dtype) if want_image else None
+    part = torch.empty((b, t, c, h, w, 2), device=image.device, dtype=image.dtype) if want_sens else None
+    check(lib().cine_kspace_loss_grad(image.data_ptr(), sens.data_ptr(), kspace.data_ptr(), mask.data_ptr(), rec.data_ptr(), gloss.data_ptr(),
+                                      _p(gimg), _p(part), b, t, c, h, w, ws.data_ptr(), nbytes, _stream()), "cine_kspace_loss_grad")
+    return gimg, part
 
 
 def sens_tile_pack(sens: torch.Tensor) -> Optional[torch.Tensor]:

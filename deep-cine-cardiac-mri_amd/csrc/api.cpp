@@ -17,8 +17,14 @@ void set_error(const char* fmt, ...) {
 
 thread_local int g_alone_on_chip = 0;      // conv_cfg.h: AloneScope (set by entry points whose arguments say one slice runs alone)
 
-static std::atomic<long> g_diag[D_COUNT];
-void diag_count(int which) { if (which >= 0 && which < D_COUNT) g_diag[which].fetch_add(1, std::memory_order_relaxed); }
+static std::atomic<long> g_diag[D_COUNT + (D_EXT_END - D_EXT_FIRST)];
+// slot of a counter id, -1 for an unknown one: ids 0 .. D_COUNT - 1, then D_EXT_FIRST .. D_EXT_END - 1
+static int diag_slot(int which) {
+    if (which >= 0 && which < D_COUNT) return which;
+    if (which >= D_EXT_FIRST && which < D_EXT_END) return D_COUNT + (which - D_EXT_FIRST);
+    return -1;
+}
+void diag_count(int which) { const int s = diag_slot(which); if (s >= 0) g_diag[s].fetch_add(1, std::memory_order_relaxed); }
 
 // ---- optional launch profiler
 static std::atomic<int> g_prof_on{0};
@@ -67,8 +73,9 @@ const char* cine_profile_family_name(int i) {
     return (i >= 0 && i < cine::F_COUNT) ? names[i] : "";
 }
 long cine_diag_counter(int which, int reset) {
-    if (which < 0 || which >= cine::D_COUNT) return -1;
-    return reset ? cine::g_diag[which].exchange(0) : cine::g_diag[which].load();
+    const int s = cine::diag_slot(which);
+    if (s < 0) return -1;
+    return reset ? cine::g_diag[s].exchange(0) : cine::g_diag[s].load();
 }
 int cine_version(void) { return 3; }       // 3: U-Net passes as concurrent branches, C time sweeps, diagnostic counters (round 6); 2: LeakyReLU slope per call (round 5)
 const char* cine_last_error(void) { return cine::g_err; }

@@ -47,6 +47,10 @@ enum Diag { D_WGRAD_PLANE = 0, D_WGRAD_GENERAL, D_UNET_BRANCHED, D_CRNN_SWEEP_C,
             D_CONV_GENERAL_VEC, D_CONV_GENERAL_ELEM, D_POOL3D_VEC, D_POOL3D_SCALAR,
             D_DC_MASK2D,          // column-pass launches that weight by a mask plane (cine_image_dc_general / cine_normal_op_general / cine_image_dc_general_sens_grad)
             D_COUNT };
+// Counters added later take ids from 32 on: the suite pins id D_COUNT as the first unknown one of the block above.
+enum DiagExt { D_EXT_FIRST = 32,
+               D_KSPACE_LOSS = D_EXT_FIRST,   // column-pass launches of the k-space loss (cine_kspace_loss, cine_kspace_loss_grad): one per column chunk
+               D_EXT_END };
 void diag_count(int which);
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }

@@ -31,8 +31,12 @@ constexpr int kMaxGenericN = 400;                  // direct DFT, O(n^2): any le
 constexpr int kMaxSmoothN = 512;                   // mixed radix: 2^a 3^b 5^c (two 512 x 9 tiles + twiddles = 78 KB of LDS, opted in per kernel)
 constexpr int kMaxOut = 4;                          // reduce outputs per thread
 
-enum { POST_NONE = 0, POST_DC = 1, POST_HARD = 2, POST_RESID = 3, POST_W2D = 4 };   // RESID: mask ? k - kref : 0 (xpdnet.py:128-131,295-298)
-                                                                                      // W2D: k * (mask(ky, kx) ? w1 : w0), the mask a full (h, w) plane per frame
+enum { POST_NONE = 0, POST_DC = 1, POST_HARD = 2, POST_RESID = 3, POST_W2D = 4,     // RESID: mask ? k - kref : 0 (xpdnet.py:128-131,295-298)
+       POST_LOSS = 5, POST_LOSSG = 6 };                                              // W2D: k * (mask(ky, kx) ? w1 : w0), the mask a full (h, w) plane per frame
+// LOSS (cine_kspace_loss): nothing is stored; at the points of the mask plane r = k - kref and the workgroup's sums of r^2, |r|_1, kref^2, |kref|_1
+// go into its slot (loss_slot).  LOSSG (cine_kspace_loss_grad): mask ? g (a r + b sign(r)) : 0 with a, b from the loss record and g the incoming scalar.
+constexpr bool post_plane(int post) { return post == POST_W2D || post == POST_LOSS || post == POST_LOSSG; }
+constexpr bool post_kref(int post) { return post == POST_DC || post == POST_RESID || post == POST_LOSS || post == POST_LOSSG; }
 enum { PRE_NONE = 0, PRE_SMUL = 1 };
 enum { RPOST_NONE = 0, RPOST_REDUCE = 1, RPOST_REDUCE_ABS = 2, RPOST_RSS = 3,     // RSS: sqrt(sum_c |x_c|^2) (coil_combine.py:21-34)
        RPOST_REDUCE_ZF = 4, RPOST_REDUCE_ZF_ABS = 5,                             // REDUCE (_ABS) of sum + beta * zf
@@ -104,7 +108,46 @@ struct ColArgs {
     const uint8_t* premask;   // optional: rows with premask == 0 enter the transform as zeros and are not read
     float w1, w0;         // POST_W2D: weight of sampled / unsampled points (lam != null: the soft-DC pair 1 / (1 + softplus(*lam)), 1);
                           // mask is then the chunk's first (H, W) plane, one plane per `coils` images
+    const float* rec; const float* gscale;   // POST_LOSSG: the loss record (8 floats: a at 5, b at 6) and the incoming scalar gradient, both on the device
 };
+
+// ---- k-space loss (cine_kspace_loss): per-workgroup partial sums
+// A column workgroup owns the columns [w0, w0 + lines) of its image in the workspace: once its tile is loaded nobody else reads them, so its four
+// partial sums go there -- the workspace holds the slots and needs no byte beyond cine_image_dc_general_ws_bytes.  Float j of the slot: row 0,
+// columns w0 and w0 + 1; a one-column tile takes rows 0 and 1 of its column instead (h == 1 with such a tile is refused by the entry points).
+// The record (8 floats): sum r^2, sum |r|_1, sum y^2, sum |y|_1, L, a, b, 0.
+__device__ __forceinline__ float* loss_slot(cf* imgbase, int W, int w0, int lines, int j) {
+    return min(lines, W - w0) >= 2 ? reinterpret_cast<float*>(imgbase + w0) + j
+                                   : reinterpret_cast<float*>(imgbase + (long)(j >> 1) * W + w0) + (j & 1);
+}
+__device__ __forceinline__ float sign0(float x) { return (float)((x > 0.f) - (x < 0.f)); }
+__device__ __forceinline__ void loss_point(bool on, cf k, cf y, float (&s)[4]) {
+    const cf r = csub(k, y);
+    s[0] += on ? r.x * r.x + r.y * r.y : 0.f;        // selects, not products: kref may hold anything (NaN) off the mask
+    s[1] += on ? fabsf(r.x) + fabsf(r.y) : 0.f;
+    s[2] += on ? y.x * y.x + y.y * y.y : 0.f;
+    s[3] += on ? fabsf(y.x) + fabsf(y.y) : 0.f;
+}
+__device__ __forceinline__ cf loss_grad_point(bool on, cf k, cf y, float ca, float cb) {
+    const cf r = csub(k, y);
+    return on ? mk(fmaf(ca, r.x, cb * sign0(r.x)), fmaf(ca, r.y, cb * sign0(r.y))) : mk(0.f, 0.f);
+}
+// the workgroup's four sums in a fixed order (a tree over the threads), written to its slot by threads 0 .. 3.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void loss_slot_store(const float (&s)[4], cf* imgbase, int W, int w0, int lines) {
+    __shared__ float red[4][256];
+    const int tid = threadIdx.x, nt = blockDim.x;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[q][tid] = s[q];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st && tid + st < nt) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + st];
+        }
+        __syncthreads();
+    }
+    if (tid < 4) *loss_slot(imgbase, W, w0, lines, tid) = red[tid][0];
+}
 
 __device__ __forceinline__ void col_weights(const ColArgs& a, float& w1, float& w0) {
     w1 = a.w1; w0 = a.w0;
@@ -138,11 +181,25 @@ __global__ void col_pass_kernel(ColArgs a) {
 
     float v = 0.f, inv1v = 1.f;
     if (POST == POST_DC) { v = softplus1(*a.lam); }
-    const uint8_t* mrow = (POST != POST_NONE && POST != POST_W2D) ? a.mask + (img / a.coils) * H : nullptr;
-    const uint8_t* mpl = (POST == POST_W2D) ? a.mask + (img / a.coils) * H * a.W : nullptr;
+    const uint8_t* mrow = (POST != POST_NONE && !post_plane(POST)) ? a.mask + (img / a.coils) * H : nullptr;
+    const uint8_t* mpl = post_plane(POST) ? a.mask + (img / a.coils) * H * a.W : nullptr;
     float ws1 = 1.f, ws0 = 1.f;                 // POST_W2D: weight of sampled / unsampled points
     if (POST == POST_W2D) col_weights(a, ws1, ws0);
-    const cf* kref = (POST == POST_DC || POST == POST_RESID) ? a.kref + img * H * a.W : nullptr;
+    const cf* kref = post_kref(POST) ? a.kref + img * H * a.W : nullptr;
+    if constexpr (POST == POST_LOSS) {
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int e = tid; e < H * LINES; e += nt) {
+            const int i = e / LINES, l = e % LINES, col = w0 + l;
+            if (col >= a.W) continue;
+            int k = i - a.s_out; if (k < 0) k += H;
+            const long o = (long)i * a.W + col;
+            if (mpl[o]) loss_point(true, res[res_pos<F200>(k) * LP + l], kref[o], s);      // this kernel reads kref at the mask's points only
+        }
+        loss_slot_store(s, out, a.W, w0, LINES);
+        return;
+    }
+    float ca = 0.f, cb = 0.f;
+    if (POST == POST_LOSSG) { const float go = *a.gscale; ca = a.rec[5] * go; cb = a.rec[6] * go; }
     for (int e = tid; e < H * LINES; e += nt) {
         const int i = e / LINES, l = e % LINES, col = w0 + l;
         if (col >= a.W) continue;
@@ -159,10 +216,13 @@ __global__ void col_pass_kernel(ColArgs a) {
             val = mrow[i] ? csub(val, kref[(long)i * a.W + col]) : mk(0.f, 0.f);
         } else if (POST == POST_W2D) {
             val = cscale(val, mpl[(long)i * a.W + col] ? ws1 : ws0);
+        } else if (POST == POST_LOSSG) {
+            const long o = (long)i * a.W + col;
+            val = mpl[o] ? loss_grad_point(true, val, kref[o], ca, cb) : mk(0.f, 0.f);
         }
         out[(long)i * a.W + col] = val;
     }
-    (void)inv1v;
+    (void)inv1v; (void)ca; (void)cb;
 }
 
 // ------------------------------------------------------------------ row pass
@@ -353,7 +413,7 @@ __global__ __launch_bounds__(kFT, 3) void col200_kernel(ColArgs a) {
     cf rr[20];
     if (POST != POST_NONE) {
         const int g2 = tid / kFL;
-        if (POST == POST_W2D) {
+        if (post_plane(POST)) {
             // this thread's 20 points of its own column: byte loads strided by W, the 16 lanes of a row on consecutive bytes
             const uint8_t* mcol = a.mask + (img / a.coils) * 200 * a.W + min(w0 + tid % kFL, a.W - 1);
 #pragma unroll
@@ -363,7 +423,8 @@ __global__ __launch_bounds__(kFT, 3) void col200_kernel(ColArgs a) {
 #pragma unroll
             for (int k2 = 0; k2 < 20; ++k2) mbits |= (mrow[rot10(k2, g2)] ? 1u : 0u) << k2;
         }
-        if (POST == POST_DC || POST == POST_RESID) {
+        if (POST == POST_LOSS && w0 + tid % kFL >= a.W) mbits = 0;         // a lane past the edge holds a copy of the last column: it adds nothing
+        if (post_kref(POST)) {
             const cf* kref = a.kref + img * 200 * a.W;
             const int colc = min(w0 + tid % kFL, a.W - 1);
 #pragma unroll
@@ -427,6 +488,17 @@ __global__ __launch_bounds__(kFT, 3) void col200_kernel(ColArgs a) {
             col_weights(a, ws1, ws0);
 #pragma unroll
             for (int k2 = 0; k2 < 20; ++k2) v[k2] = cscale(v[k2], ((mbits >> k2) & 1u) ? ws1 : ws0);
+        } else if (POST == POST_LOSSG) {
+            const float go = *a.gscale, ca = a.rec[5] * go, cb = a.rec[6] * go;
+#pragma unroll
+            for (int k2 = 0; k2 < 20; ++k2) v[k2] = loss_grad_point((mbits >> k2) & 1u, v[k2], rr[k2], ca, cb);
+        }
+        if constexpr (POST == POST_LOSS) {
+            float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int k2 = 0; k2 < 20; ++k2) loss_point((mbits >> k2) & 1u, v[k2], rr[k2], s);
+            loss_slot_store(s, out, a.W, w0, kFL);
+            return;
         }
         if (!INV_AFTER) {
             if (col < a.W) {
@@ -1070,11 +1142,14 @@ static int allow_lds(const void* kern, size_t lds, const char* what) {
 }
 template <typename K> static int allow_lds(K kern, size_t lds, const char* what) { return allow_lds(reinterpret_cast<const void*>(kern), lds, what); }
 
+// columns per workgroup of a column pass along h: launch_col's tiling, and what kspace_loss_final_kernel walks the slots by
+static int col_lines(int h) { return h == 200 ? kFL : kLinesGen; }
+
 template <int POST, bool INV_AFTER = false, bool PREMASK = false>
 static int launch_col(const ColArgs& a, long nimg, bool inverse, hipStream_t st) {
     if (nimg == 0) return CINE_OK;
     const bool f200 = a.H == 200;
-    const int lines = f200 ? kFL : kLinesGen;
+    const int lines = col_lines(a.H);
     dim3 grid(ceil_div(a.W, lines), (unsigned)nimg);
     CINE_REQUIRE(nimg <= 65535, CINE_EUNSUPPORTED, "column pass: %ld images > 65535", nimg);
     ProfScope prof(F_FFT_COL, st);
@@ -1593,8 +1668,12 @@ extern "C" size_t cine_image_dc_general_ws_bytes(int b, int t, int c, int h, int
 
 // Steps 1 and 2 for one operand: hyb = column IFFT[ wgt * column FFT( row FFT(S x) ) ], the coil images of T(S x) but for the row IFFT.
 // Fills `r` and `rgrid` for the row IFFT that follows.
+// POST_W2D weights by the mask plane; POST_LOSS / POST_LOSSG (cine_kspace_loss[_grad]) compare with `kref` on it: LOSS stores nothing and has no
+// inverse pass (hyb then holds the partial sums), LOSSG reads the loss record `rec` and the incoming scalar `gscale`.
+struct ColExtra { const float* kref = nullptr; const float* rec = nullptr; const float* gscale = nullptr; };
+template <int POST = POST_W2D>
 static int general_expand_weight(const float* img, const float* sens, const uint8_t* mask, const float* lam, float w_sampled, float w_unsampled,
-                                 cf* hyb, int b, int t, int c, int h, int w, RowArgs& r, dim3& rgrid, hipStream_t st) {
+                                 cf* hyb, int b, int t, int c, int h, int w, RowArgs& r, dim3& rgrid, hipStream_t st, ColExtra x = ColExtra()) {
     r = RowArgs{};
     r.out = hyb;
     r.W = w; r.s_in = (w + 1) / 2; r.s_out = w / 2;
@@ -1613,15 +1692,18 @@ static int general_expand_weight(const float* img, const float* sens, const uint
         ca.H = h; ca.W = w; ca.s_in = (h + 1) / 2; ca.s_out = h / 2; ca.coils = c;
         ca.mask = mask + (i0 / c) * h * w;
         ca.lam = lam; ca.w1 = w_sampled; ca.w0 = w_unsampled;
-        if (h == 200) {
-            if (int e = launch_col<POST_W2D, true>(ca, ni, false, st)) return e;
-            diag_count(D_DC_MASK2D);
+        ca.kref = x.kref ? reinterpret_cast<const cf*>(x.kref) + i0 * h * w : nullptr;
+        ca.rec = x.rec; ca.gscale = x.gscale;
+        if (h == 200 && POST != POST_LOSS) {
+            if (int e = launch_col<POST, true>(ca, ni, false, st)) return e;
         } else {
-            if (int e = launch_col<POST_W2D>(ca, ni, false, st)) return e;
-            diag_count(D_DC_MASK2D);
-            ColArgs ci = ca; ci.mask = nullptr; ci.lam = nullptr;
-            if (int e = launch_col<POST_NONE>(ci, ni, true, st)) return e;
+            if (int e = launch_col<POST>(ca, ni, false, st)) return e;
+            if (POST != POST_LOSS) {
+                ColArgs ci = ca; ci.mask = nullptr; ci.lam = nullptr; ci.kref = nullptr;
+                if (int e = launch_col<POST_NONE>(ci, ni, true, st)) return e;
+            }
         }
+        diag_count(POST == POST_W2D ? (int)D_DC_MASK2D : (int)D_KSPACE_LOSS);
     }
     r.in = hyb; r.img = nullptr; r.sens = nullptr;
     return CINE_OK;
@@ -1722,4 +1804,114 @@ extern "C" int cine_image_dc_general_sens_grad(const float* img, const float* go
         return e;
     r.out = reinterpret_cast<cf*>(part); r.img = reinterpret_cast<const cf*>(img);
     return launch_row<PRE_NONE, RPOST_MULC_ACC>(r, rgrid, true, st);
+}
+
+// ------------------------------------------------------------------ self-supervised k-space loss on held-out samples
+// SSDU (Yaman et al., MRM 2020): with u = FFT2(S_c x) (sens_expand, varnet.py:181-185), r = L (u - y) and v = L y for a 0/1 loss mask L,
+//     loss = 1/2 ||r||_2 / ||v||_2 + 1/2 ||r||_1 / ||v||_1        (both norms over every real component of the batch)
+// The coil-wise k-space exists only inside the column workgroups, as in cine_image_dc_general:
+//   forward   1  S x -> row FFT -> ws                                        (row200_expand_kernel / row_pass_kernel<PRE_SMUL>)
+//             2  column FFT -> four partial sums per workgroup, into ws      (POST_LOSS; y is read at the mask's points; off the mask the h == 200
+//                kernel re-reads one cached element of the image, y[0], and discards it, as POST_DC does: no branches, no traffic)
+//             3  kspace_loss_final_kernel: the slots added in a fixed order in float64 -> the record (8 floats)
+//   backward  1  as above (nothing coil-wise is kept between the passes)
+//             2  column FFT -> g (a r + b sign(r)) on the mask -> column IFFT  (POST_LOSSG)
+//             3  row IFFT -> conj(S), coil sum -> gimg;  row IFFT -> * conj(x) -> gsens_part, per frame (RPOST_MULC)
+namespace cine {
+__global__ __launch_bounds__(256) void kspace_loss_final_kernel(cf* ws, long nimg, int H, int W, int lines, float* rec) {
+    __shared__ double red[4][256];
+    const int tid = threadIdx.x;
+    const int ntx = (W + lines - 1) / lines;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long e = tid; e < nimg * ntx; e += 256) {
+        const long img = e / ntx;
+        const int w0 = (int)(e - img * ntx) * lines;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] += (double)*loss_slot(ws + img * H * W, W, w0, lines, q);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[q][tid] = s[q];
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + st];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double r2 = red[0][0], r1 = red[1][0], y2 = red[2][0], y1 = red[3][0];
+        rec[0] = (float)r2; rec[1] = (float)r1; rec[2] = (float)y2; rec[3] = (float)y1;
+        rec[4] = (float)(0.5 * sqrt(r2) / sqrt(y2) + 0.5 * r1 / y1);           // an empty mask: 0 / 0, as the torch expression
+        rec[5] = r2 > 0.0 ? (float)(1.0 / (2.0 * sqrt(r2) * sqrt(y2))) : 0.f;  // the 2-norm's subgradient at r = 0 is 0 (as torch's norm backward)
+        rec[6] = (float)(1.0 / (2.0 * y1));
+        rec[7] = 0.f;
+    }
+}
+}  // namespace cine
+
+extern "C" size_t cine_kspace_loss_ws_bytes(int b, int t, int c, int h, int w) {
+    if (h == 1 && w > 0 && w % col_lines(h) == 1) return 0;       // a one-point tile cannot hold its slot (loss_slot)
+    return cine_image_dc_general_ws_bytes(b, t, c, h, w);
+}
+
+static int kspace_loss_check(const char* what, int b, int t, int c, int h, int w, size_t ws_bytes) {
+    CINE_REQUIRE(b > 0 && t > 0 && c > 0 && c <= 32768 && h > 0 && w > 0, CINE_EINVAL, "%s: bad sizes", what);
+    CINE_REQUIRE((long)b * t <= 65535, CINE_EUNSUPPORTED, "%s: b*t > 65535", what);
+    if (int e = check_n(h, what)) return e;
+    if (int e = check_n(w, what)) return e;
+    const size_t need = cine_kspace_loss_ws_bytes(b, t, c, h, w);
+    CINE_REQUIRE(need > 0, CINE_EUNSUPPORTED, "%s: h == 1 with a last column tile of one point (w %% %d == 1) is not supported", what, col_lines(h));
+    CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
+    return CINE_OK;
+}
+
+extern "C" int cine_kspace_loss(const float* img, const float* sens, const float* kspace, const uint8_t* mask, float* rec,
+                                int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream) {
+    const char* what = "cine_kspace_loss";
+    CINE_REQUIRE(img && sens && kspace && mask && rec && ws, CINE_EINVAL, "%s: null pointer", what);
+    CINE_REQUIRE(rec != img && rec != sens && rec != kspace && (const void*)rec != (const void*)mask && (const void*)rec != ws &&
+                 ws != (const void*)img && ws != (const void*)sens && ws != (const void*)kspace && ws != (const void*)mask,
+                 CINE_EINVAL, "%s: rec and ws must not alias an input or each other", what);
+    if (int e = kspace_loss_check(what, b, t, c, h, w, ws_bytes)) return e;
+    hipStream_t st = as_stream(stream);
+    RowArgs r; dim3 rgrid;
+    ColExtra x; x.kref = kspace;
+    if (int e = general_expand_weight<POST_LOSS>(img, sens, mask, nullptr, 0.f, 0.f, reinterpret_cast<cf*>(ws), b, t, c, h, w, r, rgrid, st, x))
+        return e;
+    ProfScope prof(F_MISC, st);
+    hipLaunchKernelGGL(kspace_loss_final_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<cf*>(ws), (long)b * t * c, h, w,
+                       col_lines(h), rec);
+    return check_launch("kspace_loss_final_kernel");
+}
+
+extern "C" int cine_kspace_loss_grad(const float* img, const float* sens, const float* kspace, const uint8_t* mask, const float* rec,
+                                     const float* gloss, float* gimg, float* gsens_part, int b, int t, int c, int h, int w,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    const char* what = "cine_kspace_loss_grad";
+    CINE_REQUIRE(img && sens && kspace && mask && rec && gloss && ws && (gimg || gsens_part), CINE_EINVAL, "%s: null pointer", what);
+    for (float* o : {gimg, gsens_part}) {
+        if (!o) continue;
+        CINE_REQUIRE(o != img && o != sens && o != kspace && (const void*)o != (const void*)mask && o != rec && o != gloss &&
+                     (const void*)o != ws, CINE_EINVAL, "%s: an output must not alias an input or ws", what);
+    }
+    CINE_REQUIRE(gimg != gsens_part, CINE_EINVAL, "%s: gimg and gsens_part must differ", what);
+    CINE_REQUIRE(ws != (const void*)img && ws != (const void*)sens && ws != (const void*)kspace && ws != (const void*)mask &&
+                 ws != (const void*)rec && ws != (const void*)gloss, CINE_EINVAL, "%s: ws must not alias an input", what);
+    if (int e = kspace_loss_check(what, b, t, c, h, w, ws_bytes)) return e;
+    hipStream_t st = as_stream(stream);
+    RowArgs r; dim3 rgrid;
+    ColExtra x; x.kref = kspace; x.rec = rec; x.gscale = gloss;
+    if (int e = general_expand_weight<POST_LOSSG>(img, sens, mask, nullptr, 0.f, 0.f, reinterpret_cast<cf*>(ws), b, t, c, h, w, r, rgrid, st, x))
+        return e;
+    if (gimg) {
+        RowArgs rr = r;
+        rr.sens = reinterpret_cast<const cf*>(sens); rr.out = reinterpret_cast<cf*>(gimg); rr.out_abs = gimg;
+        if (int e = launch_row<PRE_NONE, RPOST_REDUCE>(rr, rgrid, true, st)) return e;
+    }
+    if (gsens_part) {
+        r.out = reinterpret_cast<cf*>(gsens_part); r.img = reinterpret_cast<const cf*>(img);
+        if (int e = launch_row<PRE_NONE, RPOST_MULC>(r, rgrid, true, st)) return e;
+    }
+    return CINE_OK;
 }

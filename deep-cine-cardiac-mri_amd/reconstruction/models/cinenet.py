@@ -149,7 +149,9 @@ class CineNet(nn.Module):
         self.cascades = nn.ModuleList(
             [CineNetBlock(self.model, CG_iters, dynamic_type, weight_sharing) for _ in range(num_cascades)])
 
-    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor) -> torch.Tensor:
+    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
+        """``output="complex"``: the (b, t, h, w, 2) image in front of the final magnitude (``ops.complex_output``)."""
+        cplx = ops.complex_output(output)
         mask = ops.as_mask_u8(mask, masked_kspace)          # any numeric 0 / 1 mask that broadcasts, like the reference
         if ag.grad_mode(self):               # k-space and maps are data: the graph starts at the first regulariser
             with torch.no_grad():
@@ -157,14 +159,14 @@ class CineNet(nn.Module):
                 image_ref = image_pred.clone()
             for cascade in self.cascades:
                 image_pred = cascade(image_pred, image_ref, mask, sens_maps)
-            return ag.AbsFn.apply(image_pred.squeeze(2))
+            return image_pred.squeeze(2) if cplx else ag.AbsFn.apply(image_pred.squeeze(2))
         with torch.no_grad():
-            return self._forward_infer(masked_kspace, mask, sens_maps)
+            return self._forward_infer(masked_kspace, mask, sens_maps, cplx)
 
-    def _forward_infer(self, masked_kspace, mask, sens_maps):
+    def _forward_infer(self, masked_kspace, mask, sens_maps, cplx=False):
         image_pred = ops.sens_reduce(masked_kspace, sens_maps)
         image_ref = image_pred.clone()
         tiled = ops.sens_tile_pack(sens_maps)          # once per forward: 42 applications of the normal operator read it (6 cascades x (1 + 6 CG iterations))
         for cascade in self.cascades:
             image_pred = cascade(image_pred, image_ref, mask, sens_maps, tiled)
-        return ops.complex_abs(image_pred.squeeze(2))
+        return image_pred.squeeze(2) if cplx else ops.complex_abs(image_pred.squeeze(2))

@@ -22,14 +22,16 @@ class CineNet_RNN(CRNNBody):
     HOperator = CineNetBlock.HOperator
     ConjGrad = CineNetBlock.ConjGrad
 
-    def forward(self, ref_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor) -> torch.Tensor:
+    def forward(self, ref_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
+        """``output="complex"``: the (b, t, h, w, 2) image in front of the final magnitude (``ops.complex_output``)."""
+        cplx = ops.complex_output(output)
         mask = ops.as_mask_u8(mask, ref_kspace)          # any numeric 0 / 1 mask; broadcast along batch / time like the reference
         if ag.grad_mode(self):
-            return self._forward_train(ref_kspace, mask, sens_maps)
+            return self._forward_train(ref_kspace, mask, sens_maps, cplx)
         with torch.no_grad():
-            return self._forward_infer(ref_kspace, mask, sens_maps)
+            return self._forward_infer(ref_kspace, mask, sens_maps, cplx)
 
-    def _forward_train(self, ref_kspace, mask, sens_maps):
+    def _forward_train(self, ref_kspace, mask, sens_maps, cplx=False):
         """``_forward_infer`` as an autograd graph (k-space and maps are data): CRNN body through the HIP backward kernels, the
         conjugate-gradient solve through its adjoint recurrence (detached step sizes, recurrent_cinenet.py:113-123), lambda through both."""
         b, t, _, h, w, _ = ref_kspace.shape
@@ -45,9 +47,9 @@ class CineNet_RNN(CRNNBody):
             x = out.permute(0, 2, 3, 1).reshape(1, t, 1, h, w, 2)
             rhs = ag.AxpbyLamFn.apply(x_ref, x, self.lambda_reg)
             img = ag.ConjGradFn.apply(x, rhs, self.lambda_reg, mask, sens_maps, self.CG_iters)
-        return ag.AbsFn.apply(img.squeeze(2))
+        return img.squeeze(2) if cplx else ag.AbsFn.apply(img.squeeze(2))
 
-    def _forward_infer(self, ref_kspace, mask, sens_maps):
+    def _forward_infer(self, ref_kspace, mask, sens_maps, cplx=False):
         b, t, _, h, w, _ = ref_kspace.shape
         if b != 1:
             raise NotImplementedError("the CRNN models assume batch 1, like the reference")
@@ -61,4 +63,4 @@ class CineNet_RNN(CRNNBody):
             x = ops.normunet_unpack(out, None, h, w).view(1, t, 1, h, w, 2)
             rhs = ops.axpby_dev(x_ref, x, lambda_reg=self.lambda_reg)
             img = self.ConjGrad(x, rhs, mask, sens_maps, self.CG_iters, tiled)
-        return ops.complex_abs(img.squeeze(2))
+        return img.squeeze(2) if cplx else ops.complex_abs(img.squeeze(2))

@@ -31,14 +31,16 @@ class XPDNet_RNN(CRNNBody):
     def measurements_residual(concat_kspace: torch.Tensor) -> torch.Tensor:
         return concat_kspace[..., [0, 2]] - concat_kspace[..., [1, 3]]
 
-    def forward(self, ref_kspace: torch.Tensor, mask: torch.Tensor, acs=None) -> torch.Tensor:
+    def forward(self, ref_kspace: torch.Tensor, mask: torch.Tensor, acs=None, output: str = "magnitude") -> torch.Tensor:
+        """``output="complex"``: the (b, t, h, w, 2) image in front of the final magnitude (``ops.complex_output``)."""
+        cplx = ops.complex_output(output)
         mask = ops.as_mask_u8(mask, ref_kspace)          # any numeric 0 / 1 mask; broadcast along batch / time like the reference
         if ag.grad_mode(self):
-            return self._forward_train(ref_kspace, mask, acs)
+            return self._forward_train(ref_kspace, mask, acs, cplx)
         with torch.no_grad():
-            return self._forward_infer(ref_kspace, mask, acs)
+            return self._forward_infer(ref_kspace, mask, acs, cplx)
 
-    def _forward_train(self, ref_kspace, mask, acs):
+    def _forward_train(self, ref_kspace, mask, acs, cplx=False):
         """The chain of ``_forward_infer`` as an autograd graph: sensitivity network, K step + masked backward operator (image space for the
         primal-only model; forward / k-space net / backward Functions with the dual buffer: cine_hip/dc.py), CRNN body on the buffer planes."""
         n = self.i_buffer_size
@@ -56,9 +58,10 @@ class XPDNet_RNN(CRNNBody):
             planes = cat.view(t, h, w, 2 * (n + 1)).permute(0, 3, 1, 2).contiguous()                       # (t, 2(n+1), h, w)
             out, state = self.body_train(planes.view(t, 1, 2 * (n + 1), h, w), state, torch.cat([planes[:, :n], planes[:, n + 1:2 * n + 1]], dim=1))
             image_buffer = out.permute(0, 2, 3, 1).reshape(1, t, 1, h, w, 2 * n)
-        return ag.AbsFn.apply(pick(image_buffer).squeeze(2))
+        image = pick(image_buffer).squeeze(2)
+        return image if cplx else ag.AbsFn.apply(image)
 
-    def _forward_infer(self, ref_kspace, mask, acs):
+    def _forward_infer(self, ref_kspace, mask, acs, cplx=False):
         n = self.i_buffer_size
         b, t, _, h, w, _ = ref_kspace.shape
         if b != 1:
@@ -76,4 +79,5 @@ class XPDNet_RNN(CRNNBody):
             planes = ops.chanlast_to_planes(cat.view(t, h, w, 2 * (n + 1)))                 # (t, 2(n+1), h, w)
             out, state = self.body(planes.view(t, 1, 2 * (n + 1), h, w), state, planes.index_select(1, keep))
             image_buffer = ops.planes_to_chanlast(out, h, w).view(1, t, 1, h, w, 2 * n)
-        return ops.complex_abs(ops.extract_complex(image_buffer, 0, n).squeeze(2))
+        image = ops.extract_complex(image_buffer, 0, n).squeeze(2)
+        return image if cplx else ops.complex_abs(image)

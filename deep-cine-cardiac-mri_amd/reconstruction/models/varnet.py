@@ -142,25 +142,27 @@ class VarNet(nn.Module):
             [VarNetBlock(self.model, dynamic_type, weight_sharing) for _ in range(num_cascades)])
 
     def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor,
-                sens_maps: Optional[torch.Tensor] = None, acs=None) -> torch.Tensor:
-        """(b,t,c,h,w,2), (b,t,1,h,1,1) uint8 -> (b,t,h,w) magnitude.  ``sens_maps`` (optional,
+                sens_maps: Optional[torch.Tensor] = None, acs=None, output: str = "magnitude") -> torch.Tensor:
+        """(b,t,c,h,w,2), (b,t,1,h,1,1) uint8 -> (b,t,h,w) magnitude, or with ``output="complex"`` the (b,t,h,w,2) image in front of it
+        (``ops.complex_output``).  ``sens_maps`` (optional,
         (b,1,c,h,w,2)) bypasses the sens-map network; ``acs`` = (pad, n_low) skips the host
         read-back of the mask (needed inside hipGraph capture).  Masks of another dtype (the reference's
         apply_mask returns a float mask) are converted once."""
         mask = ops.as_mask_u8(mask, masked_kspace)         # row mask (b,t,1,h,1,1), or general mask (b,t,1,h,w,1) when it varies along w
+        cplx = ops.complex_output(output)
         if ag.grad_mode(self):
-            return self._forward_train(masked_kspace, mask, sens_maps, acs)
+            return self._forward_train(masked_kspace, mask, sens_maps, acs, cplx)
         with torch.no_grad():
-            return self._forward_infer(masked_kspace, mask, sens_maps, acs)
+            return self._forward_infer(masked_kspace, mask, sens_maps, acs, cplx)
 
-    def _forward_train(self, masked_kspace, mask, sens_maps, acs):
+    def _forward_train(self, masked_kspace, mask, sens_maps, acs, cplx=False):
         """The image-space cascade chain of ``_forward_infer`` as an autograd graph (reference varnet.py:143-151)."""
-        return self._cascade_chain(masked_kspace, mask, sens_maps, acs, True)
+        return self._cascade_chain(masked_kspace, mask, sens_maps, acs, True, cplx)
 
-    def _forward_infer(self, masked_kspace, mask, sens_maps, acs):
-        return self._cascade_chain(masked_kspace, mask, sens_maps, acs, False)
+    def _forward_infer(self, masked_kspace, mask, sens_maps, acs, cplx=False):
+        return self._cascade_chain(masked_kspace, mask, sens_maps, acs, False, cplx)
 
-    def _cascade_chain(self, masked_kspace, mask, sens_maps, acs, train):
+    def _cascade_chain(self, masked_kspace, mask, sens_maps, acs, train, cplx=False):
         # Cascade chain on the coil-combined image.  The k-space between two cascades (reference varnet.py:147-148) is consumed only by
         # the next sens_reduce, so each step is reduce(DC(expand(x))); with a row mask the DC commutes with the transform along w and
         #   reduce(DC(expand(x))) = sum_c conj(S_c) IFFT_h[(m ? 1/(1+v) : 1) FFT_h(S_c x)] + v/(1+v) reduce(m k_ref)
@@ -170,9 +172,11 @@ class VarNet(nn.Module):
             sens_maps = self.sens_net(masked_kspace, mask, acs)
         acq = Acquisition(masked_kspace, mask, sens_maps, train)
         image = acq.image()                                # first cascade's sens_reduce(masked_kspace)
-        last = None if train else len(self.cascades) - 1   # the last DC step of the inference chain writes the magnitude itself
+        last = None if train or cplx else len(self.cascades) - 1   # the last DC step of the inference chain writes the magnitude itself
         for i, cascade in enumerate(self.cascades):
             image = acq.soft_dc(cascade.regularise(image), cascade.lambda_reg, magnitude=(i == last))
+        if cplx:
+            return image.squeeze(2)
         if train:
             return ag.AbsFn.apply(image.squeeze(2))
         return image if self.cascades else ops.complex_abs(image.squeeze(2))

@@ -161,14 +161,16 @@ class XPDNet(nn.Module):
     def measurements_residual(concat_kspace: torch.Tensor) -> torch.Tensor:
         return concat_kspace[..., [0, 2]] - concat_kspace[..., [1, 3]]
 
-    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, acs=None) -> torch.Tensor:
+    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, acs=None, output: str = "magnitude") -> torch.Tensor:
+        """``output="complex"``: the (b, t, h, w, 2) image in front of the final magnitude (``ops.complex_output``)."""
+        cplx = ops.complex_output(output)
         mask = ops.as_mask_u8(mask, masked_kspace)          # any numeric 0 / 1 mask; broadcast along batch / time like the reference
         if ag.grad_mode(self):
-            return self._forward_train(masked_kspace, mask, acs)
+            return self._forward_train(masked_kspace, mask, acs, cplx)
         with torch.no_grad():
-            return self._forward_infer(masked_kspace, mask, acs)
+            return self._forward_infer(masked_kspace, mask, acs, cplx)
 
-    def _forward_train(self, masked_kspace, mask, acs):
+    def _forward_train(self, masked_kspace, mask, acs, cplx=False):
         """The chain of ``_forward_infer`` (reference xpdnet.py:301-326) as an autograd graph.  Primal-only: the K step + masked backward
         operator is one image-space Function; with the KSpaceCNN dual net the k-space buffer is a learned quantity and the forward / backward
         operators are Functions with k-space gradients (FFT2 is unitary: each adjoint is the other operator)."""
@@ -182,9 +184,10 @@ class XPDNet(nn.Module):
         for i_domain in range(1, len(self.domain_sequence), 2):
             backward_img, kbuf = acq.k_step(pick(image_buffer), kbuf, self.kspace_net[i_domain // 2])
             image_buffer = self.cascades[i_domain].regularise(i_domain, image_buffer, backward_img)
-        return ag.AbsFn.apply(pick(image_buffer).squeeze(2))                      # (:321-326)
+        image = pick(image_buffer).squeeze(2)
+        return image if cplx else ag.AbsFn.apply(image)                           # (:321-326)
 
-    def _forward_infer(self, masked_kspace, mask, acs):
+    def _forward_infer(self, masked_kspace, mask, acs, cplx=False):
         n = self.i_buffer_size
         acq = Acquisition(masked_kspace, mask, self.sens_net(masked_kspace, mask, acs))
         image_buffer = ops.repeat_complex(acq.image(), n)                         # unmasked backward op (:303), (:307)
@@ -193,4 +196,5 @@ class XPDNet(nn.Module):
             x0 = ops.extract_complex(image_buffer, 0, n)                          # channel 0 of the buffer (:128)
             backward_img, kbuf = acq.k_step(x0, kbuf, self.kspace_net[i_domain // 2])
             image_buffer = self.cascades[i_domain].regularise(i_domain, image_buffer, backward_img)
-        return ops.complex_abs(ops.extract_complex(image_buffer, 0, n).squeeze(2))      # (:321-326)
+        image = ops.extract_complex(image_buffer, 0, n).squeeze(2)
+        return image if cplx else ops.complex_abs(image)                          # (:321-326)

@@ -859,6 +859,31 @@ int cine_image_dc_general_sens_grad(const float* img, const float* gout, const f
                                     const float* lambda_dev, float w_sampled, float w_unsampled,
                                     float* part, int b, int t, int c, int h, int w,
                                     void* ws, size_t ws_bytes, void* stream);
+/* Self-supervised k-space loss on held-out samples (SSDU, Yaman et al., MRM 2020; no reference counterpart: the reference trains against a
+ * fully sampled target only).  img (b, t, h, w, 2), sens (b, c, h, w, 2), kspace (b, t, c, h, w, 2), mask uint8 (b, t, h, w): with
+ * u = FFT2(S_c img) (sens_expand, varnet.py:181-185), r = mask (u - kspace), v = mask kspace,
+ *     L = 1/2 ||r||_2 / ||v||_2 + 1/2 ||r||_1 / ||v||_1,
+ * both norms over every real component of the batch (||.||_1 = sum |re| + |im|, sign(0) = 0).  cine_kspace_loss takes the first two stages of
+ * cine_image_dc_general (S x -> row FFT -> ws, column FFT) and leaves, per column workgroup, four partial sums in ws (no atomics; the split
+ * depends on the shape only); a one-workgroup kernel adds them in a fixed order in float64 and writes rec (8 floats, device):
+ * sum r^2, sum |r|_1, sum kspace^2, sum |kspace|_1 (on the mask), L, a = 1 / (2 ||r||_2 ||v||_2) (0 where r = 0), b = 1 / (2 ||v||_1), 0.
+ * Results are bit-identical from call to call; an empty mask gives the IEEE result of the expression (no host check).  kspace is used at
+ * the mask's points only: what it holds elsewhere (NaN included) changes no output (off the mask the h == 200 kernels re-read one cached
+ * element per image and discard it, the others read nothing).  cine_kspace_loss_grad recomputes both stages (nothing coil-wise is kept), forms g_k = *gloss mask (a r +
+ * b sign(r)) with a, b read from rec, and continues as cine_image_dc_general: column IFFT, then gimg (b, t, h, w, 2) = sum_c conj(S_c)
+ * IFFT_w(.) and / or gsens_part (b, t, c, h, w, 2) = IFFT2(g_k)_c conj(img), the maps' gradient per frame (add the frames with
+ * cine_coil_accum(NULL, part, ...)); either output may be NULL, not both.  Workspace: cine_kspace_loss_ws_bytes() =
+ * cine_image_dc_general_ws_bytes().  h, w: any length cine_fft_line_supported() accepts (CINE_EUNSUPPORTED otherwise, and for h == 1 with
+ * w % 8 == 1, whose last column tile cannot hold its partial sums: the size function returns 0 there); c <= 32768 (CINE_EINVAL),
+ * b*t <= 65535 (CINE_EUNSUPPORTED); rec, ws and the outputs must not alias an input or each other (CINE_EINVAL); a short workspace is
+ * CINE_EWORKSPACE.  Every argument is checked before the first launch; no allocation, no synchronisation, capturable.
+ * cine_diag_counter(32) counts the column-pass launches of both entry points. */
+size_t cine_kspace_loss_ws_bytes(int b, int t, int c, int h, int w);
+int cine_kspace_loss(const float* img, const float* sens, const float* kspace, const uint8_t* mask, float* rec,
+                     int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
+int cine_kspace_loss_grad(const float* img, const float* sens, const float* kspace, const uint8_t* mask, const float* rec,
+                          const float* gloss, float* gimg, float* gsens_part, int b, int t, int c, int h, int w,
+                          void* ws, size_t ws_bytes, void* stream);
 /* gs (b, c, h, w, 2) (+)= sum_t conj(g[b, t]) z[b, t, c]: gradient of sens_reduce's coil sum sum_c conj(S_c) z_c (varnet.py:187-194)
  * with respect to S; z (b, t, c, h, w, 2) are the coil images.  g == NULL: gs (+)= sum_t z.  accumulate == 0 overwrites gs. */
 int cine_coil_accum(const float* g, const float* z, float* gs, int b, int t, int c, int h, int w, int accumulate, void* stream);
@@ -897,8 +922,8 @@ int cine_profile_begin(void);
  * 10 the general kernel's two-set pair form, 11 the general kernel with vectorised staging, 12 the general kernel with element-wise
  * staging -- input-gradient launches on the general kernel count in 10 .. 12 too; 13 / 14 cine_pool3d_act on its float4 / scalar
  * kernel; 15 column-pass launches that weight by a mask plane: cine_image_dc_general / cine_normal_op_general /
- * cine_image_dc_general_sens_grad).  reset != 0 returns the count and zeroes it;
- * -1 for an unknown counter. */
+ * cine_image_dc_general_sens_grad; 32 column-pass launches of cine_kspace_loss / cine_kspace_loss_grad -- counters added after the
+ * first block take ids from 32 on, 16 .. 31 stay unknown).  reset != 0 returns the count and zeroes it; -1 for an unknown counter. */
 long cine_diag_counter(int which, int reset);
 /* Diagnostics: a one-workgroup kernel that runs for `microseconds` (1 .. 100 000; clock-bounded AND iteration-bounded: it always ends).  The
  * binding times two of them on two streams to learn whether the streams share a hardware queue (GPU_MAX_HW_QUEUES): streams on one queue run
