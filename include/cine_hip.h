@@ -28,6 +28,13 @@
  *     one of them flips the diagnostic mask and uses another slope.
  *   - the library creates no streams.  The two backward entry points that overlap weight gradients with the input-gradient
  *     chain (cine_unet2d_backward, cine_unet3d_backward, cine_mwcnn_backward) create and destroy hipEvents (no timing) to order the two streams.
+ *
+ * The Python binding is generated from this file
+ *   cine_hip/_lib.py parses every prototype below into its ctypes signature; there is no second table to keep in step.  So the
+ *   declarations keep to one style, and the parser refuses anything else: every statement is a prototype `T cine_name(args);`,
+ *   by-value arguments and returns are int, long, float, double or size_t (a leading const is allowed), every pointer argument is
+ *   opaque to the binding (it passes an address, whatever the pointee type says), and the only pointer return is const char*.
+ *   No other by-value type (uint8_t, unsigned, int64_t, bool, structs), no char* argument, no function pointer, array or `...`.
  */
 #ifndef CINE_HIP_H
 #define CINE_HIP_H
