@@ -34,4 +34,14 @@ _hw_queue_default()
 
 from . import synth  # noqa: F401,E402  (host-only, numpy)
 
-__all__ = ["synth"]
+__all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense"]
+
+_CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense")
+
+
+def __getattr__(name):
+    # the weight-free baseline (cine_hip.classical), imported on first use: the package import itself stays host-only
+    if name in _CLASSICAL:
+        from . import classical
+        return getattr(classical, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -662,6 +662,82 @@ def normal_op(img: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_
     return out
 
 
+KT_REC = 4              # floats of one record row of kt_prox / kt_fista: sum |xnew - xprev|^2, sum |xnew|^2, sum_f w_f |F_t xnew|, 0
+KT_MAX_FRAMES = 64      # 2 <= t <= 64, as xfyf_pack
+
+
+def kt_prox_pixels() -> int:
+    """Pixels per workgroup of cine_kt_prox's kernel: the tile the shape sweeps of the tests place their sizes around."""
+    return int(lib().cine_kt_prox_pixels())
+
+
+def _kt_scalar(v: torch.Tensor, name: str) -> torch.Tensor:
+    v = _dev(v, name)
+    if v.numel() != 1:
+        raise ValueError(f"{name}: expected one float on the device, got shape {tuple(v.shape)}")
+    return v
+
+
+def kt_prox(z: torch.Tensor, g: torch.Tensor, xprev: torch.Tensor, step: torch.Tensor, thresh: torch.Tensor, beta: float = 0.0,
+            penalise_dc: bool = True, record: bool = False, xnew: Optional[torch.Tensor] = None, znew: Optional[torch.Tensor] = None):
+    """cine_kt_prox, the second half of one k-t FISTA iteration in one launch: v = z - step g, xnew = F_t^H soft(F_t v, step thresh w_f),
+    znew = xnew + beta (xnew - xprev).  z, g, xprev: (b, t, [1,] h, w, 2); ``step``, ``thresh``: one device float each.  ``xnew`` / ``znew``:
+    where to write (``znew`` may be ``z`` and ``xnew`` may be ``xprev``: in place); new tensors of z's shape by default.
+    Returns (xnew, znew), with ``record`` (xnew, znew, rec) with rec the ``KT_REC`` device floats of the record."""
+    _pair(z)
+    z = _dev(z, "z"); g = _dev(g, "g"); xprev = _dev(xprev, "xprev")
+    step = _kt_scalar(step, "step"); thresh = _kt_scalar(thresh, "thresh")
+    if z.dim() not in (5, 6) or (z.dim() == 6 and z.shape[2] != 1):
+        raise ValueError(f"kt_prox: z {tuple(z.shape)} is not (b, t, [1,] h, w, 2)")
+    b, t, h, w = z.shape[0], z.shape[1], z.shape[-3], z.shape[-2]
+    if g.numel() != z.numel() or xprev.numel() != z.numel():
+        raise ValueError(f"kt_prox: g {tuple(g.shape)} / xprev {tuple(xprev.shape)} do not match z {tuple(z.shape)}")
+    for o, name in ((xnew, "xnew"), (znew, "znew")):
+        if o is not None and (not o.is_cuda or o.dtype != z.dtype or not o.is_contiguous() or o.numel() != z.numel()):
+            raise CineHipError(f"kt_prox: {name} must be a contiguous float32 GPU tensor of z's size")
+    xnew = torch.empty_like(z) if xnew is None else xnew
+    znew = torch.empty_like(z) if znew is None else znew
+    rec = ws = None
+    nbytes = 0
+    if record:
+        rec = torch.empty(KT_REC, device=z.device, dtype=torch.float32)
+        nbytes = lib().cine_kt_prox_ws_bytes(b, t, h, w)
+        ws = _general_ws(nbytes, z.device)
+    check(lib().cine_kt_prox(z.data_ptr(), g.data_ptr(), xprev.data_ptr(), step.data_ptr(), thresh.data_ptr(), float(beta), int(bool(penalise_dc)),
+                             xnew.data_ptr(), znew.data_ptr(), _p(rec), b, t, h, w, _p(ws), nbytes, _stream()), "cine_kt_prox")
+    return (xnew, znew, rec) if record else (xnew, znew)
+
+
+def kt_fista(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: torch.Tensor, thresh: torch.Tensor, iters: int,
+             penalise_dc: bool = True, sens_tiled: Optional[torch.Tensor] = None, record: bool = False):
+    """cine_kt_fista: ``iters`` FISTA iterations of k-t SPARSE-SENSE from x_0 = zf = A^H M y in one C call (``image_dc`` with weights
+    (1, 0, -1), then ``kt_prox``, per iteration; the momentum of ``classical.fista_momentum``).  zf (b, t, [1,] h, w, 2); sens (b, 1, c, h, w, 2);
+    ``mask``: either layout of ``as_mask_u8``; ``step``, ``thresh``: one device float each.  Returns x in zf's shape, with ``record``
+    (x, rec) with rec (iters, ``KT_REC``)."""
+    _pair(zf); _pair(sens)
+    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
+    step = _kt_scalar(step, "step"); thresh = _kt_scalar(thresh, "thresh")
+    if sens.dim() != 6:
+        raise ValueError(f"kt_fista: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
+    b, _, c, h, w, _ = sens.shape
+    t = zf.shape[1]
+    layout = mask_layout(mask, sens, t)
+    if zf.numel() != b * t * h * w * 2 or layout is None:
+        raise ValueError(f"kt_fista: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError(f"kt_fista: iters = {iters}")
+    mask_w = 1 if layout == "row" else w
+    x = torch.empty_like(zf)
+    rec = torch.empty((iters, KT_REC), device=zf.device, dtype=torch.float32) if record else None
+    nbytes = lib().cine_kt_fista_ws_bytes(b, t, c, h, w, mask_w, iters)
+    ws = _general_ws(nbytes, zf.device)
+    check(lib().cine_kt_fista(x.data_ptr(), zf.data_ptr(), sens.data_ptr(), _p(sens_tiled), mask.data_ptr(), mask_w, step.data_ptr(),
+                              thresh.data_ptr(), iters, int(bool(penalise_dc)), _p(rec), b, t, c, h, w, ws.data_ptr(), nbytes, _stream()),
+          "cine_kt_fista")
+    return (x, rec) if record else x
+
+
 def h_operator(x: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_reg: torch.Tensor,
                _hyb: Optional[torch.Tensor] = None, sens_tiled: Optional[torch.Tensor] = None, literal: bool = False) -> torch.Tensor:
     """CineNet's H = A^H M A + softplus(lambda) I (reference cinenet.py:121-133) for either mask layout: the one-kernel image-space

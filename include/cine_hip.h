@@ -913,6 +913,40 @@ int cine_ssim_loss_bwd(const float* x, const float* y, int t, int h, int w, int 
                        const void* ws, size_t ws_bytes, float* gx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * k-t SPARSE-SENSE: FISTA with a temporal-sparsity penalty (no reference counterpart: a reconstruction that needs no trained
+ * weights, the compressed-sensing baseline on the same operators)
+ * ------------------------------------------------------------------------------------------ */
+/* The second half of one proximal-gradient iteration, in one launch.  z, g, xprev, xnew, znew: (b, t, h, w, 2); g = A^H M A z - zf is the
+ * data term's gradient (cine_image_dc with weights (1, 0, -1)).  With F_t the centered ortho transform along t (cine_fft1c variant 0: the
+ * temporal DC bin is index t / 2) and soft(c, th) = c max(|c| - th, 0) / |c| (0 at c = 0):
+ *     v = z - (*step_dev) g;   xnew = F_t^H soft(F_t v, (*step_dev) (*thresh_dev) w_f);   znew = xnew + beta (xnew - xprev)
+ * w_f = 1, or with penalise_dc == 0, 0 at the DC bin.  step_dev, thresh_dev: one float each in device memory (nothing waits for the host).
+ * rec != NULL: 4 device floats = sum |xnew - xprev|^2, sum |xnew|^2, sum_f w_f |F_t xnew|, 0 -- per-workgroup partial sums in ws
+ * (cine_kt_prox_ws_bytes; ws may be NULL without rec), added in float64 in a fixed order by a second launch: the same bits on every call.
+ * A workgroup owns all frames of cine_kt_prox_pixels() consecutive pixels and reads before it writes: znew may alias z and xnew may alias
+ * xprev (z == xprev is fine too); any other aliasing of an output, and g == z or g == xprev, is CINE_EINVAL, as are null pointers and
+ * non-positive sizes.  2 <= t <= 64 and b <= 65535, else CINE_EUNSUPPORTED; a short workspace is CINE_EWORKSPACE.  Every argument is
+ * checked before the first launch; no allocation, no synchronisation, no atomics. */
+int cine_kt_prox_pixels(void);
+size_t cine_kt_prox_ws_bytes(int b, int t, int h, int w);
+int cine_kt_prox(const float* z, const float* g, const float* xprev, const float* step_dev, const float* thresh_dev,
+                 float beta, int penalise_dc, float* xnew, float* znew, float* rec,
+                 int b, int t, int h, int w, void* ws, size_t ws_bytes, void* stream);
+/* The whole solve in one call: x_0 = z_0 = zf, s_0 = 1, and for k = 0 .. iters - 1
+ *     g = A^H M A z_k - zf   (cine_image_dc_t for a row mask, mask_w == 1: mask (b, t, h); cine_image_dc_general for mask_w == w: (b, t, h, w))
+ *     (x_{k+1}, z_{k+1}) = cine_kt_prox(z_k, g, x_k, beta_k),   s_{k+1} = (1 + sqrt(1 + 4 s_k^2)) / 2,  beta_k = float((s_k - 1) / s_{k+1})
+ * with the momentum computed on the host in double.  x (out), zf: (b, t, h, w, 2); sens (b, c, h, w, 2); sens_tiled: cine_sens_tile_pack's
+ * copy or NULL (row masks, h == 200; same results).  rec: (iters, 4) device floats, one row of cine_kt_prox's record per iteration (all rows
+ * are added up in one launch at the end), or NULL.  x and rec equal, bit for bit, what the caller gets from the two entry points iterated by
+ * hand.  ws: cine_kt_fista_ws_bytes() = the operator's scratch, g, z and the partial sums.  iters >= 1, c > 0, mask_w in {1, w}, x / rec / ws
+ * aliasing nothing (CINE_EINVAL); t and b as cine_kt_prox; h, w, c: what the operator accepts -- it is called first and refuses before
+ * anything is launched. */
+size_t cine_kt_fista_ws_bytes(int b, int t, int c, int h, int w, int mask_w, int iters);
+int cine_kt_fista(float* x, const float* zf, const float* sens, const float* sens_tiled, const uint8_t* mask, int mask_w,
+                  const float* step_dev, const float* thresh_dev, int iters, int penalise_dc, float* rec,
+                  int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement aid (no reference counterpart; the reference only wraps time.time() around the
  * model call, traintest_scripts/run_inference.py:53-61)
  * ------------------------------------------------------------------------------------------ */
