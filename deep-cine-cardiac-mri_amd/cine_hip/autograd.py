@@ -280,6 +280,64 @@ def xfyf(image: torch.Tensor, xf: bool, wboth, wx, wy, norm: bool = True) -> tor
 
 
 # ------------------------------------------------------------------ MWCNN
+def mwcnn_forward_train(planes: torch.Tensor, w1: "ops.MwcnnWeights", w2: Optional["ops.MwcnnWeights"] = None, split: int = 0):
+    """cine_mwcnn_forward_train on (n, in_ch, h, w) planes: returns (y, workspace with the saved activations).  ``w2`` / ``split``: samples
+    [split, n) go through a second network of the same topology in the same launches.  The workspace remembers the weight sets with their
+    training keys and the slope applied, for ``mwcnn_backward``."""
+    net = w1.net
+    n, cin, h, wd = planes.shape
+    sets = (w1, w2) if w2 is not None and w2 is not w1 else (w1,)
+    L = lib()
+    need = L.cine_mwcnn_train_ws_bytes(n, h, wd, cin, net.out_chans, net.n_scales, w1.nf, w1.nc, net.first_conv_n_filters)
+    ws = torch.empty(max(need, 1), device=planes.device, dtype=torch.uint8)
+    y = torch.empty((n, net.out_chans, h, wd), device=planes.device, dtype=planes.dtype)
+    ws.cine_slope = ops.lrelu_slope()                # the backward pass differentiates the activation the forward pass applied
+    ws.cine_sets = sets + (None,) * (2 - len(sets)) + (int(split) if len(sets) == 2 else n,)
+    ws.cine_training_keys = tuple(wt.training_key() for wt in sets)
+    check(L.cine_mwcnn_forward_train(planes.data_ptr(), y.data_ptr(), w1.pointers(train=True), w2.pointers(train=True) if len(sets) == 2 else None,
+                                     ws.cine_sets[2], n, h, wd, cin, net.out_chans, net.n_scales, w1.nf, w1.nc, net.n_first_convs,
+                                     net.first_conv_n_filters, int(net.res), ws.cine_slope, ws.data_ptr(), ws.numel(), _stream()), "cine_mwcnn_forward_train")
+    return y, ws
+
+
+def mwcnn_check_fresh(fwd_ws: torch.Tensor) -> None:
+    """Host-side, before the first launch of a backward pass: the saved activations of ``fwd_ws`` still belong to the parameters' values."""
+    for wt, key in zip(fwd_ws.cine_sets, fwd_ws.cine_training_keys):
+        wt.check_training_key(key, "cine_mwcnn_backward")
+
+
+def mwcnn_backward(planes: torch.Tensor, gy: torch.Tensor, fwd_ws: torch.Tensor, need_gx: bool = True):
+    """cine_mwcnn_backward for a ``mwcnn_forward_train`` call (checked by ``mwcnn_check_fresh``): returns (gx | None, {id(parameter): gradient}),
+    the sets' gradients of a shared parameter summed."""
+    w1, w2, split = fwd_ws.cine_sets
+    net = w1.net
+    n, cin, h, wd = planes.shape
+    L = lib()
+    need = L.cine_mwcnn_backward_ws_bytes(n, h, wd, cin, net.out_chans, net.n_scales, w1.nf, w1.nc, net.first_conv_n_filters)
+    ws = torch.empty(need, device=planes.device, dtype=torch.uint8)
+    plists = [wt.param_list() for wt in (w1, w2) if wt is not None]
+    grads = _zero_grads(plists, planes.device)
+    gptr = [(ctypes.c_void_p * len(gl))(*[g.data_ptr() for g in gl]) for gl in grads] + [None]
+    gx = torch.empty_like(planes) if need_gx else None
+    check(L.cine_mwcnn_backward(planes.data_ptr(), gy.data_ptr(), w1.dgrad_pointers(), w2.dgrad_pointers() if w2 is not None else None, gptr[0], gptr[1],
+                                split, n, h, wd, cin, net.out_chans, net.n_scales, w1.nf, w1.nc, net.first_conv_n_filters, fwd_ws.cine_slope,
+                                fwd_ws.data_ptr(), fwd_ws.numel(), ws.data_ptr(), ws.numel(), _p(gx), _stream()), "cine_mwcnn_backward")
+    out = {}
+    for pl, gl in zip(plists, grads):
+        for p, g in zip(pl, gl):
+            out[id(p)] = g if id(p) not in out else out[id(p)] + g
+    return gx, out
+
+
+def _mwcnn_params(*sets):
+    """The distinct parameters of the weight sets, in order (what the Functions below take for autograd's bookkeeping)."""
+    seen = {}
+    for wt in sets:
+        for p in wt.distinct_params() if wt is not None else ():
+            seen.setdefault(id(p), p)
+    return list(seen.values())
+
+
 @_masked
 class MwcnnFn(Function):
     """MWCNN.forward (denoisers/mwcnn.py:135-179) on (n, in_ch, h, w) planes.  ``w2`` / ``split``: samples [split, n) go through a second
@@ -288,66 +346,25 @@ class MwcnnFn(Function):
     @staticmethod
     def forward(ctx, x, w, w2, split, *params):
         x = ops._dev(x, "mwcnn input")
-        net = w.net
-        n, cin, h, wd = x.shape
-        two = w2 is not None and w2 is not w
-        L = lib()
-        need = L.cine_mwcnn_train_ws_bytes(n, h, wd, cin, net.out_chans, net.n_scales, w.nf, w.nc, net.first_conv_n_filters)
-        ws = torch.empty(max(need, 1), device=x.device, dtype=torch.uint8)
-        y = torch.empty((n, net.out_chans, h, wd), device=x.device, dtype=x.dtype)
-        check(L.cine_mwcnn_forward_train(x.data_ptr(), y.data_ptr(), w.pointers(train=True), w2.pointers(train=True) if two else None, int(split) if two else n,
-                                         n, h, wd, cin, net.out_chans, net.n_scales, w.nf, w.nc, net.n_first_convs, net.first_conv_n_filters,
-                                         int(net.res), ops.lrelu_slope(), ws.data_ptr(), ws.numel(), _stream()), "cine_mwcnn_forward_train")
-        ctx.slope = ops.lrelu_slope()
-        ctx.cfg = (w, w2 if two else None, int(split) if two else n)
-        ctx.keys = tuple(tuple((p.data_ptr(), p._version) for p in wt.param_list()) for wt in ((w, w2) if two else (w,)))
-        ctx.ws, ctx.params = ws, params
+        y, ctx.ws = mwcnn_forward_train(x, w, w2, split)
+        ctx.params = params
         ctx.save_for_backward(x)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
-        w, w2, split = ctx.cfg
-        net = w.net
-        for wt, key in zip((w, w2) if w2 is not None else (w,), ctx.keys):
-            if key != tuple((p.data_ptr(), p._version) for p in wt.param_list()):
-                raise RuntimeError("cine_mwcnn_backward: an MWCNN parameter was modified between the forward and the backward pass; "
-                                   "the saved activations belong to the old weights")
+        mwcnn_check_fresh(ctx.ws)
         gy = ops._dev(_c(gy), "mwcnn output gradient")
-        n, cin, h, wd = x.shape
-        L = lib()
-        need = L.cine_mwcnn_backward_ws_bytes(n, h, wd, cin, net.out_chans, net.n_scales, w.nf, w.nc, net.first_conv_n_filters)
-        ws = torch.empty(need, device=x.device, dtype=torch.uint8)
-
-        def grads_of(wt):
-            pl = wt.param_list()
-            gl = _zero_grads([pl], x.device)[0]
-            return pl, gl, (ctypes.c_void_p * len(gl))(*[g.data_ptr() for g in gl])
-        p1, g1, gp1 = grads_of(w)
-        p2, g2, gp2 = grads_of(w2) if w2 is not None else (None, None, None)
-        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         _use_side_stream(x.device)
-        check(L.cine_mwcnn_backward(x.data_ptr(), gy.data_ptr(), w.dgrad_pointers(), w2.dgrad_pointers() if w2 is not None else None, gp1, gp2,
-                                    split, n, h, wd, cin, net.out_chans, net.n_scales, w.nf, w.nc, net.first_conv_n_filters, ctx.slope,
-                                    ctx.ws.data_ptr(), ctx.ws.numel(), ws.data_ptr(), ws.numel(), _p(gx), _stream()), "cine_mwcnn_backward")
-        out = {}
-        for pl, gl in ((p1, g1),) + (((p2, g2),) if w2 is not None else ()):
-            for p, g in zip(pl, gl):
-                out[id(p)] = g if id(p) not in out else out[id(p)] + g
+        gx, out = mwcnn_backward(x, gy, ctx.ws, ctx.needs_input_grad[0])
         return (gx, None, None, None) + tuple(out.get(id(p)) for p in ctx.params)
 
 
 def mwcnn(x: torch.Tensor, w, w2=None, split: int = 0) -> torch.Tensor:
-    params, seen = [], set()
-    for wt in (w,) + ((w2,) if w2 is not None and w2 is not w else ()):
-        for p in wt.param_list():
-            if id(p) not in seen:
-                seen.add(id(p)); params.append(p)
-    return MwcnnFn.apply(x, w, w2, split, *params)
+    return MwcnnFn.apply(x, w, w2, split, *_mwcnn_params(w, w2))
 
 
-# ------------------------------------------------------------------ coil operators
 def _image_dc_sens_grad(m, gout, sens, mask, lam, w1, w0):
     """The maps' gradient of ``ops.image_dc`` (b, 1, c, h, w, 2): per frame conj(g) T(S_c m) + T(S_c g) conj(m), the frames added by
     cine_coil_accum.  Row mask: cine_image_dc_sens_grad (one column pass); mask that varies along w: cine_image_dc_general_sens_grad, both
@@ -444,32 +461,18 @@ class XpdRegFn(Function):
         b, t, _, h, w, _ = buf.shape
         pxf, pyf, mean = ops.xpd_pack(buf, extra, n, n_scales, xf)
         joint = pxf.shape[1:] == pyf.shape[1:] and pxf.data_ptr() + pxf.numel() * 4 == pyf.data_ptr()
-        L = lib()
-
-        def run(planes, w1, w2, split):
-            net = w1.net
-            nn_, cin, hh, ww = planes.shape
-            need = L.cine_mwcnn_train_ws_bytes(nn_, hh, ww, cin, net.out_chans, net.n_scales, w1.nf, w1.nc, net.first_conv_n_filters)
-            ws = torch.empty(max(need, 1), device=planes.device, dtype=torch.uint8)
-            y = torch.empty((nn_, net.out_chans, hh, ww), device=planes.device, dtype=planes.dtype)
-            two = w2 is not None and w2 is not w1
-            check(L.cine_mwcnn_forward_train(planes.data_ptr(), y.data_ptr(), w1.pointers(train=True), w2.pointers(train=True) if two else None, split if two else nn_,
-                                             nn_, hh, ww, cin, net.out_chans, net.n_scales, w1.nf, w1.nc, net.n_first_convs,
-                                             net.first_conv_n_filters, int(net.res), ops.lrelu_slope(), ws.data_ptr(), ws.numel(), _stream()), "cine_mwcnn_forward_train")
-            ws.cine_slope = ops.lrelu_slope()
-            return y, ws
         if joint:
             planes = torch.as_strided(pxf, (pxf.shape[0] + pyf.shape[0],) + tuple(pxf.shape[1:]), pxf.stride())
-            q, ws = run(planes, wx, wy, pxf.shape[0])
+            q, ws = mwcnn_forward_train(planes, wx, wy, pxf.shape[0])
             oxf, oyf = q[:pxf.shape[0]], q[pxf.shape[0]:]
             ctx.ws = (ws,)
         else:
-            oxf, ws0 = run(pxf, wx, None, 0)
-            oyf, ws1 = run(pyf, wy, None, 0)
+            oxf, ws0 = mwcnn_forward_train(pxf, wx)
+            oyf, ws1 = mwcnn_forward_train(pyf, wy)
             ctx.ws = (ws0, ws1)
         out = ops.xpd_unpack(oxf, oyf, mean, b, t, h, w, n, n_scales, xf)
         ctx.cfg = (b, t, h, w, int(n), int(n_scales), bool(xf), joint)
-        ctx.weights, ctx.params = (wx, wy), params
+        ctx.params = params
         ctx.save_for_backward(pxf, pyf)
         return out
 
@@ -477,7 +480,8 @@ class XpdRegFn(Function):
     def backward(ctx, gout):
         pxf, pyf = ctx.saved_tensors
         b, t, h, w, n, n_scales, xf, joint = ctx.cfg
-        wx, wy = ctx.weights
+        for ws in ctx.ws:
+            mwcnn_check_fresh(ws)
         gout = ops._dev(_c(gout), "I-step output gradient")
         dev, dt = gout.device, gout.dtype
         L = lib()
@@ -491,34 +495,15 @@ class XpdRegFn(Function):
         gmean = torch.empty((b, h, w, n + 1, 2), device=dev, dtype=dt)
         check(L.cine_xpd_unpack_bwd(gout.data_ptr(), gqx.data_ptr(), gqy.data_ptr(), gmean.data_ptr(), b, t, h, w, n, n_scales, int(xf), _stream()),
               "cine_xpd_unpack_bwd")
-        out = {}
-
-        def back(planes, gy, w1, w2, split, fws):
-            net = w1.net
-            nn_, cin, hh, ww = planes.shape
-            need = L.cine_mwcnn_backward_ws_bytes(nn_, hh, ww, cin, net.out_chans, net.n_scales, w1.nf, w1.nc, net.first_conv_n_filters)
-            ws = torch.empty(need, device=dev, dtype=torch.uint8)
-            two = w2 is not None and w2 is not w1
-            lists = []
-            pls = [wt.param_list() for wt in (w1,) + ((w2,) if two else ())]
-            for pl, gl in zip(pls, _zero_grads(pls, dev)):
-                lists.append((pl, gl, (ctypes.c_void_p * len(gl))(*[g.data_ptr() for g in gl])))
-            gx = torch.empty_like(planes)
-            check(L.cine_mwcnn_backward(planes.data_ptr(), gy.data_ptr(), w1.dgrad_pointers(), w2.dgrad_pointers() if two else None, lists[0][2],
-                                        lists[1][2] if two else None, split if two else nn_, nn_, hh, ww, cin, net.out_chans, net.n_scales, w1.nf, w1.nc,
-                                        net.first_conv_n_filters, getattr(fws, "cine_slope", ops.lrelu_slope()), fws.data_ptr(), fws.numel(), ws.data_ptr(), ws.numel(), gx.data_ptr(), _stream()),
-                  "cine_mwcnn_backward")
-            for pl, gl, _ in lists:
-                for p, g in zip(pl, gl):
-                    out[id(p)] = g if id(p) not in out else out[id(p)] + g
-            return gx
         if joint:
             planes = torch.as_strided(pxf, (pxf.shape[0] + pyf.shape[0],) + tuple(pxf.shape[1:]), pxf.stride())
-            gp = back(planes, gq, wx, wy, pxf.shape[0], ctx.ws[0])
+            gp, out = mwcnn_backward(planes, gq, ctx.ws[0])
             gpx, gpy = gp[:pxf.shape[0]], gp[pxf.shape[0]:]
         else:
-            gpx = back(pxf, gqx, wx, None, 0, ctx.ws[0])
-            gpy = back(pyf, gqy, wy, None, 0, ctx.ws[1])
+            gpx, out = mwcnn_backward(pxf, gqx, ctx.ws[0])
+            gpy, g1 = mwcnn_backward(pyf, gqy, ctx.ws[1])
+            for k, g in g1.items():
+                out[k] = g if k not in out else out[k] + g
         gbuf = torch.empty((b, t, 1, h, w, 2 * n), device=dev, dtype=dt)
         gextra = torch.empty((b, t, 1, h, w, 2), device=dev, dtype=dt)
         check(L.cine_xpd_pack_bwd(gpx.data_ptr(), gpy.data_ptr(), gmean.data_ptr(), gbuf.data_ptr(), gextra.data_ptr(), b, t, h, w, n, n_scales,
@@ -527,12 +512,7 @@ class XpdRegFn(Function):
 
 
 def xpd_regularise(buf, extra, n, n_scales, xf, wx, wy):
-    params, seen = [], set()
-    for wt in (wx, wy):
-        for p in wt.param_list():
-            if id(p) not in seen:
-                seen.add(id(p)); params.append(p)
-    return XpdRegFn.apply(buf, extra, n, n_scales, xf, wx, wy, *params)
+    return XpdRegFn.apply(buf, extra, n, n_scales, xf, wx, wy, *_mwcnn_params(wx, wy))
 
 
 # ---- 3-D U-Net (denoisers/unet.py with dims = 3) -----------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@ PyTorch is plumbing here (device memory + the current HIP stream); all
 arithmetic happens in libcine_hip.so.  Inputs must be CUDA(HIP) float32
 tensors; anything else raises -- there is no CPU path.
 """
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import contextlib
 import ctypes
@@ -263,9 +263,49 @@ def _no_capture(what: str, pack: bool = False) -> None:
     """Caches that outlive a call (packed weights, per-stream scratch) must not be filled during hipGraph capture: the
     tensors would come from the graph's private pool yet stay referenced afterwards.  (pack: a packed-weight cache, allowed inside
     ``training_capture()``.)"""
-    if torch.cuda.is_current_stream_capturing() and not (pack and (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream) in _pack_capture_streams):
+    if _capturing() and not (pack and _pack_capture_streams and (torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream) in _pack_capture_streams):
         raise CineHipError(f"{what} would be created during hipGraph capture; run one eager forward on this stream first "
                            "(and re-capture after changing weights)")
+
+
+def _capturing() -> bool:
+    """The one capture query of this module (it needs a device: host-only tests substitute it)."""
+    return torch.cuda.is_current_stream_capturing()
+
+
+class PackCache:
+    """Device tensors derived from parameters (packed weights, summed biases), rebuilt when a parameter moves, is modified in place
+    (``Tensor._version``) or the cache epoch moves.  ``get(params, build)``: ``build()`` returns (the tensors to keep, the value to hand out) and
+    runs only on a miss, never during hipGraph capture outside ``training_capture()``.  A graph captured earlier still holds the old addresses:
+    once the value has been handed out under capture, the next miss parks the superseded tensors until ``release_old()`` (call it after
+    destroying those graphs); otherwise they are dropped, so a training loop that re-packs every step does not pile them up.
+    Copies and pickles start empty."""
+
+    def __init__(self, what: str):
+        self.what = what
+        self.fills = 0                      # builder calls so far
+        self._key = self._keep = self._value = None
+        self._captured = False
+        self._old = []
+
+    def __reduce__(self):
+        return (type(self), (self.what,))
+
+    def get(self, params, build):
+        key = (_cache_epoch, tuple((p.data_ptr(), p._version) for p in params))
+        if key != self._key:
+            _no_capture(self.what, pack=True)
+            keep, value = build()
+            if self._captured:
+                self._old.append(self._keep)
+            self._keep, self._value, self._key, self._captured = keep, value, key, False
+            self.fills += 1
+        if not self._captured and _capturing():
+            self._captured = True
+        return self._value
+
+    def release_old(self) -> None:
+        self._old = []
 
 
 def _dev(x: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
@@ -505,7 +545,7 @@ _GENERAL_WS_LOCK = threading.Lock()
 def _general_ws(nbytes: int, device: torch.device) -> torch.Tensor:
     """The hybrid-space scratch of the general-mask operators: one buffer per (device, stream, size), so that the cascades of a forward
     pass (and of every later one on that stream) share it.  A captured graph gets a buffer of its own pool instead, static over replays."""
-    if torch.cuda.is_current_stream_capturing():
+    if _capturing():
         return torch.empty(nbytes, device=device, dtype=torch.uint8)
     key = (device.index, _stream(), nbytes)
     with _GENERAL_WS_LOCK:
@@ -1198,62 +1238,58 @@ def xfyf_unpack(pxf, pyf, sxf, syf, mean, b: int, t: int, h: int, w: int, xf: bo
 
 
 # ------------------------------------------------------------------ U-Net pieces
+class _Kind(NamedTuple):
+    """One packed-weight layout: cine_<stem>_packed_floats sizes it and cine_pack_<stem> fills it from a weight (dims[0], dims[1], *tail); the
+    entries take the two leading dimensions in that order.  tail None: a (cout, cin) matrix, trailing 1s allowed.  op: the number of the
+    layout in cine_pack_desc (include/cine_hip.h "Batched packing"), None where the batched re-pack has no such op."""
+    stem: str
+    dims: tuple
+    tail: Optional[tuple]
+    op: Optional[int]
+
+    @property
+    def floats_fn(self) -> str:
+        return f"cine_{self.stem}_packed_floats"
+
+    @property
+    def pack_fn(self) -> str:
+        return f"cine_pack_{self.stem}"
+
+
+_CONV, _TCONV = ("cout", "cin"), ("cin", "cout")
+_KINDS = {
+    "c3": _Kind("conv3x3", _CONV, (3, 3), 0),
+    "tc": _Kind("tconv2x2", _TCONV, (2, 2), 1),
+    "c1": _Kind("conv1x1", _CONV, None, 2),
+    "c27": _Kind("conv3d", _CONV, (3, 3, 3), None),
+    "tc3": _Kind("tconv3d", _TCONV, (2, 2, 2), None),
+    # input-gradient packings (training): include/cine_hip.h "Training"
+    "c3d": _Kind("conv3x3_dgrad", _CONV, (3, 3), 3),
+    "tcd": _Kind("tconv2x2_dgrad", _TCONV, (2, 2), 4),
+    "c1d": _Kind("conv1x1_dgrad", _CONV, None, 5),
+}
+
+
 def _pack(kind: str, w: torch.Tensor) -> torch.Tensor:
+    k = _KINDS.get(kind)
+    if k is None:
+        raise ValueError(kind)
     L = lib()
     w = _dev(w.detach(), f"{kind} weight")
-    if kind == "c3":
-        cout, cin, kh, kw = w.shape
-        if (kh, kw) != (3, 3):
-            raise ValueError("pack_conv3x3 expects a (cout, cin, 3, 3) weight")
-        out = torch.empty(L.cine_conv3x3_packed_floats(cout, cin), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_conv3x3(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "cine_pack_conv3x3")
-    elif kind == "tc":
-        cin, cout, kh, kw = w.shape
-        if (kh, kw) != (2, 2):
-            raise ValueError("pack_tconv2x2 expects a (cin, cout, 2, 2) weight")
-        out = torch.empty(L.cine_tconv2x2_packed_floats(cin, cout), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_tconv2x2(w.data_ptr(), out.data_ptr(), cin, cout, _stream()), "cine_pack_tconv2x2")
-    elif kind == "c27":
-        cout, cin = w.shape[:2]
-        if tuple(w.shape[2:]) != (3, 3, 3):
-            raise ValueError("pack_conv3d expects a (cout, cin, 3, 3, 3) weight")
-        out = torch.empty(L.cine_conv3d_packed_floats(cout, cin), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_conv3d(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "cine_pack_conv3d")
-    elif kind == "tc3":
-        cin, cout = w.shape[:2]
-        if tuple(w.shape[2:]) != (2, 2, 2):
-            raise ValueError("pack_tconv3d expects a (cin, cout, 2, 2, 2) weight")
-        out = torch.empty(L.cine_tconv3d_packed_floats(cin, cout), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_tconv3d(w.data_ptr(), out.data_ptr(), cin, cout, _stream()), "cine_pack_tconv3d")
-    elif kind == "c1":
-        cout, cin = w.shape[0], w.shape[1]
-        out = torch.empty(L.cine_conv1x1_packed_floats(cout, cin), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_conv1x1(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "cine_pack_conv1x1")
-    elif kind == "c3d":      # input-gradient packings (training): include/cine_hip.h "Training"
-        cout, cin = w.shape[:2]
-        out = torch.empty(L.cine_conv3x3_dgrad_packed_floats(cout, cin), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_conv3x3_dgrad(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "cine_pack_conv3x3_dgrad")
-    elif kind == "tcd":
-        cin, cout = w.shape[:2]
-        out = torch.empty(L.cine_tconv2x2_dgrad_packed_floats(cin, cout), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_tconv2x2_dgrad(w.data_ptr(), out.data_ptr(), cin, cout, _stream()), "cine_pack_tconv2x2_dgrad")
-    elif kind == "c1d":
-        cout, cin = w.shape[:2]
-        out = torch.empty(L.cine_conv1x1_dgrad_packed_floats(cout, cin), device=w.device, dtype=w.dtype)
-        check(L.cine_pack_conv1x1_dgrad(w.data_ptr(), out.data_ptr(), cout, cin, _stream()), "cine_pack_conv1x1_dgrad")
-    else:
-        raise ValueError(kind)
+    if w.dim() < 2 or (k.tail is not None and tuple(w.shape[2:]) != k.tail):
+        raise ValueError(f"pack_{k.stem} expects a ({', '.join(k.dims + tuple(map(str, k.tail or ())))}) weight")
+    n1, n2 = int(w.shape[0]), int(w.shape[1])
+    out = torch.empty(getattr(L, k.floats_fn)(n1, n2), device=w.device, dtype=w.dtype)
+    check(getattr(L, k.pack_fn)(w.data_ptr(), out.data_ptr(), n1, n2, _stream()), k.pack_fn)
     return out
 
 
 class _BatchedPacks:
     """Packed copies of a network's 2-D conv weights in PERSISTENT buffers, re-packed by ONE launch when a parameter's version moves (training:
     every optimiser step; per tensor that was 596 launches of 4 us in a cfg-3 step).  ``pointers(items)``: items = (kind, parameter) in pointer-list
-    order, kind in _OPS or "raw" (the parameter itself, e.g. a bias) or None (a NULL slot).  The descriptor table goes to the device once per
+    order, kind a row of _KINDS with an op number or "raw" (the parameter itself, e.g. a bias) or None (a NULL slot).  The descriptor table goes to the device once per
     (parameter addresses, cache epoch); inside a hipGraph capture only the re-pack launch is enqueued, so a captured training step packs in place.
     Inference keeps its own per-tensor packs (UnetWeights.pointers()): graphs captured from those never see these buffers change."""
-    _OPS = {"c3": 0, "tc": 1, "c1": 2, "c3d": 3, "tcd": 4, "c1d": 5}
-
     def __init__(self):
         self.idkey = self.vkey = None
         self.keep = []                       # superseded buffers stay alive: a captured graph may still re-pack into them
@@ -1262,7 +1298,7 @@ class _BatchedPacks:
     def supports(cls, items) -> bool:
         # contiguous parameters only: the descriptor table holds the parameters' OWN addresses (a .contiguous() copy of a channels_last
         # model would be packed once and then go stale); anything else takes the per-tensor packs
-        return all(k is None or ((k == "raw" or (k in cls._OPS and p.dim() == 4)) and p.is_contiguous()) for k, p in items)
+        return all(k is None or ((k == "raw" or (k in _KINDS and _KINDS[k].op is not None and p.dim() == 4)) and p.is_contiguous()) for k, p in items)
 
     def pointers(self, items):
         L = lib()
@@ -1277,8 +1313,7 @@ class _BatchedPacks:
                 if k == "raw":
                     sizes.append(0); dims.append(None); continue
                 a, b = int(p.shape[0]), int(p.shape[1])
-                fl = {"c3": L.cine_conv3x3_packed_floats, "tc": L.cine_tconv2x2_packed_floats, "c1": L.cine_conv1x1_packed_floats,
-                      "c3d": L.cine_conv3x3_dgrad_packed_floats, "tcd": L.cine_tconv2x2_dgrad_packed_floats, "c1d": L.cine_conv1x1_dgrad_packed_floats}[k](a, b)
+                fl = getattr(L, _KINDS[k].floats_fn)(a, b)
                 sizes.append((int(fl) + 63) // 64 * 64); dims.append((a, b))
             flat = torch.empty(max(sum(sizes), 1), device=dev, dtype=torch.float32)
             nb = L.cine_pack_desc_bytes()
@@ -1291,7 +1326,7 @@ class _BatchedPacks:
                 if k == "raw":
                     ptrs.append(src.data_ptr()); continue
                 dst = flat.data_ptr() + 4 * off
-                check(L.cine_pack_desc(ctypes.addressof(host) + nb * nd, self._OPS[k], src.data_ptr(), dst, dm[0], dm[1]), "cine_pack_desc")
+                check(L.cine_pack_desc(ctypes.addressof(host) + nb * nd, _KINDS[k].op, src.data_ptr(), dst, dm[0], dm[1]), "cine_pack_desc")
                 ptrs.append(dst); off += sz; nd += 1
             desc = torch.frombuffer(bytearray(host.raw), dtype=torch.uint8).to(dev) if nd else None
             out, it = [], iter(ptrs)
@@ -1391,27 +1426,96 @@ def instnorm_lrelu_apply(x: torch.Tensor, part: torch.Tensor) -> torch.Tensor:
     return y
 
 
-class UnetWeights:
-    """Device-side weight pointers of one (or several) reference ``Unet`` modules in the
-    order ``cine_unet2d_forward`` expects; 3x3 weights are repacked once and re-packed
-    automatically when a parameter is modified in place (``Tensor._version``)."""
+class _NetWeights:
+    """Device-side weight pointer lists of a network (or of several of one topology: one pointer set each) in the order its C entry points
+    expect.  A subclass states ``_params()``: per set, the (kind, parameter) slots -- kind a row of _KINDS, or "raw" for a parameter read at its
+    own address (a bias).  The weights are packed once and re-packed automatically when a parameter moves or is modified in place (PackCache);
+    training takes persistent packs re-packed by one launch per optimiser step where the kinds allow it (_BatchedPacks)."""
+    _noun = "network"
 
-    def __init__(self, unets: Sequence[torch.nn.Module]):
-        self.unets = list(unets)
-        u0 = self.unets[0]
-        self.chans, self.pools = u0.chans, u0.num_pool_layers
-        self.in_ch, self.out_ch = u0.in_chans, u0.out_chans
-        self._key = None
-        self._keep = []
-        self._ptrs = None
-        self._captured = False
-        self._dkey = None
-        self._dkeep = []
-        self._dptrs = None
+    def __init__(self, *modules):
+        self._modules = modules
+        self._fwd, self._dgrad = PackCache(f"packed {self._noun} weights"), PackCache(f"packed {self._noun} gradient weights")
+        self._tp, self._tdp = _BatchedPacks(), _BatchedPacks()
 
     def __reduce__(self):
         # copies / pickles carry the modules only; the packed device buffers and pointer tables are rebuilt on first use
-        return (type(self), (self.unets,))
+        return (type(self), self._modules)
+
+    # the input-gradient packing of a forward kind: (pack kind, the view of the weight which that packing reads, None = the weight itself)
+    _DGRAD = {"c3": ("c3d", None), "tc": ("tcd", None), "c1": ("c1d", None)}
+    _DGRAD_3D = {}          # the same for 5-D weights
+
+    def pointers(self, train: bool = False):
+        """train=True (the training forward): persistent packs re-packed by one launch per optimiser step (_BatchedPacks)."""
+        items = [kp for seq in self._params() for kp in seq]
+        if train and _BatchedPacks.supports(items):
+            return self._tp.pointers(items)
+
+        def build():
+            keep = [_dev(p.detach(), f"{self._noun} bias") if kind == "raw" else _pack(kind, p) for kind, p in items]
+            return keep, (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
+        return self._fwd.get([p for _, p in items], build)
+
+    def dgrad_pointers(self):
+        """Input-gradient packings in the order of ``pointers()`` (NULL in the bias slot); re-packed when a parameter changes."""
+        slots = [kp for seq in self._params() for kp in seq]
+        params = [p for _, p in slots]
+        rules = [None if kind == "raw" else (self._DGRAD_3D if p.dim() == 5 else self._DGRAD)[kind] for kind, p in slots]
+        if all(r is None or r[1] is None for r in rules):
+            items = [(r and r[0], p) for r, p in zip(rules, params)]
+            if _BatchedPacks.supports(items):
+                return self._tdp.pointers(items)
+
+        def build():
+            packs = [r and _pack(r[0], p if r[1] is None else r[1](p.detach())) for r, p in zip(rules, params)]
+            return packs, (ctypes.c_void_p * len(packs))(*[t if t is None else t.data_ptr() for t in packs])
+        return self._dgrad.get(params, build)
+
+    def release_old(self) -> None:
+        """Drop packed weight sets that only earlier-captured graphs may reference (call after destroying those graphs)."""
+        self._fwd.release_old(); self._dgrad.release_old()
+
+    # ---- training
+    def training_key(self):
+        """Called where a training ``autograd.Function`` is entered: the parameters' (address, version) key -- the backward pass re-packs the
+        input-gradient weights from the parameters' CURRENT values and compares this key first (torch would raise 'modified by an inplace
+        operation')."""
+        return tuple((p.data_ptr(), p._version) for seq in self._params() for _, p in seq)
+
+    def check_training_key(self, key, what: str) -> None:
+        if key is not None and key != self.training_key():
+            raise RuntimeError(f"{what}: a parameter of the {self._noun} was modified between the forward and the backward pass "
+                               "(optimizer.step() or an in-place update before loss.backward()); the saved activations belong to the old weights")
+
+    def param_lists(self):
+        """Per weight set, the parameters in the order of the pointer lists (bias last)."""
+        return [[p for _, p in seq] for seq in self._params()]
+
+    def distinct_params(self):
+        seen, out = set(), []
+        for seq in self._params():
+            for _, p in seq:
+                if id(p) not in seen:
+                    seen.add(id(p)); out.append(p)
+        return out
+
+
+class UnetWeights(_NetWeights):
+    """One (or several) reference ``Unet`` modules, 2-D (``cine_unet2d_forward``) or 3-D (``cine_unet3d_forward``)."""
+    _noun = "U-Net"
+    # cine_unet3d_backward runs its input gradients on the FORWARD kernels: the 3x3x3 kernel on the flipped taps with (cout, cin) transposed; a
+    # transpose conv (cin, cout, 2, 2, 2) read as the (cin, 8 cout) matrix of a 1x1x1 conv over the space-to-depth view; the final 1x1x1 matrix transposed
+    _DGRAD_3D = {"c27": ("c27", lambda w: w.flip(2, 3, 4).transpose(0, 1).contiguous()),
+                 "tc3": ("c1", lambda w: w.reshape(w.shape[0], -1)),
+                 "c1": ("c1", lambda w: w.reshape(w.shape[0], -1).t().contiguous())}
+
+    def __init__(self, unets: Sequence[torch.nn.Module]):
+        self.unets = list(unets)
+        super().__init__(self.unets)
+        u0 = self.unets[0]
+        self.chans, self.pools = u0.chans, u0.num_pool_layers
+        self.in_ch, self.out_ch = u0.in_chans, u0.out_chans
 
     def _params(self):
         out = []
@@ -1428,45 +1532,6 @@ class UnetWeights:
             seq += [("c1", fin.weight), ("raw", fin.bias)]
             out.append(seq)
         return out
-
-    def pointers(self, train: bool = False):
-        """train=True (the training forward): persistent packs re-packed by one launch per optimiser step (_BatchedPacks)."""
-        params = self._params()
-        if train:
-            items = [(k, p) for seq in params for k, p in seq]
-            if _BatchedPacks.supports(items):
-                if self.__dict__.get("_tp") is None:
-                    self._tp = _BatchedPacks()
-                return self._tp.pointers(items)
-        key = (_cache_epoch,) + tuple((p.data_ptr(), p._version) for seq in params for _, p in seq)
-        if key != self._key:
-            _no_capture("packed U-Net weights", pack=True)
-            # graphs captured earlier still hold the old pointers: keep the superseded packs alive only when a capture has
-            # taken place since they were made (a training loop re-packs every step and must not pile them up)
-            if self._captured:
-                self._old = getattr(self, "_old", []) + [self._keep]
-            self._captured = False
-            keep, ptrs = [], []
-            for seq in params:
-                for kind, p in seq:
-                    t = _dev(p.detach(), "unet weight") if kind == "raw" else _pack(kind, p)
-                    keep.append(t); ptrs.append(t.data_ptr())
-            self._keep, self._key = keep, key
-            self._ptrs = (ctypes.c_void_p * len(ptrs))(*ptrs)
-        if torch.cuda.is_current_stream_capturing():
-            self._captured = True
-        return self._ptrs
-
-    def release_old(self) -> None:
-        """Drop packed weight sets that only earlier-captured graphs may reference (call after destroying those graphs)."""
-        self._old = []
-
-    # ---- training (cine_unet2d_backward)
-    def training_key(self):
-        """Called where a training ``autograd.Function`` is entered: the parameters' (address, version) key -- the backward pass re-packs the
-        input-gradient weights from the parameters' CURRENT values and compares this key first (torch would raise 'modified by an inplace
-        operation')."""
-        return tuple((p.data_ptr(), p._version) for seq in self._params() for _, p in seq)
 
     def drops(self) -> bool:
         """True when a network of the set applies Dropout in its current mode."""
@@ -1503,55 +1568,6 @@ class UnetWeights:
                 ob[rows] = (blk[rows] >= p).to(torch.float32) / (1.0 - p)
             off += n * ch
         return out
-
-    def check_training_key(self, key, what: str) -> None:
-        if key is not None and key != tuple((p.data_ptr(), p._version) for seq in self._params() for _, p in seq):
-            raise RuntimeError(f"{what}: a U-Net parameter was modified between the forward and the backward pass "
-                               "(optimizer.step() or an in-place update before loss.backward()); the saved activations belong to the old weights")
-
-    def param_lists(self):
-        """Per weight set, the parameters in the order of the pointer lists (bias last)."""
-        return [[p for _, p in seq] for seq in self._params()]
-
-    def distinct_params(self):
-        seen, out = set(), []
-        for seq in self._params():
-            for _, p in seq:
-                if id(p) not in seen:
-                    seen.add(id(p)); out.append(p)
-        return out
-
-    def dgrad_pointers(self):
-        """Input-gradient packings in the order of ``pointers()`` (NULL in the bias slot); re-packed when a parameter changes."""
-        params = self._params()
-        items = [(None if k == "raw" else k + "d", p) for seq in params for k, p in seq]
-        if _BatchedPacks.supports(items):
-            if self.__dict__.get("_tdp") is None:
-                self._tdp = _BatchedPacks()
-            return self._tdp.pointers(items)
-        key = (_cache_epoch,) + tuple((p.data_ptr(), p._version) for seq in params for _, p in seq)
-        if key != self._dkey:
-            _no_capture("packed U-Net gradient weights", pack=True)
-            keep, ptrs = [], []
-            for seq in params:
-                for kind, p in seq:
-                    if kind == "raw":
-                        ptrs.append(None); continue
-                    if kind in ("c3", "tc"):
-                        t = _pack(kind + "d", p)
-                    elif kind == "c1":
-                        # 2-D: the dgrad packing; 3-D (cine_unet3d_backward): the forward 1x1x1 kernel on the transposed matrix
-                        t = _pack("c1d", p) if p.dim() == 4 else _pack("c1", p.detach().reshape(p.shape[0], -1).t().contiguous())
-                    elif kind == "c27":      # the forward 3x3x3 kernel on the flipped taps, (cout, cin) transposed
-                        t = _pack("c27", p.detach().flip(2, 3, 4).transpose(0, 1).contiguous())
-                    elif kind == "tc3":      # (cin, cout, 2, 2, 2) read as the (cin, 8 cout) matrix of a 1x1x1 conv over the space-to-depth view
-                        t = _pack("c1", p.detach().reshape(p.shape[0], -1))
-                    else:
-                        raise CineHipError(f"no input-gradient packing for weight kind {kind}")
-                    keep.append(t); ptrs.append(t.data_ptr())
-            self._dkeep, self._dkey = keep, key
-            self._dptrs = (ctypes.c_void_p * len(ptrs))(*ptrs)
-        return self._dptrs
 
 
 def _branch_count(n: int, nsets: int) -> int:
@@ -1605,19 +1621,15 @@ def mwcnn_pad(size: int, n_scales: int):
     return padded, l.value, r.value
 
 
-class MwcnnWeights:
-    """Packed 3x3 weights of one reference MWCNN in the order cine_mwcnn_forward expects."""
+class MwcnnWeights(_NetWeights):
+    """One reference MWCNN in the order cine_mwcnn_forward expects (all 3x3)."""
+    _noun = "MWCNN"
 
     def __init__(self, net: torch.nn.Module):
+        super().__init__(net)
         self.net = net
-        self._key = None
-        self._keep = []
-        self._ptrs = None
         self.nf = (ctypes.c_int * net.n_scales)(*net.n_filters_per_scale)
         self.nc = (ctypes.c_int * net.n_scales)(*net.n_convs_per_scale)
-
-    def __reduce__(self):
-        return (type(self), (self.net,))
 
     def _params(self):
         n = self.net
@@ -1626,53 +1638,10 @@ class MwcnnWeights:
             for blk in blocks:
                 seq.append(("c3", blk.layers[0].weight))
         seq += [("c3", n.first_convs[-1].weight), ("raw", n.first_convs[-1].bias)]
-        return seq
+        return [seq]
 
-    def pointers(self, train: bool = False):
-        params = self._params()
-        if train and _BatchedPacks.supports(params):
-            if self.__dict__.get("_tp") is None:
-                self._tp = _BatchedPacks()
-            return self._tp.pointers(params)
-        key = (_cache_epoch,) + tuple((p.data_ptr(), p._version) for _, p in params)
-        if key != self._key:
-            _no_capture("packed MWCNN weights", pack=True)
-            if getattr(self, "_captured", False):                    # graphs captured earlier still hold the old pointers
-                self._old = getattr(self, "_old", []) + [self._keep]
-            self._captured = False
-            keep = [(_dev(p.detach(), "mwcnn bias") if kind == "raw" else _pack(kind, p)) for kind, p in params]
-            self._keep, self._key = keep, key
-            self._ptrs = (ctypes.c_void_p * len(keep))(*[t.data_ptr() for t in keep])
-        if torch.cuda.is_current_stream_capturing():
-            self._captured = True
-        return self._ptrs
-
-    def release_old(self) -> None:
-        self._old = []
-
-    # ---- training (cine_mwcnn_backward)
     def param_list(self):
-        return [p for _, p in self._params()]
-
-    def dgrad_pointers(self):
-        params = self._params()
-        items = [(None if k == "raw" else "c3d", p) for k, p in params]
-        if _BatchedPacks.supports(items):
-            if self.__dict__.get("_tdp") is None:
-                self._tdp = _BatchedPacks()
-            return self._tdp.pointers(items)
-        key = (_cache_epoch,) + tuple((p.data_ptr(), p._version) for _, p in params)
-        if key != getattr(self, "_dkey", None):
-            _no_capture("packed MWCNN gradient weights", pack=True)
-            keep, ptrs = [], []
-            for kind, p in params:
-                if kind == "raw":
-                    ptrs.append(None); continue
-                t = _pack("c3d", p)
-                keep.append(t); ptrs.append(t.data_ptr())
-            self._dkeep, self._dkey = keep, key
-            self._dptrs = (ctypes.c_void_p * len(ptrs))(*ptrs)
-        return self._dptrs
+        return self.param_lists()[0]
 
 
 def mwcnn_forward(x: torch.Tensor, w: MwcnnWeights, w2: Optional[MwcnnWeights] = None, split: int = 0) -> torch.Tensor:

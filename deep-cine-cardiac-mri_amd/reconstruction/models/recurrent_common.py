@@ -57,19 +57,16 @@ class BCRNNlayer(nn.Module):
         super().__init__()
         self.hidden_size = hidden_size
         self.CRNN_model = CRNNcell(input_size, hidden_size, kernel_size)
-        self._key = None
+        self._packs = ops.PackCache("packed CRNN weights")
 
     def _packed(self):
         cell = self.CRNN_model
-        params = (cell.i2h.weight, cell.h2h.weight, cell.ih2ih.weight, cell.i2h.bias, cell.h2h.bias, cell.ih2ih.bias)
-        key = (ops.cache_epoch(),) + tuple((p.data_ptr(), p._version) for p in params)
-        if key != self._key:
-            ops._no_capture("packed CRNN weights", pack=True)
-            self._w_in = ops.pack_conv3x3(torch.cat([cell.ih2ih.weight, cell.i2h.weight], dim=1))
-            self._w_hh = ops.pack_conv3x3(cell.h2h.weight)
-            self._bias = (cell.i2h.bias + cell.h2h.bias + cell.ih2ih.bias).detach().contiguous()
-            self._key = key
-        return self._w_in, self._w_hh, self._bias
+
+        def build():
+            packs = (ops.pack_conv3x3(torch.cat([cell.ih2ih.weight, cell.i2h.weight], dim=1)), ops.pack_conv3x3(cell.h2h.weight),
+                     (cell.i2h.bias + cell.h2h.bias + cell.ih2ih.bias).detach().contiguous())
+            return packs, packs
+        return self._packs.get((cell.i2h.weight, cell.h2h.weight, cell.ih2ih.weight, cell.i2h.bias, cell.h2h.bias, cell.ih2ih.bias), build)
 
     def forward(self, input: torch.Tensor, hidden_iteration: torch.Tensor) -> torch.Tensor:
         """input (t, b, ch, h, w), hidden_iteration (t, b, hidden, h, w) -> (t, b, hidden, h, w)."""
@@ -121,22 +118,22 @@ class CRNNBody(nn.Module):
             setattr(self, f"conv{k}_h", nn.Conv2d(chans, chans, 3, padding=3 // 2))
         self.conv4_x = nn.Conv2d(chans, out_ch, 3, padding=3 // 2)
         self.relu = nn.ReLU(inplace=True)
-        self._body_key = None
+        self._body_packs, self._train_cache = ops.PackCache("packed CRNN weights"), ops.PackCache("packed CRNN training weights")
 
     def _body_packed(self):
         convs = [getattr(self, f"conv{k}_{s}") for k in (1, 2, 3) for s in ("x", "h")] + [self.conv4_x]
-        key = (ops.cache_epoch(),) + tuple((p.data_ptr(), p._version) for c in convs for p in (c.weight, c.bias))
-        if key != self._body_key:
-            ops._no_capture("packed CRNN weights", pack=True)
-            self._pairs = []
-            for k in (1, 2, 3):
-                cx, chh = getattr(self, f"conv{k}_x"), getattr(self, f"conv{k}_h")
-                self._pairs.append((ops.pack_conv3x3(torch.cat([cx.weight, chh.weight], dim=1)),
-                                    (cx.bias + chh.bias).detach().contiguous()))
-            self._w4 = ops.pack_conv3x3(self.conv4_x.weight)
-            self._b4 = self.conv4_x.bias.detach().contiguous()
-            self._body_key = key
-        return self._pairs, self._w4, self._b4
+
+        def build():
+            pairs = [(ops.pack_conv3x3(torch.cat([cx.weight, chh.weight], dim=1)), (cx.bias + chh.bias).detach().contiguous())
+                     for cx, chh in zip(convs[0:6:2], convs[1:6:2])]
+            packs = (pairs, ops.pack_conv3x3(self.conv4_x.weight), self.conv4_x.bias.detach().contiguous())
+            return packs, packs
+        return self._body_packs.get([p for c in convs for p in (c.weight, c.bias)], build)
+
+    def release_old(self) -> None:
+        """Drop the packed weights that only graphs captured before a weight update may reference (call after destroying those graphs)."""
+        for cache in (self.bcrnn._packs, self._body_packs, self._train_cache):
+            cache.release_old()
 
     def zero_state(self, t: int, b: int, h: int, w: int, like: torch.Tensor):
         return [zeros_ro((t * b, self.chans, h, w), like) for _ in range(4)]     # read only: sources of the first cascade
@@ -153,9 +150,8 @@ class CRNNBody(nn.Module):
         """The body's packed weights for ag.CrnnBodyFn, once per optimiser step (the cascades share them): forward packings of the concatenated
         weights ([W_ih2ih | W_i2h], [W_kx | W_kh]) with their summed biases, and the input-gradient packing of every single weight."""
         ps = self._body_params()
-        key = (ops.cache_epoch(),) + tuple((p.data_ptr(), p._version) for p in ps)
-        if key != self.__dict__.get("_tp_key"):
-            ops._no_capture("packed CRNN training weights", pack=True)
+
+        def build():
             with torch.no_grad():
                 w_ih2ih, w_i2h, w_h2h, b_i2h, b_h2h, b_ih2ih = ps[:6]
                 pk = {"in": ops.pack_conv3x3(torch.cat([w_ih2ih, w_i2h], dim=1)), "b_in": (b_i2h + b_h2h + b_ih2ih).contiguous(),
@@ -165,8 +161,8 @@ class CRNNBody(nn.Module):
                     pk[f"p{k}"] = ops.pack_conv3x3(torch.cat([wx, wh], dim=1)); pk[f"b{k}"] = (bx + bh).contiguous()
                     pk[f"d{k}x"] = ops._pack("c3d", wx); pk[f"d{k}h"] = ops._pack("c3d", wh)
                 pk["w4"] = ops.pack_conv3x3(ps[18]); pk["b4"] = ps[19].detach().contiguous(); pk["d4"] = ops._pack("c3d", ps[18])
-            self.__dict__["_tp"], self.__dict__["_tp_key"] = pk, key
-        return self.__dict__["_tp"], ps
+            return pk, pk
+        return self._train_cache.get(ps, build), ps
 
     def body_train(self, x: torch.Tensor, state, residual: torch.Tensor):
         """``body`` as an autograd graph (batch 1).  One node per cascade (ag.CrnnBodyFn: the launch sequence of ``body`` forward; backward with

@@ -1128,7 +1128,7 @@ def test_batched_weight_packs_equal_the_per_tensor_packs_and_follow_the_paramete
     u = ops.UnetWeights([unet])
     items_u = [(k, p) for seq in u._params() for k, p in seq]
     m = ops.MwcnnWeights(mw)
-    items_m = list(m._params())
+    items_m = [(k, p) for seq in m._params() for k, p in seq]
     check_all(u, items_u); check_all(m, items_m)
     addr = (u._tp.flat.data_ptr(), m._tdp.flat.data_ptr())
     with torch.no_grad():
