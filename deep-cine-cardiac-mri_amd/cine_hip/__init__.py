@@ -34,13 +34,13 @@ _hw_queue_default()
 
 from . import synth  # noqa: F401,E402  (host-only, numpy)
 
-__all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense"]
+__all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse"]
 
-_CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense")
+_CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse")
 
 
 def __getattr__(name):
-    # the weight-free baseline (cine_hip.classical), imported on first use: the package import itself stays host-only
+    # the weight-free baselines (cine_hip.classical), imported on first use: the package import itself stays host-only
     if name in _CLASSICAL:
         from . import classical
         return getattr(classical, name)

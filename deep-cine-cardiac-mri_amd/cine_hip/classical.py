@@ -1,4 +1,5 @@
-"""Reconstruction without trained weights: k-t SPARSE-SENSE, the compressed-sensing baseline on the package's own operators.
+"""Reconstruction without trained weights: k-t SPARSE-SENSE and low-rank plus sparse (L+S), the compressed-sensing baselines on the
+package's own operators.
 
     minimise over x   1/2 || M A x - y ||^2  +  lam || w F_t x ||_1
 
@@ -13,8 +14,21 @@ threshold read from device memory, so nothing waits for the host and the solve c
 ``KtSparseSense`` is an ``nn.Module`` with CineNet's ``forward`` signature: it goes through ``SlicePipeline.submit`` / ``submit_raw``
 (``sens_maps="espirit"``, ``coil_matrix=``) like a network.
 
-Not built: CG-SENSE with a Tikhonov weight (``ops.conj_grad`` solves it for callers who want it), low-rank or total-variation regularisers,
-and gradients through the solver (it is not differentiable).
+Low-rank plus sparse (Otazo et al., MRM 2015): per batch element, over L and S,
+
+    minimise   1/2 || M A (L + S) - y ||^2  +  lam_l || C(L) ||_*  +  lam_s || F_t S ||_1
+
+with ``C(L)`` the (h w) x t Casorati matrix.  Proximal gradient without momentum from L_0 = zf, S_0 = 0:
+
+    g = A^H M A (L_k + S_k) - zf;   L_{k+1} = SVT(L_k - step g, step lam_l);   S_{k+1} = F_t^H soft(F_t (S_k - step g), step lam_s)
+
+The singular values are thresholded without an SVD: t <= 64, so the t x t Gram matrix of the Casorati matrix (``ops.casorati_gram``) is
+diagonalised by a Jacobi eigensolver in one workgroup (``ops.svt_weight``) and its t x t weight is applied per pixel inside the fused
+proximal kernel (``ops.ls_prox``).  One ``ops.ls_solve`` call runs all iterations with nothing read by the host.  ``LowRankPlusSparse`` is
+the module, as ``KtSparseSense``.
+
+Not built: CG-SENSE with a Tikhonov weight (``ops.conj_grad`` solves it for callers who want it), total-variation regularisers, and
+gradients through the solvers (they are not differentiable).
 """
 from typing import Optional, Union
 
@@ -25,7 +39,7 @@ from torch import nn
 from . import dc, ops
 from ._lib import CineHipError
 
-__all__ = ["fista_momentum", "kt_sparse_sense", "KtSparseSense"]
+__all__ = ["fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse"]
 
 
 def fista_momentum(iters: int) -> np.ndarray:
@@ -40,10 +54,10 @@ def fista_momentum(iters: int) -> np.ndarray:
     return out
 
 
-def _no_grad_inputs(**tensors) -> None:
+def _no_grad_inputs(what: str = "kt_sparse_sense", **tensors) -> None:
     for name, v in tensors.items():
         if isinstance(v, torch.Tensor) and v.requires_grad:
-            raise CineHipError(f"kt_sparse_sense: {name} requires grad, but the solver is not differentiable (it runs under torch.no_grad(), "
+            raise CineHipError(f"{what}: {name} requires grad, but the solver is not differentiable (it runs under torch.no_grad(), "
                                f"gradients through the iterations are not built); pass {name}.detach()")
 
 
@@ -112,3 +126,74 @@ class KtSparseSense(nn.Module):
     def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
         return kt_sparse_sense(masked_kspace, mask, sens_maps, iters=self.iters, lam=self.lam, step=self.step, penalise_dc=self.penalise_dc,
                                output=output)
+
+
+def casorati_sigma_max(zf: torch.Tensor) -> torch.Tensor:
+    """The largest singular value of the (h w) x t Casorati matrix of ``zf`` over the batch, one device float: the scale ``lam_l`` is a
+    fraction of.  From ``ops.casorati_gram`` and ``ops.svt_weight``'s info; nothing is read by the host."""
+    zero = torch.zeros(1, device=zf.device, dtype=torch.float32)
+    _, info = ops.svt_weight(ops.casorati_gram(zf), zero)
+    return info[:, 0].amax().to(torch.float32).reshape(1)
+
+
+def low_rank_plus_sparse(masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, iters: int = 50,
+                         lam_l: Union[float, torch.Tensor] = 0.01, lam_s: Union[float, torch.Tensor] = 0.01,
+                         step: Optional[Union[float, torch.Tensor]] = None, output: str = "magnitude", components: bool = False,
+                         record: bool = False):
+    """L+S of ``masked_kspace`` (b, t, c, h, w, 2) with ``mask`` (any numeric 0 / 1 mask that broadcasts, as the models take) and
+    ``sens_maps`` (b, 1, c, h, w, 2): ``iters`` proximal-gradient iterations from L = zf, S = 0; returns L + S.
+
+    ``step``: None = ``0.5 * default_step(sens_maps)``: the data term's gradient in the joint variable (L, S) has Lipschitz constant
+    2 ||A^H M A|| <= 2 max_pixel sum_c |S_c|^2, so with this step an iteration never increases the objective.  A float or a one-element
+    device tensor is used as given; ``step=1.0`` with RSS-normalised maps is Otazo's published iteration and carries no such guarantee.
+    ``lam_l``: a float is a FRACTION of the largest singular value of C(zf) (``casorati_sigma_max``, formed on the device); ``lam_s``: a
+    float is a FRACTION of max |F_t zf| (``temporal_peak``); a one-element device tensor is the absolute weight.  The defaults 0.01 / 0.01
+    are Otazo's cine settings, taken as a convenience; nobody has tuned them here -- choose them per protocol.
+    ``output``: "magnitude" (b, t, h, w) or "complex" (b, t, h, w, 2).  ``components``: also return L and S, complex (b, t, h, w, 2).
+    ``record``: also return rec (iters, 4) device floats -- sum |x_{k+1} - x_k|^2, sum |x_{k+1}|^2, sum |F_t S_{k+1}|, || C(L_{k+1}) ||_* per
+    iteration -- and resid (iters,) float64, the residual the Jacobi eigensolver reached in each iteration.
+    The order of the results: x, [L, S,] [rec, resid].  Nothing is read by the host, so the call can be captured into a graph.
+    Not differentiable; raises ``CineHipError`` for CPU tensors (no fallback) and for an input that requires grad."""
+    cplx = ops.complex_output(output)
+    _no_grad_inputs("low_rank_plus_sparse", masked_kspace=masked_kspace, sens_maps=sens_maps, lam_l=lam_l, lam_s=lam_s, step=step)
+    if int(iters) < 1:
+        raise ValueError(f"low_rank_plus_sparse: iters = {iters}")
+    if not (isinstance(masked_kspace, torch.Tensor) and masked_kspace.is_cuda and isinstance(sens_maps, torch.Tensor) and sens_maps.is_cuda
+            and isinstance(mask, torch.Tensor) and mask.is_cuda):
+        raise CineHipError("low_rank_plus_sparse: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
+    with torch.no_grad():
+        mask = ops.as_mask_u8(mask, masked_kspace)
+        acq = dc.Acquisition(masked_kspace, mask, sens_maps)
+        zf = acq.zero_filled()                                       # (b, t, 1, h, w, 2)
+        dev = zf.device
+        if step is None:
+            step = 0.5 * default_step(sens_maps)
+        elif not isinstance(step, torch.Tensor):
+            step = torch.full((1,), float(step), device=dev, dtype=torch.float32)
+        if not isinstance(lam_l, torch.Tensor):
+            lam_l = casorati_sigma_max(zf) * float(lam_l)
+        if not isinstance(lam_s, torch.Tensor):
+            lam_s = temporal_peak(zf) * float(lam_s)
+        out = ops.ls_solve(zf, sens_maps, mask, step, lam_l, lam_s, int(iters), sens_tiled=acq.tiled, components=components, record=record)
+        out = list(out) if isinstance(out, tuple) else [out]
+        for i in range(3 if components else 1):
+            out[i] = out[i].squeeze(2)
+        out[0] = out[0] if cplx else ops.complex_abs(out[0])
+    return tuple(out) if len(out) > 1 else out[0]
+
+
+class LowRankPlusSparse(nn.Module):
+    """``low_rank_plus_sparse`` as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(LowRankPlusSparse(...).eval())``
+    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included.  The settings are the function's; the default ``lam_l`` and
+    ``lam_s`` are untuned (see there).  Not differentiable."""
+
+    def __init__(self, iters: int = 50, lam_l: Union[float, torch.Tensor] = 0.01, lam_s: Union[float, torch.Tensor] = 0.01,
+                 step: Optional[Union[float, torch.Tensor]] = None):
+        super().__init__()
+        if int(iters) < 1:
+            raise ValueError(f"LowRankPlusSparse: iters = {iters}")
+        self.iters, self.lam_l, self.lam_s, self.step = int(iters), lam_l, lam_s, step
+
+    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
+        return low_rank_plus_sparse(masked_kspace, mask, sens_maps, iters=self.iters, lam_l=self.lam_l, lam_s=self.lam_s, step=self.step,
+                                    output=output)

@@ -778,6 +778,121 @@ def kt_fista(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: tor
     return (x, rec) if record else x
 
 
+LS_REC = 4              # floats of one record row of ls_prox / ls_solve: sum |x_new - x|^2, sum |x_new|^2, sum |F_t S_new|, || C(L_new) ||_*
+LS_INFO = 4             # doubles per batch element of svt_weight: sigma_max, the nuclear norm after thresholding, the Jacobi residual, sweeps
+
+
+def ls_prox_pixels() -> int:
+    """Pixels per workgroup of cine_ls_prox's kernel."""
+    return int(lib().cine_ls_prox_pixels())
+
+
+def _ls_image(x: torch.Tensor, name: str, what: str):
+    _pair(x)
+    x = _dev(x, name)
+    if x.dim() not in (5, 6) or (x.dim() == 6 and x.shape[2] != 1):
+        raise ValueError(f"{what}: {name} {tuple(x.shape)} is not (b, t, [1,] h, w, 2)")
+    return x, (x.shape[0], x.shape[1], x.shape[-3], x.shape[-2])
+
+
+def casorati_gram(a: torch.Tensor, g: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cine_casorati_gram: the (b, t, t) complex128 Gram matrix of the (h w) x t Casorati matrix of v = a - step g (``g`` None: of ``a``),
+    gram[i][j] = sum_pixels conj(v_i) v_j -- exact float32 products added in float64 in a fixed order; exactly Hermitian.  a, g:
+    (b, t, [1,] h, w, 2); ``step``: one device float.  Returns (b, t, t, 2) float64."""
+    a, (b, t, h, w) = _ls_image(a, "a", "casorati_gram")
+    if g is not None:
+        g = _dev(g, "g")
+        if g.numel() != a.numel() or step is None:
+            raise ValueError(f"casorati_gram: g {tuple(g.shape)} does not match a {tuple(a.shape)}, or comes without a step")
+        step = _kt_scalar(step, "step")
+    gram = torch.empty((b, t, t, 2), device=a.device, dtype=torch.float64)
+    nbytes = lib().cine_casorati_gram_ws_bytes(b, t, h, w)
+    ws = _general_ws(nbytes, a.device)
+    check(lib().cine_casorati_gram(a.data_ptr(), _p(g), _p(step) if g is not None else None, gram.data_ptr(), b, t, h, w, _p(ws), nbytes, _stream()),
+          "cine_casorati_gram")
+    return gram
+
+
+def svt_weight(gram: torch.Tensor, thresh: torch.Tensor, step: Optional[torch.Tensor] = None):
+    """cine_svt_weight: W (b, t, t, 2) float32 with SVT(X, th) = X W for X of Gram matrix ``gram`` (b, t, t, 2) float64 and
+    th = step * thresh (``step`` None: thresh), by a Jacobi eigensolver in one workgroup per batch element.  Returns (W, info) with info
+    (b, ``LS_INFO``) float64 on the device: sigma_max, the nuclear norm of X W, the residual reached, the sweeps used."""
+    gram = _dev(gram, "gram", torch.float64)
+    if gram.dim() != 4 or gram.shape[1] != gram.shape[2] or gram.shape[3] != 2:
+        raise ValueError(f"svt_weight: gram {tuple(gram.shape)} is not (b, t, t, 2)")
+    thresh = _kt_scalar(thresh, "thresh")
+    step = None if step is None else _kt_scalar(step, "step")
+    b, t = gram.shape[0], gram.shape[1]
+    weight = torch.empty((b, t, t, 2), device=gram.device, dtype=torch.float32)
+    info = torch.empty((b, LS_INFO), device=gram.device, dtype=torch.float64)
+    check(lib().cine_svt_weight(gram.data_ptr(), thresh.data_ptr(), _p(step), weight.data_ptr(), info.data_ptr(), b, t, _stream()), "cine_svt_weight")
+    return weight, info
+
+
+def ls_prox(l: torch.Tensor, s: torch.Tensor, g: torch.Tensor, weight: torch.Tensor, step: torch.Tensor, thresh_s: torch.Tensor,
+            record: bool = False, lnew: Optional[torch.Tensor] = None, snew: Optional[torch.Tensor] = None):
+    """cine_ls_prox, the proximal half of one L+S iteration in one launch: lnew = (l - step g) W per pixel, snew = F_t^H soft(F_t (s - step g),
+    step thresh_s), xsum = lnew + snew.  l, s, g: (b, t, [1,] h, w, 2); ``weight``: ``svt_weight``'s W; ``step``, ``thresh_s``: one device
+    float each.  ``lnew`` / ``snew``: where to write (``lnew`` may be ``l`` and ``snew`` may be ``s``: in place); new tensors by default.
+    Returns (lnew, snew, xsum), with ``record`` also rec, the ``LS_REC`` device floats of the record (column 3 is 0 here)."""
+    l, (b, t, h, w) = _ls_image(l, "l", "ls_prox")
+    s = _dev(s, "s"); g = _dev(g, "g"); weight = _dev(weight, "weight")
+    step = _kt_scalar(step, "step"); thresh_s = _kt_scalar(thresh_s, "thresh_s")
+    if s.numel() != l.numel() or g.numel() != l.numel() or weight.numel() != b * t * t * 2:
+        raise ValueError(f"ls_prox: s {tuple(s.shape)} / g {tuple(g.shape)} / weight {tuple(weight.shape)} do not match l {tuple(l.shape)}")
+    for o, name in ((lnew, "lnew"), (snew, "snew")):
+        if o is not None and (not o.is_cuda or o.dtype != l.dtype or not o.is_contiguous() or o.numel() != l.numel()):
+            raise CineHipError(f"ls_prox: {name} must be a contiguous float32 GPU tensor of l's size")
+    lnew = torch.empty_like(l) if lnew is None else lnew
+    snew = torch.empty_like(l) if snew is None else snew
+    xsum = torch.empty_like(l)
+    rec = ws = None
+    nbytes = 0
+    if record:
+        rec = torch.empty(LS_REC, device=l.device, dtype=torch.float32)
+        nbytes = lib().cine_ls_prox_ws_bytes(b, t, h, w)
+        ws = _general_ws(nbytes, l.device)
+    check(lib().cine_ls_prox(l.data_ptr(), s.data_ptr(), g.data_ptr(), weight.data_ptr(), step.data_ptr(), thresh_s.data_ptr(), lnew.data_ptr(),
+                             snew.data_ptr(), xsum.data_ptr(), _p(rec), b, t, h, w, _p(ws), nbytes, _stream()), "cine_ls_prox")
+    return (lnew, snew, xsum, rec) if record else (lnew, snew, xsum)
+
+
+def ls_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: torch.Tensor, thresh_l: torch.Tensor, thresh_s: torch.Tensor,
+             iters: int, sens_tiled: Optional[torch.Tensor] = None, components: bool = False, record: bool = False):
+    """cine_ls_solve: ``iters`` proximal-gradient iterations of L+S from L_0 = zf = A^H M y, S_0 = 0 in one C call (``image_dc`` with weights
+    (1, 0, -1), ``casorati_gram``, ``svt_weight``, ``ls_prox`` per iteration).  zf (b, t, [1,] h, w, 2); sens (b, 1, c, h, w, 2); ``mask``:
+    either layout of ``as_mask_u8``; ``step``, ``thresh_l``, ``thresh_s``: one device float each.  Returns x = L + S in zf's shape; with
+    ``components`` (x, L, S); with ``record`` also rec (iters, ``LS_REC``) float32 and resid (iters,) float64, the worst Jacobi residual of
+    each iteration."""
+    _pair(zf); _pair(sens)
+    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
+    step = _kt_scalar(step, "step"); thresh_l = _kt_scalar(thresh_l, "thresh_l"); thresh_s = _kt_scalar(thresh_s, "thresh_s")
+    if sens.dim() != 6:
+        raise ValueError(f"ls_solve: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
+    b, _, c, h, w, _ = sens.shape
+    t = zf.shape[1]
+    layout = mask_layout(mask, sens, t)
+    if zf.numel() != b * t * h * w * 2 or layout is None:
+        raise ValueError(f"ls_solve: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError(f"ls_solve: iters = {iters}")
+    mask_w = 1 if layout == "row" else w
+    x = torch.empty_like(zf)
+    lo = torch.empty_like(zf) if components else None
+    so = torch.empty_like(zf) if components else None
+    rec = torch.empty((iters, LS_REC), device=zf.device, dtype=torch.float32) if record else None
+    resid = torch.empty((iters,), device=zf.device, dtype=torch.float64) if record else None
+    nbytes = lib().cine_ls_solve_ws_bytes(b, t, c, h, w, mask_w, iters)
+    ws = _general_ws(nbytes, zf.device)
+    check(lib().cine_ls_solve(x.data_ptr(), _p(lo), _p(so), zf.data_ptr(), sens.data_ptr(), _p(sens_tiled), mask.data_ptr(), mask_w,
+                              step.data_ptr(), thresh_l.data_ptr(), thresh_s.data_ptr(), iters, _p(rec), _p(resid), b, t, c, h, w,
+                              ws.data_ptr(), nbytes, _stream()), "cine_ls_solve")
+    out = (x, lo, so) if components else (x,)
+    out = out + ((rec, resid) if record else ())
+    return out if len(out) > 1 else x
+
+
 def h_operator(x: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_reg: torch.Tensor,
                _hyb: Optional[torch.Tensor] = None, sens_tiled: Optional[torch.Tensor] = None, literal: bool = False) -> torch.Tensor:
     """CineNet's H = A^H M A + softplus(lambda) I (reference cinenet.py:121-133) for either mask layout: the one-kernel image-space

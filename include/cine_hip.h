@@ -947,6 +947,57 @@ int cine_kt_fista(float* x, const float* zf, const float* sens, const float* sen
                   int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Low-rank plus sparse (L+S, Otazo et al. 2015; no reference counterpart): singular-value thresholding of the (h w) x t Casorati
+ * matrix through its t x t Gram matrix, on the device
+ *     minimise over L, S   1/2 || M A (L + S) - y ||^2 + lam_L || C(L) ||_* + lam_S || F_t S ||_1
+ *     g = A^H M A (L_k + S_k) - zf;   L_{k+1} = SVT(L_k - step g, step lam_L);   S_{k+1} = F_t^H soft(F_t (S_k - step g), step lam_S)
+ * With X = C(v) and G = X^H X = V diag(lam) V^H: SVT(X, th) = X W, W = V diag(h(lam)) V^H, h(lam) = 1 - th / sqrt(lam) for
+ * lam > th^2, else 0.  Limits of all entry points: 2 <= t <= 64 and b <= 65535, else CINE_EUNSUPPORTED; null pointers and non-positive
+ * sizes are CINE_EINVAL, a short workspace CINE_EWORKSPACE.  Every argument is checked before the first launch; no allocation, no
+ * synchronisation, no atomics: capturable, and the same bits on every call.
+ * ------------------------------------------------------------------------------------------ */
+/* gram (b, t, t) complex128 (double pairs, row-major), gram[i][j] = sum over the h w pixels of conj(v_i) v_j with v = a - (*step_dev) g
+ * formed in float32 and never written (g == NULL: v = a, step_dev may be NULL too); a, g: (b, t, h, w, 2).  Every product of two floats
+ * is exact in float64, the sums run in float64 in an order that depends on the shape only (the scheme of cine_coil_gram): exactly
+ * Hermitian with a real diagonal.  A workgroup stages cine_casorati_gram_pixels(t) pixels at a time and the number of workgroups that
+ * leave a record in ws is capped (256 over the batch), so ws stays below 8.2 MiB at t = 64.  gram and ws: 16-byte aligned, aliasing
+ * nothing (CINE_EINVAL). */
+int cine_casorati_gram_pixels(int t);
+size_t cine_casorati_gram_ws_bytes(int b, int t, int h, int w);
+int cine_casorati_gram(const float* a, const float* g, const float* step_dev, double* gram, int b, int t, int h, int w,
+                       void* ws, size_t ws_bytes, void* stream);
+/* weight (b, t, t) complex64 = W of gram (b, t, t) complex128 for th = (*step_dev) (*thresh_dev) (step_dev == NULL: th = *thresh_dev).
+ * One workgroup per batch element: the matrix and the eigenvector accumulator in LDS in float64, a cyclic Jacobi eigensolver for complex
+ * Hermitian matrices with round-robin pairs, sweeping until max |off-diagonal| <= 1e-14 max |diagonal| or 40 sweeps (a NaN input ends at
+ * the cap).  info (b, 4) doubles: sigma_max = sqrt(lam_max), the nuclear norm sum_i sqrt(lam_i) h(lam_i) of X W, the residual
+ * max |off-diagonal| / max |diagonal| reached, the sweeps used.  W is exactly Hermitian; it is unique only off the null space of gram. */
+int cine_svt_weight(const double* gram, const float* thresh_dev, const float* step_dev, float* weight, double* info, int b, int t,
+                    void* stream);
+/* The proximal half of an iteration in one launch.  l, s, g, lnew, snew, xsum: (b, t, h, w, 2); weight: cine_svt_weight's W of
+ * cine_casorati_gram(l, g, step_dev).  Per pixel, with v_L = l - (*step_dev) g and v_S = s - (*step_dev) g:
+ *     lnew[t'] = sum_t v_L[t] W[t][t'];   snew = F_t^H soft(F_t v_S, (*step_dev) (*thresh_s_dev));   xsum = lnew + snew
+ * rec != NULL: 4 device floats = sum |xsum - (l + s)|^2, sum |xsum|^2, sum |F_t snew|, 0, from per-workgroup partial sums in ws
+ * (cine_ls_prox_ws_bytes; ws may be NULL without rec) added in float64 in a fixed order by a second launch.  A workgroup owns all
+ * frames of cine_ls_prox_pixels() consecutive pixels and reads before it writes: lnew may alias l and snew may alias s; any other
+ * aliasing of an output is CINE_EINVAL. */
+int cine_ls_prox_pixels(void);
+size_t cine_ls_prox_ws_bytes(int b, int t, int h, int w);
+int cine_ls_prox(const float* l, const float* s, const float* g, const float* weight, const float* step_dev,
+                 const float* thresh_s_dev, float* lnew, float* snew, float* xsum, float* rec,
+                 int b, int t, int h, int w, void* ws, size_t ws_bytes, void* stream);
+/* The whole solve in one call: L_0 = zf, S_0 = 0, and for k = 0 .. iters - 1 the operator (cine_image_dc_t for mask_w == 1,
+ * cine_image_dc_general for mask_w == w; sens_tiled as cine_kt_fista), cine_casorati_gram(L_k, g), cine_svt_weight with thresh_l_dev,
+ * cine_ls_prox with thresh_s_dev.  x (out) = L + S; l_out, s_out: the components, or NULL; rec: (iters, 4) floats or NULL, a row of
+ * cine_ls_prox's record per iteration with column 3 = the nuclear norm of L_{k+1} (info, added over the batch); resid: (iters) doubles or
+ * NULL (only with rec), the worst Jacobi residual of each iteration.  x, l_out, s_out and rec equal, bit for bit, what the caller gets
+ * from the entry points iterated by hand.  ws: cine_ls_solve_ws_bytes(), 16-byte aligned.  The operator is called first and refuses what
+ * it does not accept (h, w, c) before anything is launched. */
+size_t cine_ls_solve_ws_bytes(int b, int t, int c, int h, int w, int mask_w, int iters);
+int cine_ls_solve(float* x, float* l_out, float* s_out, const float* zf, const float* sens, const float* sens_tiled,
+                  const uint8_t* mask, int mask_w, const float* step_dev, const float* thresh_l_dev, const float* thresh_s_dev,
+                  int iters, float* rec, double* resid, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement aid (no reference counterpart; the reference only wraps time.time() around the
  * model call, traintest_scripts/run_inference.py:53-61)
  * ------------------------------------------------------------------------------------------ */
