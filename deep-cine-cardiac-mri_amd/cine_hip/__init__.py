@@ -34,9 +34,11 @@ _hw_queue_default()
 
 from . import synth  # noqa: F401,E402  (host-only, numpy)
 
-__all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse"]
+__all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
+           "TotalVariation"]
 
-_CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse")
+_CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
+              "TotalVariation")
 
 
 def __getattr__(name):

@@ -1,5 +1,5 @@
-"""Reconstruction without trained weights: k-t SPARSE-SENSE and low-rank plus sparse (L+S), the compressed-sensing baselines on the
-package's own operators.
+"""Reconstruction without trained weights: k-t SPARSE-SENSE, low-rank plus sparse (L+S) and spatio-temporal total variation (TV), the
+compressed-sensing baselines on the package's own operators.
 
     minimise over x   1/2 || M A x - y ||^2  +  lam || w F_t x ||_1
 
@@ -27,8 +27,22 @@ diagonalised by a Jacobi eigensolver in one workgroup (``ops.svt_weight``) and i
 proximal kernel (``ops.ls_prox``).  One ``ops.ls_solve`` call runs all iterations with nothing read by the host.  ``LowRankPlusSparse`` is
 the module, as ``KtSparseSense``.
 
-Not built: CG-SENSE with a Tikhonov weight (``ops.conj_grad`` solves it for callers who want it), total-variation regularisers, and
-gradients through the solvers (they are not differentiable).
+Spatio-temporal total variation: per batch element, over x,
+
+    minimise   1/2 || M A x - y ||^2  +  lam_t || D_t x ||_1  +  lam_s sum_pixels sqrt(|D_h x|^2 + |D_w x|^2)
+
+with ``D_t`` the forward difference along the frames (wrapping from the last frame to the first with ``periodic``, 0 at the last frame
+otherwise) and ``D_h``, ``D_w`` the forward differences along h and w (0 at the last row / column); the spatial term is isotropic.
+Condat-Vu primal-dual (Condat 2013, Vu 2013) from x_0 = zf, p_0 = 0 with the dual p = (p_t, p_h, p_w):
+
+    g = A^H M A x_k - zf;   x_{k+1} = x_k - tau (g + D^H p_k);   p_{k+1} = P(p_k + sigma D (2 x_{k+1} - x_k))
+
+``P`` projects p_t onto the ball of radius lam_t and (p_h, p_w) jointly onto the ball of radius lam_s.  Everything after g is one launch
+(``ops.tv_pd_step``: a spatial stencil with a recomputed one-pixel halo), one ``ops.tv_solve`` call runs all iterations with nothing read
+by the host.  The objective is not monotone under this iteration.  ``TotalVariation`` is the module, as ``KtSparseSense``.
+
+Not built: CG-SENSE with a Tikhonov weight (``ops.conj_grad`` solves it for callers who want it), second-order (TGV) and anisotropic
+spatial penalties, and gradients through the solvers (they are not differentiable).
 """
 from typing import Optional, Union
 
@@ -39,7 +53,8 @@ from torch import nn
 from . import dc, ops
 from ._lib import CineHipError
 
-__all__ = ["fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse"]
+__all__ = ["fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "tv_peaks", "total_variation",
+           "TotalVariation"]
 
 
 def fista_momentum(iters: int) -> np.ndarray:
@@ -197,3 +212,98 @@ class LowRankPlusSparse(nn.Module):
     def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
         return low_rank_plus_sparse(masked_kspace, mask, sens_maps, iters=self.iters, lam_l=self.lam_l, lam_s=self.lam_s, step=self.step,
                                     output=output)
+
+
+def tv_peaks(zf: torch.Tensor, periodic: bool = True):
+    """(max |D_t zf|, max sqrt(|D_h zf|^2 + |D_w zf|^2)), one device float each: the scales ``lam_t`` and ``lam_s`` are fractions of.  zf:
+    (b, t, [1,] h, w, 2).  Plain torch, once per solve; nothing is read by the host."""
+    b, t, h, w = zf.shape[0], zf.shape[1], zf.shape[-3], zf.shape[-2]
+    x = zf.reshape(b, t, h, w, 2)
+    dt = x.roll(-1, dims=1) - x
+    if not periodic:
+        dt = dt[:, :-1]
+    dh = torch.zeros_like(x)
+    dw = torch.zeros_like(x)
+    dh[:, :, :-1] = x[:, :, 1:] - x[:, :, :-1]
+    dw[:, :, :, :-1] = x[:, :, :, 1:] - x[:, :, :, :-1]
+    peak_t = (dt * dt).sum(dim=-1).amax().sqrt().reshape(1)
+    peak_s = ((dh * dh).sum(dim=-1) + (dw * dw).sum(dim=-1)).amax().sqrt().reshape(1)
+    return peak_t, peak_s
+
+
+def total_variation(masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, iters: int = 50,
+                    lam_t: Union[float, torch.Tensor] = 0.02, lam_s: Union[float, torch.Tensor] = 0.01,
+                    step: Optional[Union[float, torch.Tensor]] = None, sigma: Optional[Union[float, torch.Tensor]] = None,
+                    periodic: bool = True, output: str = "magnitude", record: bool = False, dual: bool = False):
+    """Spatio-temporal total variation of ``masked_kspace`` (b, t, c, h, w, 2) with ``mask`` (any numeric 0 / 1 mask that broadcasts, as the
+    models take) and ``sens_maps`` (b, 1, c, h, w, 2): ``iters`` Condat-Vu iterations from x = zf, p = 0.
+
+    ``lam_t`` / ``lam_s``: a float is a FRACTION of max |D_t zf| / max sqrt(|D_h zf|^2 + |D_w zf|^2) (``tv_peaks``, formed on the device);
+    a one-element device tensor is the absolute weight; the float 0 switches the term off (its dual planes are then neither allocated nor
+    touched); both off raises ``ValueError``.  The defaults 0.02 / 0.01 are a convenience that gives a sensible picture on the synthetic
+    phantom; nobody has tuned them on real data -- choose them per protocol.
+    ``step`` (tau): None = ``default_step(sens_maps)`` = 1 / max sum_c |S_c|^2 <= 1 / ||A^H M A||.  ``sigma``: None = 1 / (2 tau B) with
+    B = 4 [temporal on] + 8 [spatial on] >= ||D||^2, which gives 1 / tau - sigma ||D||^2 >= ||A^H M A|| / 2, Condat's condition.  A float
+    or a one-element device tensor is used as given.  The objective is not monotone under this iteration.
+    ``periodic``: D_t wraps from the last frame to the first (a cine is one cardiac cycle); False: its last difference is 0.
+    ``output``: "magnitude" (b, t, h, w) or "complex" (b, t, h, w, 2).  ``dual``: also return the final p (3, b, t, h, w, 2) = (p_t, p_h,
+    p_w), zeros in the planes of a term that is off.  ``record``: also return rec (iters, 4) device floats -- sum |x_{k+1} - x_k|^2,
+    sum |x_{k+1}|^2, sum |D_t x_{k+1}|, sum sqrt(|D_h x_{k+1}|^2 + |D_w x_{k+1}|^2) per iteration (0 for a term that is off).
+    The order of the results: x, [p,] [rec].  Nothing is read by the host, so the call can be captured into a graph.
+    Not differentiable; raises ``CineHipError`` for CPU tensors (no fallback) and for an input that requires grad."""
+    cplx = ops.complex_output(output)
+    _no_grad_inputs("total_variation", masked_kspace=masked_kspace, sens_maps=sens_maps, lam_t=lam_t, lam_s=lam_s, step=step, sigma=sigma)
+    if int(iters) < 1:
+        raise ValueError(f"total_variation: iters = {iters}")
+    terms = (0 if not isinstance(lam_t, torch.Tensor) and float(lam_t) == 0.0 else ops.TV_TEMPORAL) | \
+            (0 if not isinstance(lam_s, torch.Tensor) and float(lam_s) == 0.0 else ops.TV_SPATIAL)
+    if terms == 0:
+        raise ValueError("total_variation: lam_t and lam_s are both 0, no term is left")
+    if not (isinstance(masked_kspace, torch.Tensor) and masked_kspace.is_cuda and isinstance(sens_maps, torch.Tensor) and sens_maps.is_cuda
+            and isinstance(mask, torch.Tensor) and mask.is_cuda):
+        raise CineHipError("total_variation: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
+    with torch.no_grad():
+        mask = ops.as_mask_u8(mask, masked_kspace)
+        acq = dc.Acquisition(masked_kspace, mask, sens_maps)
+        zf = acq.zero_filled()                                       # (b, t, 1, h, w, 2)
+        dev = zf.device
+        if step is None:
+            step = default_step(sens_maps)
+        elif not isinstance(step, torch.Tensor):
+            step = torch.full((1,), float(step), device=dev, dtype=torch.float32)
+        if sigma is None:
+            bound = 4.0 * bool(terms & ops.TV_TEMPORAL) + 8.0 * bool(terms & ops.TV_SPATIAL)
+            sigma = (step * (2.0 * bound)).reciprocal()
+        elif not isinstance(sigma, torch.Tensor):
+            sigma = torch.full((1,), float(sigma), device=dev, dtype=torch.float32)
+        if not (isinstance(lam_t, torch.Tensor) and isinstance(lam_s, torch.Tensor)):
+            peak_t, peak_s = tv_peaks(zf, periodic)
+            if not isinstance(lam_t, torch.Tensor):
+                lam_t = peak_t * float(lam_t) if terms & ops.TV_TEMPORAL else None
+            if not isinstance(lam_s, torch.Tensor):
+                lam_s = peak_s * float(lam_s) if terms & ops.TV_SPATIAL else None
+        out = ops.tv_solve(zf, sens_maps, mask, step, sigma, lam_t, lam_s, int(iters), terms=terms, periodic=periodic, sens_tiled=acq.tiled,
+                           record=record, dual=dual)
+        out = list(out) if isinstance(out, tuple) else [out]
+        out[0] = out[0].squeeze(2)
+        if dual:
+            out[1] = out[1].squeeze(3)
+        out[0] = out[0] if cplx else ops.complex_abs(out[0])
+    return tuple(out) if len(out) > 1 else out[0]
+
+
+class TotalVariation(nn.Module):
+    """``total_variation`` as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(TotalVariation(...).eval())``
+    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included.  The settings are the function's; the default ``lam_t``
+    and ``lam_s`` are untuned (see there).  Not differentiable."""
+
+    def __init__(self, iters: int = 50, lam_t: Union[float, torch.Tensor] = 0.02, lam_s: Union[float, torch.Tensor] = 0.01,
+                 step: Optional[Union[float, torch.Tensor]] = None, sigma: Optional[Union[float, torch.Tensor]] = None, periodic: bool = True):
+        super().__init__()
+        if int(iters) < 1:
+            raise ValueError(f"TotalVariation: iters = {iters}")
+        self.iters, self.lam_t, self.lam_s, self.step, self.sigma, self.periodic = int(iters), lam_t, lam_s, step, sigma, bool(periodic)
+
+    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
+        return total_variation(masked_kspace, mask, sens_maps, iters=self.iters, lam_t=self.lam_t, lam_s=self.lam_s, step=self.step,
+                               sigma=self.sigma, periodic=self.periodic, output=output)

@@ -893,6 +893,104 @@ def ls_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: tor
     return out if len(out) > 1 else x
 
 
+TV_REC = 4              # floats of one record row of tv_pd_step / tv_solve: sum |x_new - x|^2, sum |x_new|^2, sum |D_t x_new|, sum |(D_h, D_w) x_new|
+TV_TEMPORAL, TV_SPATIAL = 1, 2          # the bits of ``terms``
+
+
+def tv_pd_tile():
+    """(rows, columns) of the spatial tile of cine_tv_pd_step's kernel: the seams the shape sweeps of the tests aim at."""
+    import ctypes
+    th, tw = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().cine_tv_pd_tile(ctypes.byref(th), ctypes.byref(tw)), "cine_tv_pd_tile")
+    return th.value, tw.value
+
+
+def _tv_terms(terms, what: str) -> int:
+    terms = int(terms)
+    if terms not in (1, 2, 3):
+        raise ValueError(f"{what}: terms = {terms} is not 1 (temporal), 2 (spatial) or 3 (both)")
+    return terms
+
+
+def _tv_dual(p: torch.Tensor, name: str, what: str, x: torch.Tensor) -> torch.Tensor:
+    p = _dev(p, name)
+    if p.dim() < 1 or p.shape[0] != 3 or p.numel() != 3 * x.numel():
+        raise ValueError(f"{what}: {name} {tuple(p.shape)} is not (3,) + x's shape {tuple(x.shape)}")
+    return p
+
+
+def tv_pd_step(x: torch.Tensor, g: torch.Tensor, p: torch.Tensor, tau: torch.Tensor, sigma: torch.Tensor,
+               lam_t: Optional[torch.Tensor], lam_s: Optional[torch.Tensor], terms: int = 3, periodic: bool = True, record: bool = False,
+               xnew: Optional[torch.Tensor] = None, pnew: Optional[torch.Tensor] = None):
+    """cine_tv_pd_step, everything after the gradient of one Condat-Vu iteration of spatio-temporal TV in one launch:
+    xnew = x - tau (g + D^H p), pnew = P(p + sigma D (2 xnew - x)).  x, g: (b, t, [1,] h, w, 2); p: (3,) + x's shape = (p_t, p_h, p_w);
+    ``tau``, ``sigma``, ``lam_t``, ``lam_s``: one device float each (the ``lam`` of a term that is off may be None).  ``terms``: 1 temporal,
+    2 spatial, 3 both; the planes of a term that is off are neither read nor written (a ``pnew`` made here holds zeros there).
+    ``xnew`` / ``pnew``: where to write; never an operand -- workgroups read across each other's seams.
+    Returns (xnew, pnew), with ``record`` (xnew, pnew, rec) with rec the ``TV_REC`` device floats of the record."""
+    x, (b, t, h, w) = _ls_image(x, "x", "tv_pd_step")
+    terms = _tv_terms(terms, "tv_pd_step")
+    g = _dev(g, "g"); p = _tv_dual(p, "p", "tv_pd_step", x)
+    tau = _kt_scalar(tau, "tau"); sigma = _kt_scalar(sigma, "sigma")
+    lam_t = _kt_scalar(lam_t, "lam_t") if terms & TV_TEMPORAL else None
+    lam_s = _kt_scalar(lam_s, "lam_s") if terms & TV_SPATIAL else None
+    if g.numel() != x.numel():
+        raise ValueError(f"tv_pd_step: g {tuple(g.shape)} does not match x {tuple(x.shape)}")
+    for o, name, n in ((xnew, "xnew", x.numel()), (pnew, "pnew", p.numel())):
+        if o is not None and (not o.is_cuda or o.dtype != x.dtype or not o.is_contiguous() or o.numel() != n):
+            raise CineHipError(f"tv_pd_step: {name} must be a contiguous float32 GPU tensor of the size of its operand")
+    xnew = torch.empty_like(x) if xnew is None else xnew
+    if pnew is None:
+        pnew = torch.empty_like(p) if terms == 3 else torch.zeros_like(p)
+    rec = ws = None
+    nbytes = 0
+    if record:
+        rec = torch.empty(TV_REC, device=x.device, dtype=torch.float32)
+        nbytes = lib().cine_tv_pd_ws_bytes(b, t, h, w)
+        ws = _general_ws(nbytes, x.device)
+    check(lib().cine_tv_pd_step(x.data_ptr(), g.data_ptr(), p.data_ptr(), tau.data_ptr(), sigma.data_ptr(), _p(lam_t), _p(lam_s), terms,
+                                int(bool(periodic)), xnew.data_ptr(), pnew.data_ptr(), _p(rec), b, t, h, w, _p(ws), nbytes, _stream()),
+          "cine_tv_pd_step")
+    return (xnew, pnew, rec) if record else (xnew, pnew)
+
+
+def tv_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, tau: torch.Tensor, sigma: torch.Tensor,
+             lam_t: Optional[torch.Tensor], lam_s: Optional[torch.Tensor], iters: int, terms: int = 3, periodic: bool = True,
+             sens_tiled: Optional[torch.Tensor] = None, record: bool = False, dual: bool = False):
+    """cine_tv_solve: ``iters`` Condat-Vu iterations of spatio-temporal TV from x_0 = zf = A^H M y, p_0 = 0 in one C call (``image_dc`` with
+    weights (1, 0, -1), then ``tv_pd_step``, per iteration).  zf (b, t, [1,] h, w, 2); sens (b, 1, c, h, w, 2); ``mask``: either layout of
+    ``as_mask_u8``; ``tau``, ``sigma``, ``lam_t``, ``lam_s``: one device float each (the ``lam`` of a term that is off may be None).
+    Returns x in zf's shape; with ``dual`` also the final p, (3,) + zf's shape, zeros in the planes of a term that is off; with ``record``
+    also rec (iters, ``TV_REC``).  The order of the results: x, [p,] [rec]."""
+    _pair(zf); _pair(sens)
+    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
+    terms = _tv_terms(terms, "tv_solve")
+    tau = _kt_scalar(tau, "tau"); sigma = _kt_scalar(sigma, "sigma")
+    lam_t = _kt_scalar(lam_t, "lam_t") if terms & TV_TEMPORAL else None
+    lam_s = _kt_scalar(lam_s, "lam_s") if terms & TV_SPATIAL else None
+    if sens.dim() != 6:
+        raise ValueError(f"tv_solve: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
+    b, _, c, h, w, _ = sens.shape
+    t = zf.shape[1]
+    layout = mask_layout(mask, sens, t)
+    if zf.numel() != b * t * h * w * 2 or layout is None:
+        raise ValueError(f"tv_solve: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError(f"tv_solve: iters = {iters}")
+    mask_w = 1 if layout == "row" else w
+    x = torch.empty_like(zf)
+    p_out = torch.empty((3,) + tuple(zf.shape), device=zf.device, dtype=zf.dtype) if dual else None
+    rec = torch.empty((iters, TV_REC), device=zf.device, dtype=torch.float32) if record else None
+    nbytes = lib().cine_tv_solve_ws_bytes(b, t, c, h, w, mask_w, iters)
+    ws = _general_ws(nbytes, zf.device)
+    check(lib().cine_tv_solve(x.data_ptr(), zf.data_ptr(), sens.data_ptr(), _p(sens_tiled), mask.data_ptr(), mask_w, tau.data_ptr(),
+                              sigma.data_ptr(), _p(lam_t), _p(lam_s), terms, int(bool(periodic)), iters, _p(rec), _p(p_out), b, t, c, h, w,
+                              ws.data_ptr(), nbytes, _stream()), "cine_tv_solve")
+    out = (x,) + ((p_out,) if dual else ()) + ((rec,) if record else ())
+    return out if len(out) > 1 else x
+
+
 def h_operator(x: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, lambda_reg: torch.Tensor,
                _hyb: Optional[torch.Tensor] = None, sens_tiled: Optional[torch.Tensor] = None, literal: bool = False) -> torch.Tensor:
     """CineNet's H = A^H M A + softplus(lambda) I (reference cinenet.py:121-133) for either mask layout: the one-kernel image-space

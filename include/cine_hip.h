@@ -998,6 +998,44 @@ int cine_ls_solve(float* x, float* l_out, float* s_out, const float* zf, const f
                   int iters, float* rec, double* resid, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * spatio-temporal total variation (no reference counterpart: the third weight-free baseline, on the same operators)
+ *     minimise  1/2 || M A x - y ||^2  +  lam_t || D_t x ||_1  +  lam_s sum_pixels sqrt(|D_h x|^2 + |D_w x|^2)
+ * D_t: x[t + 1] - x[t], wrapping from the last frame to the first with periodic != 0, 0 at the last frame otherwise; D_h, D_w: forward
+ * differences, 0 at the last row / column.  The dual variable p = (p_t, p_h, p_w) is (3, b, t, h, w, 2).
+ * ------------------------------------------------------------------------------------------ */
+/* One Condat-Vu primal-dual iteration after the data term's gradient g = A^H M A x - zf, in one launch:
+ *     xnew = x - tau (g + D^H p);   pnew = P(p + sigma D (2 xnew - x))
+ *     P: p_t <- p_t / max(1, |p_t| / lam_t);   (p_h, p_w) <- (p_h, p_w) / max(1, sqrt(|p_h|^2 + |p_w|^2) / lam_s)
+ * with D^H the exact adjoint of D.  x, g, xnew: (b, t, h, w, 2); p, pnew: (3, b, t, h, w, 2); tau_dev, sigma_dev, lam_t_dev, lam_s_dev:
+ * one float each in device memory (nothing waits for the host).  terms: 1 = temporal, 2 = spatial, 3 = both; the planes of p and pnew
+ * of a term that is off are neither read nor written, and its lam pointer may be NULL.
+ * rec != NULL: 4 device floats = sum |xnew - x|^2, sum |xnew|^2, sum |D_t xnew|, sum sqrt(|D_h xnew|^2 + |D_w xnew|^2) (the sum of a
+ * term that is off is 0) -- per-workgroup partial sums over the pixels a workgroup owns in ws (cine_tv_pd_ws_bytes; ws may be NULL
+ * without rec), added in float64 in a fixed order by a second launch: the same bits on every call.
+ * A workgroup owns a tile of cine_tv_pd_tile() pixels and recomputes xnew on a one-pixel halo from x, g and p across the seams, so
+ * nothing is in place: xnew and pnew aliasing an operand or each other is CINE_EINVAL, as are null pointers, non-positive sizes and
+ * terms outside 1 .. 3.  2 <= t <= 64 and b <= 65535, else CINE_EUNSUPPORTED; any h, w >= 1; a short workspace is CINE_EWORKSPACE.
+ * Every argument is checked before the first launch; no allocation, no synchronisation, no atomics. */
+int cine_tv_pd_tile(int* th, int* tw);
+size_t cine_tv_pd_ws_bytes(int b, int t, int h, int w);
+int cine_tv_pd_step(const float* x, const float* g, const float* p, const float* tau_dev, const float* sigma_dev,
+                    const float* lam_t_dev, const float* lam_s_dev, int terms, int periodic, float* xnew, float* pnew, float* rec,
+                    int b, int t, int h, int w, void* ws, size_t ws_bytes, void* stream);
+/* The whole solve in one call: x_0 = zf, p_0 = 0, and for k = 0 .. iters - 1 the operator (cine_image_dc_t for mask_w == 1: mask
+ * (b, t, h); cine_image_dc_general for mask_w == w: (b, t, h, w); sens_tiled as cine_kt_fista) and cine_tv_pd_step.  x (out), zf:
+ * (b, t, h, w, 2).  The iterates alternate between x and the workspace, the duals between two sets of planes in the workspace that hold
+ * only the planes of the terms that are on.  rec: (iters, 4) device floats, one row of cine_tv_pd_step's record per iteration (all
+ * rows are added up in one launch at the end), or NULL.  p_out: the final dual (3, b, t, h, w, 2) with zeros in the planes of a term
+ * that is off, or NULL.  x, rec and p_out equal, bit for bit, what the caller gets from the two entry points iterated by hand.
+ * ws: cine_tv_solve_ws_bytes() = the operator's scratch, g, one image, two sets of three planes and the partial sums.  iters >= 1,
+ * c > 0, mask_w in {1, w}, terms in 1 .. 3, x / rec / p_out / ws aliasing nothing (CINE_EINVAL); t and b as cine_tv_pd_step; h, w, c:
+ * what the operator accepts -- it is called first and refuses before anything is launched. */
+size_t cine_tv_solve_ws_bytes(int b, int t, int c, int h, int w, int mask_w, int iters);
+int cine_tv_solve(float* x, const float* zf, const float* sens, const float* sens_tiled, const uint8_t* mask, int mask_w,
+                  const float* tau_dev, const float* sigma_dev, const float* lam_t_dev, const float* lam_s_dev, int terms, int periodic,
+                  int iters, float* rec, float* p_out, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement aid (no reference counterpart; the reference only wraps time.time() around the
  * model call, traintest_scripts/run_inference.py:53-61)
  * ------------------------------------------------------------------------------------------ */
