@@ -35,10 +35,10 @@ _hw_queue_default()
 from . import synth  # noqa: F401,E402  (host-only, numpy)
 
 __all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
-           "TotalVariation"]
+           "TotalVariation", "locally_low_rank", "LocallyLowRank"]
 
 _CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
-              "TotalVariation")
+              "TotalVariation", "locally_low_rank", "LocallyLowRank")
 
 
 def __getattr__(name):

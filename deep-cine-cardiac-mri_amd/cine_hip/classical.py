@@ -1,5 +1,5 @@
-"""Reconstruction without trained weights: k-t SPARSE-SENSE, low-rank plus sparse (L+S) and spatio-temporal total variation (TV), the
-compressed-sensing baselines on the package's own operators.
+"""Reconstruction without trained weights: k-t SPARSE-SENSE, low-rank plus sparse (L+S), spatio-temporal total variation (TV) and locally
+low-rank (LLR), the compressed-sensing baselines on the package's own operators.
 
     minimise over x   1/2 || M A x - y ||^2  +  lam || w F_t x ||_1
 
@@ -41,8 +41,24 @@ Condat-Vu primal-dual (Condat 2013, Vu 2013) from x_0 = zf, p_0 = 0 with the dua
 (``ops.tv_pd_step``: a spatial stencil with a recomputed one-pixel halo), one ``ops.tv_solve`` call runs all iterations with nothing read
 by the host.  The objective is not monotone under this iteration.  ``TotalVariation`` is the module, as ``KtSparseSense``.
 
+Locally low-rank (Trzasko & Manduca 2011; Zhang et al. 2015; the usual dynamic baseline of BART's ``pics``): per batch element, over x,
+
+    minimise   1/2 || M A x - y ||^2  +  lam sum over the blocks beta of P of || C_beta(x) ||_*
+
+with ``C_beta(x)`` the (pixels of beta) x t Casorati matrix of the spatial block beta and ``P`` a partition of the image into
+``block`` x ``block`` squares whose grid origin lies at (-shift_h, -shift_w), clipped to the image (no wrap-around).  Proximal gradient
+without momentum from x_0 = zf, the partition shifted from iteration to iteration ("cycle spinning", which removes the block seams):
+
+    g = A^H M A x_k - zf;   x_{k+1} = BlockSVT_{P_k}(x_k - step g, step lam)
+
+Every block has a t x t eigenproblem of its own, so the step, the Gram matrix, the Jacobi eigensolver, the thresholding and the
+application are ONE launch with a workgroup per block (``ops.llr_prox``); one ``ops.llr_solve`` call runs all iterations with nothing read
+by the host.  With a fixed partition this is ISTA and the objective never increases at the default step; with shifts the regulariser
+changes per iteration and no such statement holds.  ``LocallyLowRank`` is the module, as ``KtSparseSense``.
+
 Not built: CG-SENSE with a Tikhonov weight (``ops.conj_grad`` solves it for callers who want it), second-order (TGV) and anisotropic
-spatial penalties, and gradients through the solvers (they are not differentiable).
+spatial penalties, overlapping blocks, momentum and multi-scale low rank for LLR, and gradients through the solvers (they are not
+differentiable).
 """
 from typing import Optional, Union
 
@@ -54,7 +70,7 @@ from . import dc, ops
 from ._lib import CineHipError
 
 __all__ = ["fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "tv_peaks", "total_variation",
-           "TotalVariation"]
+           "TotalVariation", "llr_shifts", "block_sigma_max", "locally_low_rank", "LocallyLowRank"]
 
 
 def fista_momentum(iters: int) -> np.ndarray:
@@ -307,3 +323,96 @@ class TotalVariation(nn.Module):
     def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
         return total_variation(masked_kspace, mask, sens_maps, iters=self.iters, lam_t=self.lam_t, lam_s=self.lam_s, step=self.step,
                                sigma=self.sigma, periodic=self.periodic, output=output)
+
+
+def llr_shifts(iters: int, block: int, seed: int = 0) -> np.ndarray:
+    """The partition shifts of ``locally_low_rank(shifts="random")``: (iters, 2) int32 = ``np.random.RandomState(seed).randint(0, block,
+    size=(iters, 2))``, row k = (shift_h, shift_w) of iteration k.  This sequence is the contract: the float64 yardstick of the tests draws
+    the same one."""
+    return np.random.RandomState(int(seed)).randint(0, int(block), size=(int(iters), 2)).astype(np.int32)
+
+
+def block_sigma_max(zf: torch.Tensor, block: int) -> torch.Tensor:
+    """The largest singular value over all ``block`` x ``block`` blocks (shift (0, 0)) of ``zf`` (b, t, [1,] h, w, 2) and over the batch, one
+    device float: the scale ``lam`` is a fraction of.  Formed on the device by ``ops.llr_prox`` with no image output; nothing is read by
+    the host."""
+    zero = torch.zeros(1, device=zf.device, dtype=torch.float32)
+    _, info = ops.llr_prox(zf, None, None, zero, block, image=False)
+    return info[0].to(torch.float32).reshape(1)
+
+
+def _llr_settings(what: str, iters, block, shifts):
+    """(iters, block, the (iters, 2) int32 host array or None) of ``locally_low_rank`` / ``LocallyLowRank``, validated on the host."""
+    if int(iters) < 1:
+        raise ValueError(f"{what}: iters = {iters}")
+    iters, block = int(iters), int(block)
+    if not ops.LLR_MIN_BLOCK <= block <= ops.LLR_MAX_BLOCK:
+        raise ValueError(f"{what}: block = {block} is outside {ops.LLR_MIN_BLOCK} .. {ops.LLR_MAX_BLOCK}")
+    if shifts is None or (isinstance(shifts, str) and shifts == "fixed"):
+        return iters, block, None
+    if isinstance(shifts, str):
+        if shifts != "random":
+            raise ValueError(f'{what}: shifts = {shifts!r} is not "random", "fixed", None or an (iters, 2) integer array')
+        return iters, block, llr_shifts(iters, block, 0)
+    return iters, block, ops.llr_shift_array(shifts, iters, block, what)
+
+
+def locally_low_rank(masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, iters: int = 30,
+                     lam: Union[float, torch.Tensor] = 0.005, block: int = 8, shifts="random",
+                     step: Optional[Union[float, torch.Tensor]] = None, output: str = "magnitude", record: bool = False):
+    """Locally low-rank reconstruction of ``masked_kspace`` (b, t, c, h, w, 2) with ``mask`` (any numeric 0 / 1 mask that broadcasts, as the
+    models take) and ``sens_maps`` (b, 1, c, h, w, 2): ``iters`` proximal-gradient iterations from x = zf.
+
+    ``block``: the side of the square blocks, 2 .. 16 (no power of two needed).  ``shifts``: "random" = ``llr_shifts(iters, block, 0)``, a
+    seeded partition shift per iteration; None or "fixed" = the unshifted partition in every iteration; an (iters, 2) integer array with
+    entries in [0, block) is used as given (validated on the host, ``ValueError``).
+    ``step``: None = ``default_step(sens_maps)`` <= 1 / ||A^H M A||; a float or a one-element device tensor is used as given.  With a fixed
+    partition the iteration is ISTA and never increases the objective at that step; with shifts the regulariser changes from iteration to
+    iteration and no such statement holds.
+    ``lam``: a float is a FRACTION of ``block_sigma_max(zf, block)`` (formed on the device); a one-element device tensor is the absolute
+    weight.  The default 0.005 is the best of a few values tried on the synthetic phantom; nobody has tuned it on real data -- choose it per
+    protocol.
+    ``output``: "magnitude" (b, t, h, w) or "complex" (b, t, h, w, 2).  ``record``: also return rec (iters, 4) device floats --
+    sum |x_{k+1} - x_k|^2, sum |x_{k+1}|^2, sum over the blocks of || C_beta(x_{k+1}) ||_*, 0 per iteration -- and info (iters, 4) float64:
+    the largest block sigma_max of the iteration's operand, the worst residual and the most sweeps of the Jacobi eigensolver, the number of
+    blocks.  The order of the results: x, [rec, info].  Nothing is read by the host, so the call can be captured into a graph; a replayed
+    graph replays the shift sequence it was captured with.
+    Not differentiable; raises ``CineHipError`` for CPU tensors (no fallback) and for an input that requires grad."""
+    cplx = ops.complex_output(output)
+    _no_grad_inputs("locally_low_rank", masked_kspace=masked_kspace, sens_maps=sens_maps, lam=lam, step=step)
+    iters, block, host_shifts = _llr_settings("locally_low_rank", iters, block, shifts)
+    if not (isinstance(masked_kspace, torch.Tensor) and masked_kspace.is_cuda and isinstance(sens_maps, torch.Tensor) and sens_maps.is_cuda
+            and isinstance(mask, torch.Tensor) and mask.is_cuda):
+        raise CineHipError("locally_low_rank: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
+    with torch.no_grad():
+        mask = ops.as_mask_u8(mask, masked_kspace)
+        acq = dc.Acquisition(masked_kspace, mask, sens_maps)
+        zf = acq.zero_filled()                                       # (b, t, 1, h, w, 2)
+        dev = zf.device
+        if step is None:
+            step = default_step(sens_maps)
+        elif not isinstance(step, torch.Tensor):
+            step = torch.full((1,), float(step), device=dev, dtype=torch.float32)
+        if not isinstance(lam, torch.Tensor):
+            lam = block_sigma_max(zf, block) * float(lam)
+        out = ops.llr_solve(zf, sens_maps, mask, step, lam, block, iters, shifts=host_shifts, sens_tiled=acq.tiled, record=record)
+        x, rec, info = out if record else (out, None, None)
+        x = x.squeeze(2)
+        x = x if cplx else ops.complex_abs(x)
+    return (x, rec, info) if record else x
+
+
+class LocallyLowRank(nn.Module):
+    """``locally_low_rank`` as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(LocallyLowRank(...).eval())``
+    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included (a replayed graph replays the same shift sequence, which
+    is intended).  The settings are the function's; the default ``lam`` is untuned (see there).  Not differentiable."""
+
+    def __init__(self, iters: int = 30, lam: Union[float, torch.Tensor] = 0.005, block: int = 8, shifts="random",
+                 step: Optional[Union[float, torch.Tensor]] = None):
+        super().__init__()
+        self.iters, self.block, self.shifts = _llr_settings("LocallyLowRank", iters, block, shifts)
+        self.lam, self.step = lam, step
+
+    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
+        return locally_low_rank(masked_kspace, mask, sens_maps, iters=self.iters, lam=self.lam, block=self.block, shifts=self.shifts,
+                                step=self.step, output=output)

@@ -9,6 +9,7 @@ from typing import NamedTuple, Optional, Sequence
 import contextlib
 import ctypes
 import threading
+import numpy as np
 import torch
 
 from ._lib import CineHipError, check, lib
@@ -891,6 +892,102 @@ def ls_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: tor
     out = (x, lo, so) if components else (x,)
     out = out + ((rec, resid) if record else ())
     return out if len(out) > 1 else x
+
+
+LLR_REC = 4             # floats of one record row of llr_prox / llr_solve: sum |x_new - x|^2, sum |x_new|^2, sum over the blocks of || C_beta(x_new) ||_*, 0
+LLR_INFO = 4            # doubles of one info row of llr_prox / llr_solve: the largest block sigma_max, the worst Jacobi residual, the most sweeps, the blocks
+LLR_MIN_BLOCK, LLR_MAX_BLOCK = 2, 16
+
+
+def _llr_block(block, what: str) -> int:
+    block = int(block)
+    if not LLR_MIN_BLOCK <= block <= LLR_MAX_BLOCK:
+        raise ValueError(f"{what}: block = {block} is outside {LLR_MIN_BLOCK} .. {LLR_MAX_BLOCK}")
+    return block
+
+
+def llr_shift_array(shifts, iters: int, block: int, what: str) -> np.ndarray:
+    """``shifts`` as the contiguous (iters, 2) int32 host array cine_llr_solve reads: an integer array of that shape with every entry in
+    [0, block), validated here on the host (ValueError)."""
+    a = np.asarray(shifts)
+    if a.dtype.kind not in "iu" or a.shape != (int(iters), 2):
+        raise ValueError(f"{what}: shifts must be an integer array of shape ({int(iters)}, 2), got {a.dtype} {a.shape}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= block):
+        raise ValueError(f"{what}: shifts must lie in [0, {block}), got {int(a.min())} .. {int(a.max())}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def llr_prox(x: torch.Tensor, g: Optional[torch.Tensor], step: Optional[torch.Tensor], thresh: torch.Tensor, block: int, shift=(0, 0),
+             record: bool = False, xnew: Optional[torch.Tensor] = None, image: bool = True):
+    """cine_llr_prox, the proximal half of one locally low-rank iteration in one launch: v = x - step g (``g`` None: v = x, and ``step`` may
+    be None too), every ``block`` x ``block`` square of the partition with its grid origin at (-shift[0], -shift[1]) (clipped to the image)
+    has the singular values of its (pixels x t) Casorati matrix thresholded by step * thresh (``step`` None: thresh).  x, g:
+    (b, t, [1,] h, w, 2); ``step``, ``thresh``: one device float each.  ``xnew``: where to write (may be ``x``: in place); a new tensor by
+    default.  ``image`` False: no image is written at all and (rec, info) is returned -- how ``classical.block_sigma_max`` is formed.
+    Returns xnew, with ``record`` (xnew, rec, info): rec the ``LLR_REC`` device floats, info the ``LLR_INFO`` device doubles."""
+    x, (b, t, h, w) = _ls_image(x, "x", "llr_prox")
+    block = _llr_block(block, "llr_prox")
+    sh, sw = (int(v) for v in shift)
+    if not (0 <= sh < block and 0 <= sw < block):
+        raise ValueError(f"llr_prox: shift {(sh, sw)} is outside [0, {block})")
+    thresh = _kt_scalar(thresh, "thresh")
+    step = None if step is None else _kt_scalar(step, "step")
+    if g is not None:
+        g = _dev(g, "g")
+        if g.numel() != x.numel() or step is None:
+            raise ValueError(f"llr_prox: g {tuple(g.shape)} does not match x {tuple(x.shape)}, or comes without a step")
+    if xnew is not None and (not image or not xnew.is_cuda or xnew.dtype != x.dtype or not xnew.is_contiguous() or xnew.numel() != x.numel()):
+        raise CineHipError("llr_prox: xnew must be a contiguous float32 GPU tensor of x's size (and image must be on)")
+    if image and xnew is None:
+        xnew = torch.empty_like(x)
+    record = record or not image
+    rec = info = ws = None
+    nbytes = 0
+    if record:
+        rec = torch.empty(LLR_REC, device=x.device, dtype=torch.float32)
+        info = torch.empty(LLR_INFO, device=x.device, dtype=torch.float64)
+        nbytes = lib().cine_llr_prox_ws_bytes(b, t, h, w, block, sh, sw)
+        ws = _general_ws(nbytes, x.device)
+    check(lib().cine_llr_prox(x.data_ptr(), _p(g), _p(step), thresh.data_ptr(), block, sh, sw, _p(xnew), _p(rec), _p(info), b, t, h, w,
+                              _p(ws), nbytes, _stream()), "cine_llr_prox")
+    if not image:
+        return rec, info
+    return (xnew, rec, info) if record else xnew
+
+
+def llr_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: torch.Tensor, thresh: torch.Tensor, block: int, iters: int,
+              shifts=None, sens_tiled: Optional[torch.Tensor] = None, record: bool = False):
+    """cine_llr_solve: ``iters`` proximal-gradient iterations of the locally low-rank solve from x_0 = zf = A^H M y in one C call
+    (``image_dc`` with weights (1, 0, -1), then ``llr_prox`` with the iteration's shift, per iteration).  zf (b, t, [1,] h, w, 2); sens
+    (b, 1, c, h, w, 2); ``mask``: either layout of ``as_mask_u8``; ``step``, ``thresh``: one device float each.  ``shifts``: None (no shift)
+    or an (iters, 2) integer HOST array with entries in [0, block) -- it is read during the call, so a captured graph replays the shifts it
+    was captured with.  Returns x in zf's shape, with ``record`` (x, rec, info) with rec (iters, ``LLR_REC``) float32 and info
+    (iters, ``LLR_INFO``) float64."""
+    _pair(zf); _pair(sens)
+    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
+    step = _kt_scalar(step, "step"); thresh = _kt_scalar(thresh, "thresh")
+    if sens.dim() != 6:
+        raise ValueError(f"llr_solve: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
+    b, _, c, h, w, _ = sens.shape
+    t = zf.shape[1]
+    layout = mask_layout(mask, sens, t)
+    if zf.numel() != b * t * h * w * 2 or layout is None:
+        raise ValueError(f"llr_solve: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError(f"llr_solve: iters = {iters}")
+    block = _llr_block(block, "llr_solve")
+    host = None if shifts is None else llr_shift_array(shifts, iters, block, "llr_solve")
+    mask_w = 1 if layout == "row" else w
+    x = torch.empty_like(zf)
+    rec = torch.empty((iters, LLR_REC), device=zf.device, dtype=torch.float32) if record else None
+    info = torch.empty((iters, LLR_INFO), device=zf.device, dtype=torch.float64) if record else None
+    nbytes = lib().cine_llr_solve_ws_bytes(b, t, c, h, w, mask_w, block, iters)
+    ws = _general_ws(nbytes, zf.device)
+    check(lib().cine_llr_solve(x.data_ptr(), zf.data_ptr(), sens.data_ptr(), _p(sens_tiled), mask.data_ptr(), mask_w, step.data_ptr(),
+                               thresh.data_ptr(), block, None if host is None else host.ctypes.data, iters, _p(rec), _p(info), b, t, c, h, w,
+                               ws.data_ptr(), nbytes, _stream()), "cine_llr_solve")
+    return (x, rec, info) if record else x
 
 
 TV_REC = 4              # floats of one record row of tv_pd_step / tv_solve: sum |x_new - x|^2, sum |x_new|^2, sum |D_t x_new|, sum |(D_h, D_w) x_new|

@@ -14,7 +14,8 @@
 //                        (entry, pixel slice) sums its slice, a capped number of workgroups leaves one upper-triangle record each.
 //   ls_svt_kernel        one workgroup per batch element; G and the eigenvector accumulator in LDS in float64 (2 x 16 t^2 bytes: 128 KiB
 //                        at t = 64, the large-LDS opt-in above 64 KiB); cyclic Jacobi for a complex Hermitian matrix, round-robin pairs
-//                        (the t / 2 rotations of a round are disjoint: column phase, barrier, row phase), bounded sweeps.
+//                        (the t / 2 rotations of a round are disjoint: column phase, barrier, row phase), bounded sweeps: ls_jacobi in
+//                        ls_jacobi.h, which llr_kernels.hip runs per spatial block.
 //   ls_prox_kernel       one workgroup = kLsPix consecutive pixels, all frames: W in LDS, L' = v_L W, then the W region is reused for the
 //                        twiddles and the tile for the temporal prox of kt_prox_kernel; 64 KiB of LDS at t = 64, no scratch.
 #include <cstdint>
@@ -22,27 +23,15 @@
 #include <string>
 #include "common.h"
 #include "fft_core.h"
+#include "ls_jacobi.h"
 
 namespace cine {
 
-constexpr int kLsMaxT = 64;
 constexpr int kLsPix = 64;                      // prox: pixels per workgroup (one wavefront = one frame / bin of the tile)
-constexpr int kLsThreads = 256;
 constexpr int kLsItems = kLsMaxT * kLsPix / kLsThreads;
 constexpr int kLsGramTile = 2048;               // gram: complex128 entries of one staged tile (32 KiB)
 constexpr int kLsGramRecords = 256;             // gram: records (workgroups) over the whole batch, unless b itself is larger
 constexpr int kLsGramItems = (kLsMaxT * (kLsMaxT + 1) / 2 + kLsThreads - 1) / kLsThreads;     // entries per thread at t = 64
-constexpr int kLsMaxSweeps = 40;
-constexpr double kLsJacobiTol = 1e-14;
-
-// v = a - step g in float32: ONE expression for the Gram matrix and the prox, so that both see the same v
-__device__ __forceinline__ cf ls_v(cf a, cf g, float step) { return mk(fmaf(-step, g.x, a.x), fmaf(-step, g.y, a.y)); }
-
-__device__ __forceinline__ float ls_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ------------------------------------------------------------------ Gram matrix of the Casorati matrix
 struct LsGramArgs {
@@ -51,16 +40,6 @@ struct LsGramArgs {
     long HW, run;                               // pixels, pixels per workgroup (a multiple of S)
     int T, S, P, nq;                            // S pixels per staged tile, P = T (T + 1) / 2 entries, nq pixel slices per entry
 };
-
-__host__ __device__ __forceinline__ int ls_row_start(int i, int t) { return i * t - i * (i - 1) / 2; }
-
-// entry p of the row-major upper triangle -> (i, j), i <= j
-__device__ __forceinline__ void ls_pair_of(int p, int t, int& i, int& j) {
-    int r = 0;
-    while (r + 1 < t && ls_row_start(r + 1, t) <= p) ++r;
-    i = r;
-    j = r + (p - ls_row_start(r, t));
-}
 
 __global__ __launch_bounds__(kLsThreads) void ls_gram_partial_kernel(LsGramArgs a) {
     __shared__ double2 tile[kLsGramTile + kLsMaxT];           // [T][S + 1], converted to float64 once
@@ -183,8 +162,6 @@ static int ls_sizes(const char* what, int b, int t, int h, int w) {
     return CINE_OK;
 }
 
-static bool ls_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 static int ls_gram_launch(const float* a, const float* g, const float* step_dev, double* gram, int b, int t, int h, int w, void* ws,
                           hipStream_t st) {
     const LsGramPlan p = ls_gram_plan(b, t, h, w);
@@ -206,115 +183,21 @@ struct LsSvtArgs {
     int T;
 };
 
-// round r of the round-robin schedule on n (even) players, pair k: player n - 1 stays, the others rotate
-__device__ __forceinline__ void ls_round_pair(int n, int r, int k, int& p, int& q) {
-    const int m = n - 1;
-    int x, y;
-    if (k == 0) { x = m; y = r; }
-    else { x = (r + k) % m; y = (r - k + m) % m; }
-    p = x < y ? x : y;
-    q = x < y ? y : x;
-}
-
-// max that keeps a NaN once it has seen one
-__device__ __forceinline__ double ls_nanmax(double m, double v) { return (v > m || v != v) ? v : m; }
-
 __global__ __launch_bounds__(kLsThreads) void ls_svt_kernel(LsSvtArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int T = a.T, tid = threadIdx.x, b = blockIdx.x;
-    const int n = (T + 1) & ~1, nh = n >> 1;
     double2* A = reinterpret_cast<double2*>(smem);            // [T][T]: the matrix, in the end its diagonal = the eigenvalues
     double2* V = A + T * T;                                   // [T][T]: the product of the rotations, columns = eigenvectors
     double* rot = reinterpret_cast<double*>(V + T * T);       // [kLsMaxT / 2][8]: c, s, e^{i phi}, the new diagonal pair, on / off
-    double* red = rot + (kLsMaxT / 2) * 8;                    // [2][kLsThreads]
+    double* red = rot + kLsRotDoubles;                        // [2][kLsThreads]
     const double2* G = a.gram + (long)b * T * T;
     for (int e = tid; e < T * T; e += kLsThreads) {
         A[e] = G[e];
         V[e] = make_double2((e / T == e % T) ? 1.0 : 0.0, 0.0);
     }
     __syncthreads();
-    double off = 0.0, diag = 0.0;
-    int sweeps = 0;
-    for (int sweep = 0; sweep <= kLsMaxSweeps; ++sweep) {     // bounded: a NaN never satisfies the test and ends at the cap
-        double mo = 0.0, md = 0.0;
-        for (int e = tid; e < T * T; e += kLsThreads) {
-            const int i = e / T, j = e - i * T;
-            const double2 v = A[e];
-            if (i == j) md = ls_nanmax(md, fabs(v.x));
-            else mo = ls_nanmax(mo, hypot(v.x, v.y));
-        }
-        red[tid] = mo; red[kLsThreads + tid] = md;
-        __syncthreads();
-        for (int st = kLsThreads / 2; st > 0; st >>= 1) {
-            if (tid < st) {
-                red[tid] = ls_nanmax(red[tid], red[tid + st]);
-                red[kLsThreads + tid] = ls_nanmax(red[kLsThreads + tid], red[kLsThreads + tid + st]);
-            }
-            __syncthreads();
-        }
-        off = red[0]; diag = red[kLsThreads];
-        __syncthreads();
-        sweeps = sweep;
-        if (off <= kLsJacobiTol * diag || sweep == kLsMaxSweeps) break;
-        for (int r = 0; r < n - 1; ++r) {
-            if (tid < nh) {                                   // the rotation of pair tid from the 2 x 2 block [[al, be], [conj(be), ga]]
-                int p, q;
-                ls_round_pair(n, r, tid, p, q);
-                double* o = rot + tid * 8;
-                o[6] = 0.0;
-                if (q < T) {
-                    const double al = A[p * T + p].x, ga = A[q * T + q].x;
-                    const double2 be = A[p * T + q];
-                    const double bm = hypot(be.x, be.y);
-                    // an element a tenth of the stopping bar below its own diagonal pair is left alone: inside a cluster of equal
-                    // eigenvalues its rotation would be 45 degrees of noise, which slows the sweeps to linear convergence
-                    if (!(bm <= 0.1 * kLsJacobiTol * sqrt(fabs(al * ga)))) {
-                        // t = sgn(d) / (|z| + sqrt(1 + z^2)), z = d / (2 |be|), written without z: no overflow for a tiny |be|, no 0 / 0
-                        const double d = ga - al;
-                        const double tt = (d < 0.0 ? -2.0 : 2.0) * bm / (fabs(d) + hypot(d, 2.0 * bm));
-                        const double c = 1.0 / sqrt(1.0 + tt * tt);
-                        o[0] = c; o[1] = c * tt; o[2] = be.x / bm; o[3] = be.y / bm;
-                        o[4] = al - tt * bm; o[5] = ga + tt * bm; o[6] = 1.0;
-                    }
-                }
-            }
-            __syncthreads();
-            // columns: M <- M J for M = A and V, J = [[c, s], [-s e^{-i phi}, c e^{-i phi}]] on (p, q); the pair on the lanes
-            for (int it = tid; it < nh * T * 2; it += kLsThreads) {
-                const int k = it % nh, rest = it / nh;
-                const int row = rest % T;
-                const double* o = rot + k * 8;
-                if (o[6] == 0.0) continue;
-                int p, q;
-                ls_round_pair(n, r, k, p, q);
-                double2* M = rest >= T ? V : A;
-                const double c = o[0], s = o[1], ex = o[2], ey = o[3];
-                const double2 x = M[row * T + p], y = M[row * T + q];
-                const double yx = ex * y.x + ey * y.y, yy = ex * y.y - ey * y.x;          // e^{-i phi} y
-                M[row * T + p] = make_double2(c * x.x - s * yx, c * x.y - s * yy);
-                M[row * T + q] = make_double2(s * x.x + c * yx, s * x.y + c * yy);
-            }
-            __syncthreads();
-            // rows: A <- J^H A; the 2 x 2 block itself takes its closed form (zero off the diagonal, a real diagonal)
-            for (int it = tid; it < nh * T; it += kLsThreads) {
-                const int k = it / T, col = it - k * T;
-                const double* o = rot + k * 8;
-                if (o[6] == 0.0) continue;
-                int p, q;
-                ls_round_pair(n, r, k, p, q);
-                const double c = o[0], s = o[1], ex = o[2], ey = o[3];
-                const double2 x = A[p * T + col], y = A[q * T + col];
-                const double yx = ex * y.x - ey * y.y, yy = ex * y.y + ey * y.x;          // e^{i phi} y
-                double2 xn = make_double2(c * x.x - s * yx, c * x.y - s * yy);
-                double2 yn = make_double2(s * x.x + c * yx, s * x.y + c * yy);
-                if (col == p) { xn = make_double2(o[4], 0.0); yn = make_double2(0.0, 0.0); }
-                if (col == q) { xn = make_double2(0.0, 0.0); yn = make_double2(o[5], 0.0); }
-                A[p * T + col] = xn;
-                A[q * T + col] = yn;
-            }
-            __syncthreads();
-        }
-    }
+    double off, diag;
+    const int sweeps = ls_jacobi(A, V, rot, red, T, tid, off, diag);
     // h(lam) per eigenvalue; A's off-diagonal part is dead now and takes conj(V)^T diag(h)
     const float thf = a.step ? *a.step * *a.thresh : *a.thresh;
     const double th = (double)thf;
@@ -358,16 +241,6 @@ __global__ __launch_bounds__(kLsThreads) void ls_svt_kernel(LsSvtArgs a) {
 }
 
 static size_t ls_svt_lds(int t) { return (size_t)2 * t * t * sizeof(double2) + ((kLsMaxT / 2) * 8 + 2 * kLsThreads) * sizeof(double); }
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device: raise it once per (kernel, device) and keep the result
-static int ls_large_lds(const void* kern, const char* what, std::once_flag* once, hipError_t* status) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    CINE_REQUIRE(dev >= 0 && dev < 64, CINE_EUNSUPPORTED, "%s: device index %d", what, dev);
-    std::call_once(once[dev], [&] { status[dev] = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    CINE_REQUIRE(status[dev] == hipSuccess, CINE_EHIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", what, hipGetErrorString(status[dev]));
-    return CINE_OK;
-}
 
 // before the first launch of a call: the opt-in of the weight kernel for this t
 static int ls_svt_prepare(int t) {
@@ -593,8 +466,6 @@ static int ls_record_launch(const float* part, long nblk, float* rec, int rows, 
     hipLaunchKernelGGL(ls_record_kernel, dim3(rows), dim3(256), 0, st, part, nblk, rec, info, nb, resid);
     return check_launch("ls_record_kernel");
 }
-
-static size_t ls_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace cine
 

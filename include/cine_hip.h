@@ -1036,6 +1036,51 @@ int cine_tv_solve(float* x, const float* zf, const float* sens, const float* sen
                   int iters, float* rec, float* p_out, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Locally low-rank (LLR; Trzasko & Manduca 2011, Zhang et al. 2015; no reference counterpart): singular-value thresholding of every
+ * small spatial block of the Casorati matrix, the fourth weight-free baseline, on the same operators
+ *     minimise over x   1/2 || M A x - y ||^2  +  lam sum over the blocks beta of a partition P of || C_beta(x) ||_*
+ * C_beta(x): the (pixels of beta) x t Casorati matrix of block beta.  P: block x block squares on a grid whose origin lies at
+ * (-shift_h, -shift_w), 0 <= shift < block, clipped to the image (no wrap-around): ceil((h + shift_h) / block) x
+ * ceil((w + shift_w) / block) blocks per image, the ones at the border as small as one pixel.  Proximal gradient without momentum,
+ *     g = A^H M A x_k - zf;   x_{k+1} = BlockSVT_{P_k}(x_k - step g, step lam)
+ * with the shift of P_k changing from iteration to iteration.  Per block, with X = C_beta(v) and G = X^H X = V diag(lam) V^H (t x t):
+ * SVT(X, th) = X W, W = V diag(h(lam)) V^H, h(lam) = 1 - th / sqrt(lam) for lam > th^2, else 0 -- the route of cine_svt_weight, here
+ * with one workgroup per (block, batch element) that forms G, diagonalises it and applies W in ONE launch.
+ * Limits of both entry points: 2 <= t <= 64, 2 <= block <= 16 (any value, no power of two needed), b <= 65535, else
+ * CINE_EUNSUPPORTED; any h, w >= 1 (the solve: what the operator accepts).  Null x, non-positive sizes and a shift outside [0, block)
+ * are CINE_EINVAL, a short workspace CINE_EWORKSPACE.  Every argument is checked before the first launch; no allocation, no
+ * synchronisation, no atomics: capturable, and the same bits on every call.
+ * ------------------------------------------------------------------------------------------ */
+/* The proximal half of an iteration in one launch.  x, g, xnew: (b, t, h, w, 2).  v = x - (*step_dev) g is formed in float32 and never
+ * written; g == NULL: v = x, and step_dev may be NULL too.  th = (*step_dev) (*thresh_dev), or *thresh_dev with step_dev == NULL.
+ * Per block: G in float64 from exact float32 products in an order that depends on the shape only (bitwise Hermitian, a real diagonal),
+ * the cyclic Jacobi eigensolver of cine_svt_weight in LDS (until max |off-diagonal| <= 1e-14 max |diagonal| or 40 sweeps; a NaN ends at
+ * the cap), W, and xnew = v W per pixel.
+ * xnew == NULL: nothing is written to an image, only rec and info are produced (the scale of lam is formed this way).  xnew may be x
+ * (a workgroup owns its block over all frames and reads before it writes); any other aliasing of an output is CINE_EINVAL.
+ * rec (or NULL): 4 device floats = sum |xnew - x|^2, sum |xnew|^2, sum over the blocks of || C_beta(xnew) ||_* (the thresholded singular
+ * values), 0.  info (or NULL): 4 device doubles over the whole call = the largest block sigma_max of v, the worst Jacobi residual
+ * max |off-diagonal| / max |diagonal| any block reached, the most sweeps any block used, the number of blocks (b times the blocks per
+ * image).  Both come from one record per workgroup in ws (cine_llr_prox_ws_bytes for exactly this shift; 16-byte aligned; ws may be
+ * NULL without rec and info), added in float64 in a fixed order by a second launch. */
+size_t cine_llr_prox_ws_bytes(int b, int t, int h, int w, int block, int shift_h, int shift_w);
+int cine_llr_prox(const float* x, const float* g, const float* step_dev, const float* thresh_dev, int block, int shift_h, int shift_w,
+                  float* xnew, float* rec, double* info, int b, int t, int h, int w, void* ws, size_t ws_bytes, void* stream);
+/* The whole solve in one call: x_0 = zf, and for k = 0 .. iters - 1 the operator (cine_image_dc_t for mask_w == 1: mask (b, t, h);
+ * cine_image_dc_general for mask_w == w: (b, t, h, w); sens_tiled as cine_kt_fista) with weights (1, 0, -1) and cine_llr_prox in place
+ * with the shift (shifts[2 k], shifts[2 k + 1]).  shifts: a HOST array of iters x 2 ints read during the call and checked in full
+ * before the first launch, or NULL for no shift.  x (out), zf: (b, t, h, w, 2).  rec: (iters, 4) floats, info: (iters, 4) doubles, a
+ * row of cine_llr_prox's per iteration, or NULL (all rows are added up in one launch at the end).  x, rec and info equal, bit for bit,
+ * what the caller gets from the two entry points iterated by hand.  ws: cine_llr_solve_ws_bytes() = the operator's scratch, g and
+ * iters rows of records sized for the WORST CASE over all shifts (ceil((h + block - 1) / block) x ceil((w + block - 1) / block)
+ * blocks per image), whatever shifts the call is given; 16-byte aligned.  iters >= 1, c > 0, mask_w in {1, w}, x / rec / info / ws
+ * aliasing nothing (CINE_EINVAL); h, w, c: what the operator accepts -- it is called first and refuses before anything is launched. */
+size_t cine_llr_solve_ws_bytes(int b, int t, int c, int h, int w, int mask_w, int block, int iters);
+int cine_llr_solve(float* x, const float* zf, const float* sens, const float* sens_tiled, const uint8_t* mask, int mask_w,
+                   const float* step_dev, const float* thresh_dev, int block, const int* shifts, int iters,
+                   float* rec, double* info, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement aid (no reference counterpart; the reference only wraps time.time() around the
  * model call, traintest_scripts/run_inference.py:53-61)
  * ------------------------------------------------------------------------------------------ */
