@@ -192,7 +192,7 @@ extern "C" int cine_scale(float* x, long n, float s, void* stream) {
 }
 
 extern "C" size_t cine_image_metrics_ws_bytes(int t, int hg, int wg, int hp, int wp, int win) {
-    if (t <= 0 || hg <= 0 || wg <= 0 || hp <= 0 || wp <= 0 || win < 1) return 0;
+    if (t <= 0 || hg <= 0 || wg <= 0 || hp <= 0 || wp <= 0 || win < 2 || win > kSsimMaxWin) return 0;
     const int ch = hg < hp ? hg : hp, cw = wg < wp ? wg : wp;
     if (ch < win || cw < win) return 0;
     const long nblk = (long)ceil_div(ch - win + 1, kSsimTile) * ceil_div(cw - win + 1, kSsimTile);
@@ -204,7 +204,7 @@ extern "C" int cine_image_metrics(const float* gt, const float* pred, int t, int
                                   double* out, void* ws, size_t ws_bytes, void* stream) {
     CINE_REQUIRE(gt && pred && out && ws, CINE_EINVAL, "cine_image_metrics: null pointer");
     CINE_REQUIRE(t > 0 && t <= 65535 && hg > 0 && wg > 0 && hp > 0 && wp > 0, CINE_EINVAL, "cine_image_metrics: bad sizes");
-    CINE_REQUIRE(win >= 1 && win <= kSsimMaxWin && (win & 1), CINE_EINVAL, "cine_image_metrics: window %d (odd, <= %d)", win, kSsimMaxWin);
+    CINE_REQUIRE(win >= 3 && win <= kSsimMaxWin && (win & 1), CINE_EINVAL, "cine_image_metrics: window %d (odd, 3 .. %d)", win, kSsimMaxWin);
     CINE_REQUIRE(range_mode >= 0 && range_mode <= 2, CINE_EINVAL, "cine_image_metrics: range_mode %d", range_mode);
     MetricArgs a{};
     a.gt = gt; a.pred = pred; a.T = t; a.Hg = hg; a.Wg = wg; a.Hp = hp; a.Wp = wp;

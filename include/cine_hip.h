@@ -203,7 +203,8 @@ int cine_zero_filled_rss(const float* k, float* out, float* tmp, int b, int t, i
 /* SSIM / NMSE / PSNR / MSE of a reconstruction against its target, on the device (reference utils/evaluate.py:6-50 --
  * skimage structural_similarity / peak_signal_noise_ratio defaults -- after data/transforms.py:161-183
  * center_crop_to_smallest; utils/losses.py:25-58 for SSIMLoss's per-frame data range).  gt (t, hg, wg), pred (t, hp, wp)
- * float32; both are center-cropped to (min h, min w).  SSIM: win x win uniform window (odd, <= 11; reference 7), sample
+ * float32; both are center-cropped to (min h, min w).  SSIM: win x win uniform window (odd, 3 .. 11; reference 7; one pixel has no
+ * sample covariance and is refused, as skimage refuses it), sample
  * covariance, K1, K2, mean over the window-valid region, then over frames; float64 arithmetic like skimage.
  * range_mode 0: data range = max of the cropped gt volume (evaluate.py:31); 1: max of each gt frame (losses.py:34);
  * 2: `maxval`.  out (device, 4 + t doubles) = {ssim, nmse, psnr, mse, ssim of frame 0..t-1}. */
@@ -904,8 +905,13 @@ int cine_axpby_lam(float* out, const float* a, const float* b, long n, const flo
 
 /* SSIMLoss (utils/losses.py:25-58): loss = mean over frames of (1 - mean SSIM over the win x win windows of the valid region), sample
  * covariance, K1 / K2, the data range of every frame = the maximum of that TARGET frame (losses.py:34).  x = reconstruction, y = target,
- * both (t, h, w) float32; *loss_dev one float.  The forward keeps the per-window derivatives in `ws` (cine_ssim_loss_ws_bytes) for
- * cine_ssim_loss_bwd: gx (t, h, w) = d loss / d x scaled by the upstream gradient *gloss_dev.  Window sums in float64. */
+ * both (t, h, w) float32; *loss_dev one float; win 2 .. 11 (a window of one pixel has no sample covariance: refused, and the size query
+ * returns 0).  The forward keeps the per-window derivatives in `ws` (cine_ssim_loss_ws_bytes) for
+ * cine_ssim_loss_bwd: gx (t, h, w) = d loss / d x scaled by the upstream gradient *gloss_dev.  Window sums in float64.
+ * Workspace (8-byte aligned), with No = (h - win + 1) (w - win + 1) windows per frame in tiles of 16 x 16: t * tiles + 2 doubles (the tile
+ * sums of S), then dS/d(ux), dS/d(uxx), dS/d(uxy) as three arrays of t * No doubles -- doubles because in a smooth window their weighted
+ * sum cancels by three orders of magnitude --, then t + 16 floats (the frame maxima).  The backward reads the workspace only, and depends
+ * on nothing but its bytes. */
 size_t cine_ssim_loss_ws_bytes(int t, int h, int w, int win);
 int cine_ssim_loss(const float* x, const float* y, int t, int h, int w, int win, double k1, double k2,
                    float* loss_dev, void* ws, size_t ws_bytes, void* stream);

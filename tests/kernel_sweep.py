@@ -107,6 +107,22 @@ class GuardedInt:
         return bool((self.buf[:GUARD] == GUARD_INT).all()) and bool((self.buf[GUARD + self.n:] == GUARD_INT).all())
 
 
+class GuardedF64:
+    """Guarded for a float64 output (cine_image_metrics' out): `n` doubles, NaN, between GUARD doubles of GUARD_VALUE on each side."""
+
+    def __init__(self, n, dev):
+        self.n = n
+        self.buf = torch.full((2 * GUARD + n,), GUARD_VALUE, dtype=torch.float64, device=dev)
+        self.t = self.buf[GUARD:GUARD + n]
+        self.t.fill_(float("nan"))
+
+    def ptr(self):
+        return self.t.data_ptr()
+
+    def intact(self):
+        return bool((self.buf[:GUARD] == GUARD_VALUE).all()) and bool((self.buf[GUARD + self.n:] == GUARD_VALUE).all())
+
+
 def same_bits(a, b):
     """Bit equality of two float32 tensors (NaN-safe, and -0 differs from +0)."""
     return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
