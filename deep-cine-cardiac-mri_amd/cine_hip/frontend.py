@@ -7,7 +7,9 @@
                     SVD coil compression of the raw data (Buehrer et al., MRM 57:1131, 2007; Huang et al., MRI 26:133, 2008): the c
                     physical coils projected onto V virtual coils BEFORE the inverse transform.  The reference has no such step; here
                     it gives every scan of a data set the same shape (one SlicePipeline graph set) and lifts the 32-coil cap of the
-                    calibration.  ``prepare_slice(..., virtual_coils=V)`` runs it in place.
+                    calibration.  ``prepare_slice(..., virtual_coils=V)`` runs it in place.  ``method="jacobi"`` takes the eigenvectors
+                    from cine_coil_matrix (a Jacobi eigensolver in LDS) instead of torch.linalg.eigh: no host read, capturable, what
+                    ``prepare_masked_slice(..., virtual_coils=V)`` and ``SlicePipeline.submit_raw(..., virtual_coils=V)`` run per slice.
 ``prepare_masked_slice``
                     prepare_slice's k-space with the row mask applied, device in, device out, capturable by a hipGraph: what
                     ``SlicePipeline.submit_raw`` runs per slice.  Line-engine raw sizes enter through ops.raw_ingest (kept frames only).
@@ -112,34 +114,101 @@ def _kept_frames(n_frames, t: int) -> int:
     return n
 
 
-def coil_gram(raw: torch.Tensor, n_frames: Optional[int] = None, region: int = 24) -> torch.Tensor:
+def coil_gram(raw: torch.Tensor, n_frames: Optional[int] = None, region: int = 24, out: Optional[torch.Tensor] = None,
+              ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Calibration Gram matrix of the coils: raw (t, x, y, coil) complex64 -> G (coil, coil) complex128,
     G[i, j] = sum over the first min(n_frames, t) frames and the central region x region block of k-space (clipped to the matrix, centred
     as espirit_maps centres its block; region 0 = the whole matrix) of raw[..., i] * conj(raw[..., j]).  Float64 sums of exact products
-    in a fixed order: exactly Hermitian, bit-identical from call to call."""
+    in a fixed order: exactly Hermitian, bit-identical from call to call.  ``out``: a contiguous complex128 (coil, coil) GPU tensor to
+    write into; ``ws``: a uint8 GPU buffer of at least ``coil_gram_ws_bytes(...)`` bytes (the pipeline's static buffers)."""
     x = _raw_pairs(raw, "coil_gram")
     t, nx, ny, c, _ = x.shape
     n = _kept_frames(n_frames, t)
     region = int(region)
     if region < 0:
         raise ValueError("coil_gram: region must be >= 0")
-    gram = torch.empty((c, c), device=x.device, dtype=torch.complex128)
+    if out is None:
+        gram = torch.empty((c, c), device=x.device, dtype=torch.complex128)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.complex128 and tuple(out.shape) == (c, c) and out.is_contiguous()):
+        raise CineHipError(f"coil_gram: out must be a contiguous complex128 GPU tensor of shape {(c, c)}")
+    else:
+        gram = out
     nbytes = lib().cine_coil_gram_ws_bytes(n, nx, ny, c, region)
-    ws = torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+    if ws is None:
+        ws = torch.empty(max(nbytes, 16), device=x.device, dtype=torch.uint8)
+    elif not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nbytes):
+        raise CineHipError(f"coil_gram: ws must be a contiguous uint8 GPU buffer of at least {nbytes} bytes")
     check(lib().cine_coil_gram(x.data_ptr(), gram.data_ptr(), ws.data_ptr(), nbytes, t, nx, ny, c, n, region, ops._stream()), "cine_coil_gram")
     return gram
 
 
-def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int) -> Tuple[torch.Tensor, torch.Tensor]:
+def coil_gram_ws_bytes(n_frames: int, nx: int, ny: int, coils: int, region: int = 24) -> int:
+    """Bytes of workspace coil_gram needs for n_frames kept frames of an (nx, ny) matrix with that many coils."""
+    return int(lib().cine_coil_gram_ws_bytes(int(n_frames), int(nx), int(ny), int(coils), int(region)))
+
+
+COIL_MATRIX_MAX_COILS = 64      # cine_coil_matrix: the two c x c float64 matrices of the eigensolver fill the LDS (include/cine_hip.h)
+COIL_MATRIX_INFO = 4            # doubles per matrix: the Jacobi residual, the sweeps used, the kept share sum(lam[:V]) / sum(lam), lam[0]
+COIL_MATRIX_METHODS = ("eigh", "jacobi")
+
+
+def _cc_method(method) -> str:
+    if method not in COIL_MATRIX_METHODS:
+        raise ValueError(f"coil compression: method must be 'eigh' or 'jacobi', got {method!r}")
+    return method
+
+
+def _coil_matrix_jacobi(gram: torch.Tensor, v: int, matrix: Optional[torch.Tensor] = None, lam: Optional[torch.Tensor] = None,
+                        info: Optional[torch.Tensor] = None):
+    """cine_coil_matrix on gram (n, c, c) complex128, contiguous, on the GPU -> (matrix (n, V, c, 2) float32, lam (n, c) float64, info
+    (n, COIL_MATRIX_INFO) float64), written into the given contiguous tensors where they are passed.  No host read."""
+    if not (isinstance(gram, torch.Tensor) and gram.is_cuda and gram.dtype == torch.complex128 and gram.dim() == 3
+            and gram.shape[1] == gram.shape[2] and gram.is_contiguous()):
+        raise CineHipError("coil_matrix_from_gram(method='jacobi'): gram must be a contiguous complex128 GPU tensor (no CPU fallback)")
+    n, c, _ = gram.shape
+    dev = gram.device
+    wanted = (("matrix", matrix, (n, v, c, 2), torch.float32), ("lam", lam, (n, c), torch.float64),
+              ("info", info, (n, COIL_MATRIX_INFO), torch.float64))
+    outs = []
+    for name, x, shape, dtype in wanted:
+        if x is None:
+            x = torch.empty(shape, device=dev, dtype=dtype)
+        elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and tuple(x.shape) == shape and x.is_contiguous()):
+            raise CineHipError(f"coil_matrix_from_gram: {name} must be a contiguous {dtype} GPU tensor of shape {shape}")
+        outs.append(x)
+    check(lib().cine_coil_matrix(gram.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), n, c, v, ops._stream()),
+          "cine_coil_matrix")
+    return tuple(outs)
+
+
+def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int, method: str = "eigh"):
     """G (c, c) Hermitian -> (A (V, c) complex64, lam (c,) float64 descending): G = U diag(lam) U^H, A[v] = conj(U[:, v]) times the unit
     phase that makes its largest-magnitude entry (lowest index on a tie) real and positive, rounded once to complex64.  Rows are
-    orthonormal and A G A^H = diag(lam[:V]).  A small dense step: torch.linalg.eigh in complex128 on the tensor's own device."""
-    if gram.dim() != 2 or gram.shape[0] != gram.shape[1] or gram.shape[0] < 1:
-        raise ValueError("coil_matrix_from_gram: gram must be a square matrix")
-    c = gram.shape[0]
+    orthonormal and A G A^H = diag(lam[:V]).  G (n, c, c): n matrices at once, every result with a leading n.
+    ``method="eigh"`` (the default): a small dense step, torch.linalg.eigh in complex128 on the tensor's own device, behind a Hermitian
+    check on the host (both wait for the device).
+    ``method="jacobi"``: cine_coil_matrix, one launch for all n matrices, at most COIL_MATRIX_MAX_COILS coils and 32 virtual coils
+    (CineHipError beyond).  It reads the upper triangle of G only, so there is nothing to check; no host read, capturable, bit-identical
+    from call to call.  Returns (A, lam, info) with info (COIL_MATRIX_INFO,) float64 ON THE DEVICE: the residual max |off-diagonal| /
+    max |diagonal| the eigensolver reached (at most 1e-14 unless its sweep cap was hit or G holds a NaN), the sweeps used, the kept
+    share sum(lam[:V]) / sum(lam), lam[0]."""
+    _cc_method(method)
+    if gram.dim() not in (2, 3) or gram.shape[-2] != gram.shape[-1] or gram.shape[-1] < 1 or gram.shape[0] < 1:
+        raise ValueError("coil_matrix_from_gram: gram must be a square matrix or a stack of them")
+    c = gram.shape[-1]
     v = int(virtual_coils)
     if not 1 <= v <= c:
         raise ValueError(f"coil_matrix_from_gram: virtual_coils must be in 1..{c}")
+    if method == "jacobi":
+        if not gram.is_cuda:
+            raise CineHipError("coil_matrix_from_gram(method='jacobi'): the HIP path needs a GPU tensor (no CPU fallback)")
+        g = gram.to(torch.complex128).contiguous()
+        a, lam, info = _coil_matrix_jacobi(g if g.dim() == 3 else g[None], v)
+        a = torch.view_as_complex(a)
+        return (a, lam, info) if gram.dim() == 3 else (a[0], lam[0], info[0])
+    if gram.dim() == 3:
+        each = [coil_matrix_from_gram(g, v) for g in gram]
+        return torch.stack([a for a, _ in each]), torch.stack([lam for _, lam in each])
     g = gram.to(torch.complex128)
     if float((g - g.conj().transpose(0, 1)).abs().max()) > 1e-12 * float(g.abs().max()):
         raise ValueError("coil_matrix_from_gram: gram is not Hermitian")
@@ -158,9 +227,9 @@ def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int) -> Tuple[torch
 
 
 def coil_compression_matrix(raw: torch.Tensor, virtual_coils: int, n_frames: Optional[int] = None,
-                            region: int = 24) -> Tuple[torch.Tensor, torch.Tensor]:
-    """coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils)."""
-    return coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils)
+                            region: int = 24, cc_method: str = "eigh"):
+    """coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils, cc_method): (A, lam), with "jacobi" (A, lam, info)."""
+    return coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils, _cc_method(cc_method))
 
 
 def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -183,9 +252,10 @@ def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[i
     return torch.view_as_complex(out)
 
 
-def _compressed(kspace_txyc: torch.Tensor, n_slices: int, virtual_coils, coil_matrix, cc_region: int) -> torch.Tensor:
+def _compressed(kspace_txyc: torch.Tensor, n_slices: int, virtual_coils, coil_matrix, cc_region: int, cc_method: str = "eigh") -> torch.Tensor:
     """The coil-compression leg of prepare_slice: the raw data on virtual coils (kept frames only), or the input itself where
     nothing is to be done."""
+    _cc_method(cc_method)
     if virtual_coils is None and coil_matrix is None:
         return kspace_txyc
     c = kspace_txyc.shape[3]
@@ -200,23 +270,24 @@ def _compressed(kspace_txyc: torch.Tensor, n_slices: int, virtual_coils, coil_ma
         raise ValueError(f"virtual_coils must be in 1..{c} (the coil count of this scan)")
     if v == c:
         return kspace_txyc                                                   # already V coils: today's path and bits
-    a, _ = coil_compression_matrix(kspace_txyc, v, n_slices, cc_region)
+    a = coil_compression_matrix(kspace_txyc, v, n_slices, cc_region, cc_method)[0]
     return compress_coils(kspace_txyc, a, n_slices)
 
 
 def prepare_slice(kspace_txyc: torch.Tensor, crop_shape=(200, 200), n_slices: int = 15,
                   filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, virtual_coils: Optional[int] = None,
-                  coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24):
+                  coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, cc_method: str = "eigh"):
     """reference data/mri_data.py:283-293 on the device.  kspace_txyc: raw (t, x, y, coil) complex64 (the HDF5 ``y`` array)
     on the GPU.  Returns (kspace (t, coil, X, Y, 2) float32 of the filtered crop, filtered images (t, coil, X, Y, 2)).  Raw sizes the FFT
     line engines take go through the full-image cine_fft2c; any other raw size through the windowed transform (ops.raw_window_ifft2c),
     which computes only the kept frames and the crop.
     ``virtual_coils=V``: the coils are first compressed to V virtual coils with the matrix of this slice's kept frames
     (coil_compression_matrix, calibration block cc_region), and everything runs on V coils; V equal to the coil count passes the data
-    through.  ``coil_matrix=A`` (V, coil): use a given matrix instead, e.g. one matrix for all slices of a scan."""
+    through.  ``coil_matrix=A`` (V, coil): use a given matrix instead, e.g. one matrix for all slices of a scan.  ``cc_method``:
+    ``coil_matrix_from_gram``'s ``method`` for the matrix of ``virtual_coils=``."""
     if not kspace_txyc.is_cuda:
         raise CineHipError("prepare_slice: the HIP path needs a GPU tensor (no CPU fallback)")
-    kspace_txyc = _compressed(kspace_txyc, n_slices, virtual_coils, coil_matrix, cc_region)
+    kspace_txyc = _compressed(kspace_txyc, n_slices, virtual_coils, coil_matrix, cc_region, cc_method)
     t, nx, ny = kspace_txyc.shape[0], kspace_txyc.shape[1], kspace_txyc.shape[2]
     if ops.fft_line_supported(nx) and ops.fft_line_supported(ny):
         k = _c2r((kspace_txyc.to(torch.complex64) * scaling).permute(0, 3, 1, 2).contiguous())
@@ -251,7 +322,8 @@ def _to_kspace_hip(filt: torch.Tensor) -> torch.Tensor:
 
 def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_shape=(200, 200), n_slices: int = 15,
                          filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix: Optional[torch.Tensor] = None,
-                         apply_mask: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         apply_mask: bool = True, out: Optional[torch.Tensor] = None, virtual_coils: Optional[int] = None,
+                         cc_region: int = 24) -> torch.Tensor:
     """Raw k-space of one cine slice -> the model's input, device in, device out: ``ops.apply_mask(prepare_slice(raw, ...)[0], mask)[None]``
     bit for bit, without a host synchronisation, a data-dependent shape or a launch outside the current stream, so that
     ``torch.cuda.graph`` captures it on any stream (run it once eagerly on that stream first, like a model's forward).  This is what
@@ -264,9 +336,12 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
     mask  the mask on the crop grid, uint8 or bool on the GPU: a row mask (1, T | 1, 1, X, 1, 1) (or any shape with T X or X entries in
           that order), or one that varies along the second axis, (1, T | 1, 1, X, Y, 1) (cine_apply_mask2d).  ``apply_mask=False`` hands the k-space on unmasked -- prospectively undersampled data, where the reference also
           only passes the stored mask on (data/transforms.py:331-339); ``mask`` may then be None.
-    coil_matrix  A (V, coil) complex64 ON THE GPU: compress_coils first, everything else on V virtual coils.  The per-slice
-          ``virtual_coils=`` of prepare_slice is not offered here: its eigen-decomposition checks the Gram matrix on the host, which
-          waits for the device.  Compute one matrix per scan with coil_compression_matrix and pass it.
+    coil_matrix  A (V, coil) complex64 ON THE GPU: compress_coils first, everything else on V virtual coils, e.g. one matrix per scan
+          from coil_compression_matrix.
+    virtual_coils  V: the matrix of THIS slice's kept frames, ``coil_matrix_from_gram(coil_gram(raw, n_slices, cc_region), V,
+          method="jacobi")[0]`` (cine_coil_matrix: no host read), then as with ``coil_matrix``; at most 64 coils, V <= 32.  Unlike
+          prepare_slice, V equal to the coil count is not passed through: the data change to the eigenbasis.  With ``coil_matrix``
+          also given its V rows are checked against ``virtual_coils`` (ValueError) and it is used.
     out   a contiguous float32 (1, T, C, X, Y, 2) GPU tensor to write the result into (the pipeline's static buffer).
     Returns masked k-space (1, T, C, X, Y, 2) float32."""
     x = torch.view_as_real(raw) if isinstance(raw, torch.Tensor) and raw.is_complex() and raw.dtype == torch.complex64 else raw
@@ -288,8 +363,17 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
             raise ValueError(f"coil_matrix must be (V, {c})")
         if not coil_matrix.is_cuda or coil_matrix.dtype != torch.complex64:
             raise CineHipError("prepare_masked_slice: coil_matrix must be a complex64 GPU tensor (a host matrix would be copied synchronously)")
+        if virtual_coils is not None and coil_matrix.shape[0] != int(virtual_coils):
+            raise ValueError(f"coil_matrix has {coil_matrix.shape[0]} rows, virtual_coils is {int(virtual_coils)}")
         x = torch.view_as_real(compress_coils(x, coil_matrix, n))            # (n, x, y, V, 2)
         c = coil_matrix.shape[0]
+    elif virtual_coils is not None:
+        v = int(virtual_coils)
+        if v < 1 or v > c:
+            raise ValueError(f"virtual_coils must be in 1..{c} (the coil count of this scan)")
+        a = _coil_matrix_jacobi(coil_gram(x, n, cc_region)[None], v)[0][0]   # (V, c, 2); refuses more than 64 coils / 32 virtual coils
+        x = torch.view_as_real(compress_coils(x, torch.view_as_complex(a), n))
+        c = v
     if ops.fft_line_supported(nx) and ops.fft_line_supported(ny):
         images = ops.fft2c(ops.raw_ingest(x, n, scaling), inverse=True)      # the kept frames only
         filt = gaussian_filter(crop_select(images, n, (cx, cy)), filter_size)
@@ -431,7 +515,7 @@ def ecalib(time_avg_kspace, *, r: int, method: str = "eigh"):
 
 def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(200, 200), crop_target=(180, 180), n_slices: int = 15,
                     filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, ecalib_r: int = 200, virtual_coils: Optional[int] = None,
-                    coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, espirit_method: str = "eigh"):
+                    coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, espirit_method: str = "eigh", cc_method: str = "eigh"):
     """``SliceDataset.__getitem__`` of the reference (data/mri_data.py:267-311) in one piece, on the device: scale -> IFFT2 -> crop +
     frame selection + Gaussian filter -> FFT2 (k-space of the filtered crop) -> sensitivity maps from the time-averaged k-space
     (ESPIRiT, where the reference shells out to ``bart ecalib -r 200``; pass ``sens`` (coil, X, Y) complex to use given maps) ->
@@ -440,7 +524,8 @@ def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(2
     Returns the reference's sample tuple (kspace (t, coil, X, Y) complex64, mask, target (t, cx, cy) float32, attrs, fname, dataslice)
     as numpy arrays, like the reference (the ``*DataTransform`` classes take it from there, data/transforms.py:300-352).
     ``virtual_coils`` / ``coil_matrix`` / ``cc_region``: as in prepare_slice; k-space, the calibration and ``sens`` are then on the V
-    virtual coils, so raw data with more than 32 coils calibrates whenever V <= 32.  ``espirit_method``: ``espirit_maps``' ``method``."""
+    virtual coils, so raw data with more than 32 coils calibrates whenever V <= 32.  ``espirit_method``: ``espirit_maps``' ``method``;
+    ``cc_method``: ``coil_matrix_from_gram``'s."""
     import numpy as np
     if hasattr(source, "keys") and "y" in source:
         raw = np.asarray(source["y"])
@@ -451,7 +536,7 @@ def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(2
     if not torch.cuda.is_available():
         raise CineHipError("prepare_example: the front-end kernels need a GPU (no CPU fallback)")
     y = torch.as_tensor(raw).to(torch.complex64).cuda()
-    kspace, filt = prepare_slice(y, crop_shape, n_slices, filter_size, scaling, virtual_coils, coil_matrix, cc_region)   # (t, c, X, Y, 2) each
+    kspace, filt = prepare_slice(y, crop_shape, n_slices, filter_size, scaling, virtual_coils, coil_matrix, cc_region, cc_method)   # (t, c, X, Y, 2) each
     if sens is not None and (virtual_coils is not None or coil_matrix is not None) and tuple(sens.shape)[0] != kspace.shape[1]:
         raise ValueError(f"sens has {tuple(sens.shape)[0]} coils, the compressed data {kspace.shape[1]}")
     if sens is None:

@@ -73,6 +73,20 @@ raw buffers (plain byte buffers then) are replaced by larger ones, after a drain
 buffers are checked against ``torch.cuda.mem_get_info`` before they are allocated.  A raw slice's copy is long (5.5 ms for 311 MB):
 on a hardware queue shared with slot streams it waits behind whole replays, so the ``slots + 1`` queues above matter more here.
 
+``submit_raw(..., virtual_coils=V, cc_region=24)``: every slice is compressed with the matrix of ITS OWN calibration block, as
+``prepare_slice(..., virtual_coils=V)`` does, without leaving the pipeline.  In front of the replay, where ``compress_coils`` runs for
+``coil_matrix=``, the slot's stream runs ``frontend.coil_gram`` into a static buffer of the (slot, parity), cine_coil_matrix (the
+eigenvectors by a Jacobi eigensolver in LDS, ``frontend.coil_matrix_from_gram(..., method="jacobi")``: no host read) into the buffer
+the copied matrix of ``coil_matrix=`` would occupy, and ``compress_coils``.  The result is bit for bit
+``model(prepare_masked_slice(raw, mask, ..., coil_matrix=A), mask)`` with ``A = coil_matrix_from_gram(coil_gram(raw, n_frames,
+cc_region), V, method="jacobi")[0]``.  ``(V, cc_region)`` is part of the set key and the coil count is not, so scans with different
+coil counts and one V share a set; the Gram workspaces grow like the raw buffers, after a drain.  At most 64 coils (the eigensolver's
+LDS) and V <= 32; scans with more coils take ``coil_matrix=``.  The eigensolver's record of every slice -- the residual
+max |off-diagonal| / max |diagonal| it reached, its sweeps, the kept share sum(lam[:V]) / sum(lam), lam[0] -- is copied to pinned
+memory with the outputs: ``results`` / ``drain`` raise ``CineHipError`` naming the slice's tag when the residual is not finite or
+exceeds the solver's own stopping bar 1e-14 (its sweep cap was hit, or the raw data hold a NaN), and file the record of every slice they
+hand out under ``pipe.last_coil_info[tag]`` (``CoilInfo(residual, sweeps, kept, lam0)``; the last ``COIL_INFO_KEPT`` slices).
+
 ``graphs=False`` is the explicit eager mode: same slots, streams, buffers, copies and events, with the launch sequence
 enqueued on the slot's stream for every slice.  A failure raises ``CineHipError``; nothing falls back to eager launches.
 
@@ -319,23 +333,35 @@ def _alloc_espirit(b, src, dev) -> None:
 
 
 _CC_MAX_COILS, _CC_MAX_VIRTUAL = 128, 32            # the limits of cine_coil_compress (include/cine_hip.h)
+_CM_MAX_COILS = frontend.COIL_MATRIX_MAX_COILS      # the limit of cine_coil_matrix
+COIL_RESIDUAL_MAX = 1e-14       # kLsJacobiTol (csrc/ls_jacobi.h): the eigensolver's own stopping test, missed only at its sweep cap
+COIL_INFO_KEPT = 4096           # records SlicePipeline.last_coil_info holds
+CoilInfo = collections.namedtuple("CoilInfo", "residual sweeps kept lam0")
 
 
 def raw_set_key(raw_shape, n_frames, crop_shape, filter_size, scaling, apply_mask, mask_shape, sens_shape, coil_matrix_shape=None,
-                espirit=None):
+                espirit=None, virtual_coils=None):
     """The key of the graph set that serves a ``submit_raw`` call, from shapes and settings alone: kind, kept raw shape, virtual coils,
     crop, filter, scaling, apply_mask, mask shape, sens shape.  With a coil matrix the raw coil count is NOT part of it: the compression
     runs in front of the graph, so scans with different coil counts and one V share a set.  ``espirit``: ``espirit_key(ecalib_r,
-    sign_iters)`` for ``sens_maps="espirit"``; it takes the place of the sens shape."""
+    sign_iters)`` for ``sens_maps="espirit"``; it takes the place of the sens shape.  ``virtual_coils``: ``(V, cc_region)`` for
+    ``submit_raw(..., virtual_coils=V, cc_region=...)``; the key then ends with ``("virtual", V, cc_region)`` and, as with a coil matrix,
+    leaves the coil count out.  Without it the key is what it was."""
     t, nx, ny, c = (int(v) for v in tuple(raw_shape)[:4])
     n = min(int(n_frames), t)
     if n < 1 or nx < 1 or ny < 1 or c < 1:
         raise ValueError("Invalid shapes.")
-    kept = (n, nx, ny, c) if coil_matrix_shape is None else (n, nx, ny)
+    if virtual_coils is not None and coil_matrix_shape is not None:
+        raise ValueError("raw_set_key: virtual_coils or coil_matrix_shape, not both")
+    kept = (n, nx, ny, c) if coil_matrix_shape is None and virtual_coils is None else (n, nx, ny)
     v = None if coil_matrix_shape is None else int(tuple(coil_matrix_shape)[0])
+    tail = ()
+    if virtual_coils is not None:
+        v, region = (int(q) for q in virtual_coils)
+        tail = (("virtual", v, region),)
     return ("raw", kept, v, (int(crop_shape[0]), int(crop_shape[1])), tuple(float(f) for f in filter_size), float(scaling),
             bool(apply_mask), tuple(int(m) for m in mask_shape),
-            tuple(espirit) if espirit is not None else None if sens_shape is None else tuple(int(m) for m in sens_shape))
+            tuple(espirit) if espirit is not None else None if sens_shape is None else tuple(int(m) for m in sens_shape)) + tail
 
 
 class _RawSource:
@@ -344,7 +370,7 @@ class _RawSource:
     input_names = ("raw", "mask", "sens", "cmat")
 
     def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask, ecalib_r=15,
-                 sign_iters=60):
+                 sign_iters=60, virtual_coils=None, cc_region=24):
         if not isinstance(raw, (np.ndarray, torch.Tensor)):
             raise CineHipError(f"raw: expected a torch tensor or a numpy array, got {type(raw).__name__}")
         if raw.ndim < 4 or raw.shape[0] < 1 or int(n_frames) < 1:
@@ -363,6 +389,21 @@ class _RawSource:
             raise CineHipError("filter_size: one sigma per axis of (t, coil, x, y)")
         self.scaling, self.apply_mask = float(scaling), bool(apply_mask)
         self.cmat, self.cmat_kind = None, None
+        self.vc, self.cc_region = None, None                                 # virtual_coils=: the matrix is computed in flight
+        if virtual_coils is not None:
+            if coil_matrix is not None:
+                raise CineHipError("virtual_coils computes every slice's own matrix, coil_matrix brings one: pass one of the two")
+            if isinstance(virtual_coils, bool) or not isinstance(virtual_coils, (int, np.integer)) or isinstance(cc_region, bool) \
+                    or not isinstance(cc_region, (int, np.integer)) or cc_region < 0:
+                raise CineHipError(f"virtual_coils and cc_region must be integers, cc_region >= 0; got {virtual_coils!r}, {cc_region!r}")
+            if c > _CM_MAX_COILS:
+                raise CineHipError(f"virtual_coils: this scan has {c} coils, the in-flight eigensolver takes at most {_CM_MAX_COILS}; "
+                                   f"compute one matrix per scan (frontend.coil_compression_matrix) and pass it as coil_matrix= (up to "
+                                   f"{_CC_MAX_COILS} coils)")
+            if not 1 <= virtual_coils <= min(c, _CC_MAX_VIRTUAL):
+                raise CineHipError(f"virtual_coils = {virtual_coils}: 1 <= V <= {min(c, _CC_MAX_VIRTUAL)} for this scan's {c} coils (at most "
+                                   f"{_CC_MAX_VIRTUAL} virtual coils)")
+            self.vc, self.cc_region = int(virtual_coils), int(cc_region)
         if coil_matrix is not None:
             a, self.cmat_kind = _pairs(coil_matrix, "coil_matrix")
             if a.dim() != 3 or a.shape[1] != c:
@@ -371,7 +412,8 @@ class _RawSource:
                 raise CineHipError(f"coil_matrix (V, coil) = {tuple(a.shape[:-1])}: 1 <= V <= coil, at most {_CC_MAX_VIRTUAL} virtual and "
                                    f"{_CC_MAX_COILS} physical coils")
             self.cmat = a
-        self.v = None if self.cmat is None else self.cmat.shape[0]
+        self.v = self.vc if self.vc is not None else None if self.cmat is None else self.cmat.shape[0]
+        self.cmat_shape = None if self.v is None else (self.v, c, 2)
         self.mk_shape = (1, n, self.v or c, self.crop[0], self.crop[1], 2)
         self.mask, self.mask_kind, self.mask_shape = _check_mask(mask, self.mk_shape)
         # a mask that varies along w: the rules of ``submit`` (the sensitivity network's ACS window needs a row mask)
@@ -381,12 +423,22 @@ class _RawSource:
             self.sens, self.espirit = None, espirit_key(ecalib_r, sign_iters)
         _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat)))
         self.raw_nbytes = x.numel() * 4
+        self.gram_nbytes = 0                                                 # asked of the library when a buffer is needed (_submit, alloc)
         self.key = raw_set_key((n, nx, ny, c), n, self.crop, self.filter, self.scaling, self.apply_mask, self.mask_shape,
-                               None if self.sens is None else self.sens.shape, None if self.cmat is None else self.cmat.shape, self.espirit)
+                               None if self.sens is None else self.sens.shape, None if self.cmat is None else self.cmat.shape, self.espirit,
+                               None if self.vc is None else (self.vc, self.cc_region))
+
+    def gram_bytes(self) -> int:
+        """Workspace of this slice's coil_gram (virtual_coils=), 0 otherwise."""
+        if self.vc is not None and not self.gram_nbytes:
+            n, nx, ny, c, _ = self.raw.shape
+            self.gram_nbytes = max(frontend.coil_gram_ws_bytes(n, nx, ny, c, self.cc_region), 16)
+        return self.gram_nbytes
 
     def alloc(self, pipe):
         """raw: a byte buffer (with a coil matrix it may be replaced by a larger one later: no graph holds its address).  cc: what the
-        eager compression writes and the graph reads.  mk: written and read inside the graph."""
+        eager compression writes and the graph reads.  mk: written and read inside the graph.  virtual_coils=: gram, lam and cinfo for
+        the largest coil count cine_coil_matrix takes, gws (coil_gram's workspace) replaced by a larger one like raw."""
         dev = pipe.device
         n, nx, ny = self.raw.shape[:3]
         b = {"raw": torch.empty(self.raw_nbytes, device=dev, dtype=torch.uint8),
@@ -396,6 +448,11 @@ class _RawSource:
              "mask": torch.empty(self.mask_shape, device=dev, dtype=torch.uint8),
              "sens": None if self.sens is None else torch.empty(self.sens.shape, device=dev, dtype=torch.float32)}
         b["front"] = b["cc"] if self.v is not None else self.raw_view(b)
+        if self.vc is not None:
+            b["gram"] = torch.empty(_CM_MAX_COILS * _CM_MAX_COILS, device=dev, dtype=torch.complex128)
+            b["lam"] = torch.empty(_CM_MAX_COILS, device=dev, dtype=torch.float64)
+            b["cinfo"] = torch.empty((1, frontend.COIL_MATRIX_INFO), device=dev, dtype=torch.float64)
+            b["gws"] = torch.empty(self.gram_bytes(), device=dev, dtype=torch.uint8)
         _alloc_espirit(b, self, dev)
         return b
 
@@ -403,7 +460,8 @@ class _RawSource:
         return b["raw"][:self.raw_nbytes].view(torch.float32).view(self.raw.shape)
 
     def cmat_view(self, b):
-        return b["cmat"][:self.cmat.numel() * 4].view(torch.float32).view(self.cmat.shape)
+        v, c, _ = self.cmat_shape
+        return b["cmat"][:v * c * 8].view(torch.float32).view(self.cmat_shape)
 
     def items(self, b):
         it = [("raw", self.raw_view(b), self.raw, self.raw_kind), ("mask", b["mask"], self.mask, self.mask_kind)]
@@ -435,9 +493,10 @@ class _Set:
 
     def __init__(self, key):
         self.key = key
-        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front" in a raw set)
+        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front" in a raw set; "gram", "gws", "lam", "cinfo" with virtual_coils=)
         self.raw = None         # the front-end's settings when the graphs start from raw data (the _RawSource that built the set)
         self.raw_bytes = 0      # capacity of each raw byte buffer
+        self.gram_bytes = 0     # capacity of each Gram workspace (virtual_coils=)
         self.espirit = None     # espirit_key(...) when the graphs calibrate the maps themselves (sens_maps="espirit")
         self.graphs = {}        # (slot, parity) -> (graph, static outputs)
         self.ready = {}         # (slot, parity) -> event recorded on the copy stream behind the copy into the set
@@ -475,7 +534,10 @@ class SlicePipeline:
         self.model, self.slots, self.device, self.graphs, self.out, self.zero_filled = model, slots, device, bool(graphs), out, bool(zero_filled)
         self._takes_sens, self._needs_sens = _forward_params(model)
         self._sched = SliceSchedule(slots)
-        self._recs = {}           # index -> [handle, outputs, inputs kept alive until the slice is done, ESPIRiT residuals (pinned) or None]
+        # index -> [handle, outputs, inputs kept alive until the slice is done, ESPIRiT residuals (pinned) or None, the coil eigensolver's
+        # record (pinned) or None]
+        self._recs = {}
+        self.last_coil_info = collections.OrderedDict()      # tag -> CoilInfo of the slices handed out (virtual_coils=), the last COIL_INFO_KEPT
         self._set = None
         self._closed = False
         self._builds = 0
@@ -493,17 +555,26 @@ class SlicePipeline:
 
     def submit_raw(self, raw, mask, sens_maps=None, tag=None, *, crop_shape=(200, 200), n_frames: int = 15,
                    filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True,
-                   ecalib_r: int = 15, sign_iters: int = 60) -> SliceHandle:
+                   ecalib_r: int = 15, sign_iters: int = 60, virtual_coils: Optional[int] = None, cc_region: int = 24) -> SliceHandle:
         """Enqueue one slice from its RAW k-space (t, x, y, coil) -- complex64 or float32 pairs, in any of the four places ``submit`` takes
         its input from.  Only ``raw[:min(n_frames, t)]`` is copied to the device.  ``frontend.prepare_masked_slice`` and the model run on
         the slot's stream inside the slot's graph; see the module docstring.  ``mask``: the mask on the crop grid, a row mask or one that varies along w under the
         rules of ``submit`` (the sensitivity network needs a row mask: pass ``sens_maps``); ``sens_maps``
         (1, 1, C, X, Y, 2) on the crop grid (on the V virtual coils with ``coil_matrix`` (V, coil)), or ``"espirit"``: calibrated in the
-        graph, behind the front-end, from the masked k-space it wrote (``ecalib_r``, ``sign_iters`` as in ``submit``)."""
+        graph, behind the front-end, from the masked k-space it wrote (``ecalib_r``, ``sign_iters`` as in ``submit``).
+        ``virtual_coils=V`` (with ``cc_region``, and without ``coil_matrix``): the slice is compressed to V virtual coils with the matrix
+        of its own kept frames, computed on the slot's stream (at most 64 coils, V <= 32; see the module docstring).  The kept share of
+        the slice is ``pipe.last_coil_info[tag].kept`` once ``results`` / ``drain`` have handed it out; ``tag`` must then be hashable."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit_raw after close()")
-        return self._submit(_RawSource(self, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask,
-                                       ecalib_r, sign_iters), tag)
+        src = _RawSource(self, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask,
+                         ecalib_r, sign_iters, virtual_coils, cc_region)
+        if src.vc is not None:
+            try:
+                hash(tag)
+            except TypeError:
+                raise CineHipError(f"virtual_coils: tag {tag!r} is not hashable (last_coil_info is keyed by it)") from None
+        return self._submit(src, tag)
 
     @property
     def set_builds(self) -> int:
@@ -517,8 +588,9 @@ class SlicePipeline:
                 self._set = None                               # one set alive: the old graphs and buffers go first
                 self._sched.new_buffers()
                 self._set = self._build(src)
-            elif src.raw is not None and src.raw_nbytes > self._set.raw_bytes:
-                self._grow_raw(src.raw_nbytes)                 # a scan with more coils than any before it (coil_matrix given)
+            elif src.raw is not None and (src.raw_nbytes > self._set.raw_bytes or src.gram_bytes() > self._set.gram_bytes):
+                # a scan with more coils than any before it (coil_matrix or virtual_coils given)
+                self._grow_raw(max(src.raw_nbytes, self._set.raw_bytes), max(src.gram_bytes(), self._set.gram_bytes))
             k0 = self._sched.must_retire()
             if k0 is not None:
                 self._recs[k0][0]._event.synchronize()
@@ -529,11 +601,11 @@ class SlicePipeline:
             h = SliceHandle(step.index, step.index if tag is None else tag, step.slot, step.parity, ev_done)
             try:
                 keep = self._copy_in(src, key, wait_done=step.copy_after is not None)
-                outs, resid = self._launch(key, src)
+                outs, resid, cinfo = self._launch(key, src)
             except Exception:
-                self._recs[step.index] = [h, None, None, None]
+                self._recs[step.index] = [h, None, None, None, None]
                 raise
-            self._recs[step.index] = [h, outs, keep, resid]
+            self._recs[step.index] = [h, outs, keep, resid, cinfo]
             return h
 
     def results(self, block: bool = False):
@@ -551,13 +623,23 @@ class SlicePipeline:
                     return
                 self._sched.retire_oldest()
                 continue
-            h, outs, _, resid = self._recs.pop(k)
+            h, outs, _, resid, cinfo = self._recs.pop(k)
             if outs is None:
                 continue                  # a submit that raised: nothing was launched for it
             if resid is not None and not bool((resid <= ESPIRIT_RESIDUAL_MAX).all()):       # pinned host memory, the slice is done
                 raise CineHipError(f"SlicePipeline: slice {h.tag!r}: the in-flight ESPIRiT calibration did not converge (max |X^2 - I| = "
                                    f"{float(resid.max()):.3e} > {ESPIRIT_RESIDUAL_MAX:g}): an eigenvalue of the calibration Gram matrix "
                                    "sits at the threshold; raise sign_iters")
+            if cinfo is not None:                                                           # pinned host memory, the slice is done
+                rec = CoilInfo(float(cinfo[0, 0]), int(cinfo[0, 1]), float(cinfo[0, 2]), float(cinfo[0, 3]))
+                if not rec.residual <= COIL_RESIDUAL_MAX:                                   # a NaN fails the comparison too
+                    raise CineHipError(f"SlicePipeline: slice {h.tag!r}: the in-flight coil compression's eigensolver stopped at "
+                                       f"max |off-diagonal| / max |diagonal| = {rec.residual:.3e} after {rec.sweeps} sweeps (bar "
+                                       f"{COIL_RESIDUAL_MAX:g}): its sweep cap was reached or the raw data hold a NaN")
+                self.last_coil_info[h.tag] = rec
+                self.last_coil_info.move_to_end(h.tag)
+                while len(self.last_coil_info) > COIL_INFO_KEPT:
+                    self.last_coil_info.popitem(last=False)
             if self.out == "device":
                 cur = torch.cuda.current_stream(self.device)
                 for o in outs:
@@ -611,9 +693,14 @@ class SlicePipeline:
 
     def _pre(self, b, src) -> None:
         """What runs eagerly on the slot's stream in front of the graph: with a coil matrix, the compression of this scan's raw data
-        (any coil count) into the static (T, x, y, V) buffer the graph starts from."""
-        if src.raw is not None and src.cmat is not None:
+        (any coil count) into the static (T, x, y, V) buffer the graph starts from; with virtual_coils= the Gram matrix and the
+        matrix of this slice in front of it."""
+        if src.raw is not None and src.v is not None:
             with torch.no_grad():
+                if src.vc is not None:                       # this slice's own matrix, where coil_matrix= has the copied one
+                    c = src.c
+                    g = frontend.coil_gram(src.raw_view(b), src.n, src.cc_region, out=b["gram"][:c * c].view(c, c), ws=b["gws"])
+                    frontend._coil_matrix_jacobi(g[None], src.vc, src.cmat_view(b)[None], b["lam"][:c][None], b["cinfo"])
                 frontend.compress_coils(src.raw_view(b), torch.view_as_complex(src.cmat_view(b)), src.n, out=b["cc"])
 
     def _body(self, b):
@@ -641,21 +728,26 @@ class SlicePipeline:
             raise CineHipError(f"SlicePipeline: {2 * self.slots} raw buffers of {nbytes} bytes need {need} bytes, {free} are free on "
                                f"{self.device}; slots={int(free // (2 * nbytes))} would fit")
 
-    def _grow_raw(self, nbytes: int) -> None:
-        """Larger raw byte buffers for every (slot, parity).  Only a set with a coil matrix gets here: its graphs start from the
-        compressed buffer, so nothing has to be captured again."""
+    def _grow_raw(self, nbytes: int, gram_bytes: int = 0) -> None:
+        """Larger raw byte buffers (and Gram workspaces) for every (slot, parity).  Only a set with a coil matrix or virtual_coils= gets
+        here: its graphs start from the compressed buffer, so nothing has to be captured again."""
         self._retire_all()
         st = self._set
         for b in st.bufs.values():
             b["raw"] = None
-        self._raw_memory(nbytes)
+            if gram_bytes:
+                b["gws"] = None
+        self._raw_memory(nbytes + gram_bytes)
         try:
             for b in st.bufs.values():
                 b["raw"] = torch.empty(nbytes, device=self.device, dtype=torch.uint8)
+                if gram_bytes:
+                    b["gws"] = torch.empty(gram_bytes, device=self.device, dtype=torch.uint8)
         except Exception as e:
             self._set = None
             raise CineHipError(f"SlicePipeline: allocating raw buffers of {nbytes} bytes failed: {type(e).__name__}: {e}") from e
-        st.raw_bytes = nbytes
+        st.raw_bytes, st.gram_bytes = nbytes, gram_bytes
+        self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))        # as in _build: new memory of the caller's stream
 
     def _build(self, src) -> _Set:
         """Buffers for every (slot, parity), filled with this slice's inputs; with graphs, one eager forward per slot stream
@@ -665,8 +757,9 @@ class SlicePipeline:
         st = _Set(src.key)
         try:
             if src.raw is not None:
-                self._raw_memory(src.raw_nbytes)
+                self._raw_memory(src.raw_nbytes + src.gram_bytes())
                 st.raw, st.raw_bytes = _settings_only(src), src.raw_nbytes     # the settings, not the first slice's data
+                st.gram_bytes = src.gram_bytes()
             st.espirit = src.espirit
             for i in range(S):
                 for p in (0, 1):
@@ -674,6 +767,9 @@ class SlicePipeline:
                     st.ready[(i, p)] = torch.cuda.Event()
                     st.done[(i, p)] = torch.cuda.Event()
             self._set = st
+            # the new buffers come from the pool of the caller's stream: whatever that stream still has to run on the memory they
+            # took over (an eager forward just before the first submit) goes first
+            self.copy_stream.wait_stream(torch.cuda.current_stream(dev))
             self._copy_in(src, (0, 0), wait_done=False)
             with torch.cuda.stream(self.copy_stream):
                 b0 = st.bufs[(0, 0)]
@@ -788,5 +884,8 @@ class SlicePipeline:
             resid = None
             if st.espirit is not None:          # with the outputs, on the slot's stream: read by results() once the slice is done
                 resid = torch.empty(st.bufs[key]["resid"].shape, dtype=torch.float64, pin_memory=True).copy_(st.bufs[key]["resid"], non_blocking=True)
+            cinfo = None
+            if src.raw is not None and src.vc is not None:      # the eigensolver's record of this slice, the same way
+                cinfo = torch.empty(st.bufs[key]["cinfo"].shape, dtype=torch.float64, pin_memory=True).copy_(st.bufs[key]["cinfo"], non_blocking=True)
             st.done[key].record(s)
-        return outs, resid
+        return outs, resid, cinfo

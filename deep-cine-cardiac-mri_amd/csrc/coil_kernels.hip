@@ -14,10 +14,16 @@
 //                        contiguous run of raw and of out, so both move with 16-byte accesses whatever c and V are; all of K is
 //                        resident in LDS, A is staged once per workgroup, one pass over the samples; the next tile's loads are
 //                        issued into registers before the current tile's MFMAs, so they overlap its compute and stores.
+//   cine_coil_matrix     the step between the two: G = U diag(lam) U^H, A[r] = conj(U[:, rank r]) times the unit phase that makes its
+//                        largest entry real and positive, r < V.  One workgroup per Gram matrix, G and U in LDS in float64, the cyclic
+//                        Jacobi eigensolver of the singular-value-thresholding kernels (ls_jacobi in ls_jacobi.h, unchanged).  Only the
+//                        upper triangle of G is read (mirrored, the diagonal's imaginary part dropped): Hermitian by construction, so
+//                        no check on the host.  No host read, no atomics: capturable, repeated calls are bit-identical.
 #include <cstdint>
 #include <mutex>
 #include "common.h"
 #include "conv_src.h"
+#include "ls_jacobi.h"
 
 namespace cine {
 
@@ -253,6 +259,93 @@ __global__ __launch_bounds__(cc::kThreads) void coil_compress_kernel(const float
     }
 }
 
+// ------------------------------------------------------------------ compression matrix from the Gram matrix
+struct CoilMatrixArgs {
+    const double2* gram;
+    float2* matrix;
+    double* lam;
+    double* info;
+    int c, v;
+};
+
+// the order of the eigenvalues: descending, a NaN in front of every number (a total order, so the ranks are a permutation whatever the
+// input holds), equal values by column index
+__device__ __forceinline__ bool cm_before(double a, int ia, double b, int ib) {
+    const bool an = a != a, bn = b != b;
+    if (an != bn) return an;
+    if (!an && a != b) return a > b;
+    return ia < ib;
+}
+
+// LDS (dynamic): A [c][c] | U [c][c] double2, rot [kLsRotDoubles], red [kLsRedDoubles] doubles.  After ls_jacobi red is reused:
+// [c] eigenvalues in rank order, then [c] ints, the column of every rank.
+__global__ __launch_bounds__(kLsThreads) void coil_matrix_kernel(CoilMatrixArgs a) {
+    extern __shared__ __align__(16) unsigned char cm_lds[];
+    const int T = a.c, nv = a.v, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long b = blockIdx.x;
+    double2* A = reinterpret_cast<double2*>(cm_lds);
+    double2* U = A + T * T;
+    double* rot = reinterpret_cast<double*>(U + T * T);
+    double* red = rot + kLsRotDoubles;
+    const double2* G = a.gram + b * T * T;
+    for (int e = tid; e < T * T; e += kLsThreads) {
+        const int i = e / T, j = e - i * T;
+        double2 g = i <= j ? G[e] : G[j * T + i];             // the upper triangle only
+        g.y = i < j ? g.y : (i == j ? 0.0 : -g.y);
+        A[e] = g;
+        U[e] = make_double2(i == j ? 1.0 : 0.0, 0.0);
+    }
+    __syncthreads();
+    double off, diag;
+    const int sweeps = ls_jacobi(A, U, rot, red, T, tid, off, diag);     // ends behind a barrier: rot and red are free
+    double* lams = red;
+    int* col_of = reinterpret_cast<int*>(red + kLsMaxT);
+    if (tid < T) {
+        const double l = A[tid * T + tid].x;
+        int rank = 0;
+        for (int j = 0; j < T; ++j) rank += (j != tid && cm_before(A[j * T + j].x, j, l, tid)) ? 1 : 0;
+        lams[rank] = l;
+        col_of[rank] = tid;
+        a.lam[b * T + rank] = l;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double kept = 0.0, all = 0.0;
+        for (int k = 0; k < T; ++k) { all += lams[k]; if (k == nv - 1) kept = all; }
+        double* o = a.info + b * 4;
+        o[0] = diag > 0.0 ? off / diag : off;
+        o[1] = (double)sweeps;
+        o[2] = all == 0.0 ? 1.0 : kept / all;
+        o[3] = lams[0];
+    }
+    // one wavefront per row, the coil on the lanes (c <= 64)
+    float2* M = a.matrix + b * nv * T;
+    for (int r = wave; r < nv; r += kLsThreads / 64) {
+        const int k = col_of[r];
+        const double2 u = lane < T ? U[lane * T + k] : make_double2(0.0, 0.0);
+        double m = lane < T ? hypot(u.x, u.y) : -1.0;
+        int at = lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {                     // the largest magnitude, the lowest index among equal ones
+            const double mo = __shfl_xor(m, o, 64);
+            const int ao = __shfl_xor(at, o, 64);
+            if (mo > m || (mo == m && ao < at)) { m = mo; at = ao; }
+        }
+        at = __shfl(at, 0, 64);                                // with a NaN in the row the lanes may disagree: lane 0 decides
+        at = at < 0 ? 0 : (at > T - 1 ? T - 1 : at);
+        const double2 pk = U[at * T + k];
+        const double pm = hypot(pk.x, pk.y);
+        const bool ok = pm > 0.0 && pm <= 1.79769313486231570e308;          // a zero or NaN peak does not divide
+        const double cx = ok ? pk.x / pm : 1.0, cy = ok ? pk.y / pm : 0.0;    // conj(conj(pk)) / |pk|
+        if (lane < T) {
+            // conj(u) (cx + i cy)
+            float2 w = make_float2((float)(u.x * cx + u.y * cy), (float)(u.x * cy - u.y * cx));
+            if (ok && lane == at) w = make_float2((float)pm, 0.f);
+            M[r * T + lane] = w;
+        }
+    }
+}
+
 namespace {
 
 struct GramPlan {
@@ -368,4 +461,32 @@ extern "C" int cine_coil_compress(const float* raw, const float* matrix, float* 
     if (c <= 32) return v <= 16 ? launch_compress<1, 4>(r, m, o, g, st) : launch_compress<2, 4>(r, m, o, g, st);
     if (c <= 64) return v <= 16 ? launch_compress<1, 8>(r, m, o, g, st) : launch_compress<2, 8>(r, m, o, g, st);
     return v <= 16 ? launch_compress<1, 16>(r, m, o, g, st) : launch_compress<2, 16>(r, m, o, g, st);
+}
+
+extern "C" int cine_coil_matrix(const double* gram, float* matrix, double* lam, double* info, int nb, int c, int v, void* stream) {
+    const char* what = "cine_coil_matrix";
+    CINE_REQUIRE(gram && matrix && lam && info, CINE_EINVAL, "%s: null pointer", what);
+    {
+        const void* g = gram; const void* m = matrix; const void* l = lam; const void* f = info;
+        CINE_REQUIRE(g != m && g != l && g != f && m != l && m != f && l != f, CINE_EINVAL, "%s: aliased pointers", what);
+    }
+    CINE_REQUIRE(nb >= 1 && c >= 1 && v >= 1 && v <= c, CINE_EINVAL, "%s: Invalid shapes. (matrices %d, coils %d, virtual coils %d)", what, nb, c, v);
+    CINE_REQUIRE(c <= kLsMaxT, CINE_EUNSUPPORTED, "%s: %d coils, at most %d", what, c, kLsMaxT);
+    CINE_REQUIRE(v <= cc::kMaxVirtual, CINE_EUNSUPPORTED, "%s: %d virtual coils, at most %d", what, v, cc::kMaxVirtual);
+    CINE_REQUIRE(aligned16(gram) && (reinterpret_cast<uintptr_t>(matrix) & 7u) == 0 && (reinterpret_cast<uintptr_t>(lam) & 7u) == 0 &&
+                     (reinterpret_cast<uintptr_t>(info) & 7u) == 0,
+                 CINE_EINVAL, "%s: gram must be 16-byte aligned, matrix, lam and info 8-byte aligned", what);
+    const size_t lds = (size_t)2 * c * c * sizeof(double2) + (size_t)(kLsRotDoubles + kLsRedDoubles) * sizeof(double);
+    if (lds >= 64 * 1024) {
+        static std::once_flag once[64];
+        static hipError_t status[64];
+        if (int e = ls_large_lds(reinterpret_cast<const void*>(coil_matrix_kernel), "coil_matrix_kernel", once, status)) return e;
+    }
+    CoilMatrixArgs a{};
+    a.gram = reinterpret_cast<const double2*>(gram); a.matrix = reinterpret_cast<float2*>(matrix); a.lam = lam; a.info = info;
+    a.c = c; a.v = v;
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(F_MISC, st);
+    hipLaunchKernelGGL(coil_matrix_kernel, dim3((unsigned)nb), dim3(kLsThreads), lds, st, a);
+    return check_launch("coil_matrix_kernel");
 }

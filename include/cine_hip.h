@@ -586,6 +586,19 @@ int cine_coil_gram(const float* raw, double* gram, void* ws, size_t ws_bytes, in
                    void* stream);
 int cine_coil_compress(const float* raw, const float* matrix, float* out, int t_in, int nx, int ny, int c, int t_out, int v,
                        void* stream);
+/* The eigen-decomposition between the two, on the device: gram (nb, c, c) complex128 as cine_coil_gram writes it -> matrix (nb, v, c)
+ * complex64, lam (nb, c) doubles in descending order (equal values by column index), info (nb, 4) doubles.  With G = U diag(lam) U^H:
+ * matrix[r] = conj(U[:, r]) times the unit phase that makes its largest-magnitude entry (float64 magnitudes, the lowest index among
+ * equal ones) real and positive; that entry is stored with imaginary part 0, every entry is rounded once to complex64; a zero or NaN
+ * peak leaves the row's phase alone.  Only the upper triangle of gram is read (mirrored, the diagonal's imaginary part taken as 0), so
+ * the input is Hermitian by construction.  One workgroup per matrix, everything in LDS in float64: the cyclic Jacobi eigensolver of
+ * cine_svt_weight (until max |off-diagonal| <= 1e-14 max |diagonal| or 40 sweeps; a NaN ends at the cap).  info: the residual max
+ * |off-diagonal| / max |diagonal| reached, the sweeps used, the kept share sum(lam[:v]) / sum(lam) (1 for a zero matrix), lam[0].
+ * nb >= 1, c >= 1, 1 <= v <= c, distinct non-null pointers, gram 16-byte and the outputs 8-byte aligned (else CINE_EINVAL); at most 64
+ * coils (the two c x c float64 matrices fill the LDS; cine_coil_gram and cine_coil_compress go on to 128) and 32 virtual coils (else
+ * CINE_EUNSUPPORTED, the limit is in the message).  Every argument is checked before the launch; no allocation, no host read, no
+ * atomics: capturable, and the same bits on every call. */
+int cine_coil_matrix(const double* gram, float* matrix, double* lam, double* info, int nb, int c, int v, void* stream);
 /* One axis pass of scipy.ndimage.gaussian_filter as transforms.py:216-217 calls it (mode 'reflect', truncate 4.0, weights and
  * accumulation in float64, float32 result) over a (outer, n, inner) array of complex pairs: the real and imaginary parts
  * are filtered alike.  The caller runs one pass per axis with sigma > 0, in axis order (mri_data.py:279: [0.7, 0, 0.3, 0.3]). */

@@ -20,7 +20,16 @@ raw, and beside them "today's way" in the same process: ``torch.as_tensor(raw).c
 ``submit``.  ``h2d_*``: the bytes one slice moves to the device and the rate that copy ALONE allows (pinned -> HBM on one stream,
 nothing else running); ``bound``: which of the two, that copy or the GPU (the device-resident rate), is the lower and so limits a
 pinned input, and ``pinned_over_limit`` how close the pinned rate comes to it.  Also the ingest kernel alone (hipEvent median) as a
-fraction of the device's copy rate measured in the same run.  Without --raw the output is unchanged."""
+fraction of the device's copy rate measured in the same run.  Without --raw the output is unchanged.
+
+    python tools/pipeline_rate.py --raw --virtual-coils 15 [--hw-queues 16] [--out profiles/virtual_coils_inflight_rate.json]
+
+Per-slice coil compression, 30 -> V coils, on 15 x 384 x 144 x 30 and 15 x 416 x 208 x 30 (pinned raw data with a designed coil
+spectrum, every slice its own): ``submit_raw(..., virtual_coils=V)`` ("in flight"), beside it today's way -- per slice a copy to the
+device, ``frontend.coil_compression_matrix`` (torch.linalg.eigh behind a host check), ``submit_raw(..., coil_matrix=A)`` -- and, as the
+ceiling, ``coil_matrix=`` with one matrix per scan computed beforehand.  Medians of --repeats regions, warm-up outside the clock; the
+spread of a line is max - min of its regions.  Also cine_coil_matrix alone (hipEvent, median of 20) at 15, 30 and 64 coils, and the
+Jacobi sweeps every slice took."""
 import argparse
 import json
 import os
@@ -234,6 +243,120 @@ def raw_main(args):
     print(json.dumps({k: v for k, v in doc.items() if k != "scans"}), flush=True)
 
 
+def _designed(shape, seed, dev):
+    """Complex64 (t, x, y, coil) on the host at the amplitude of a k-space: white samples scaled per coil by sigma_i^2 =
+    1e-4^(i / (c - 1)) and mixed by a seeded random unitary matrix (the designed input of tests/test_coil_compress.py)."""
+    c = shape[3]
+    rs = np.random.RandomState(seed)
+    q, _ = np.linalg.qr(rs.standard_normal((c, c)) + 1j * rs.standard_normal((c, c)))
+    sigma = np.sqrt(1e-4 ** (np.arange(c) / max(c - 1, 1)))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    w = torch.view_as_complex(torch.randn(shape + (2,), generator=g, device=dev, dtype=torch.float32))
+    mix = torch.from_numpy((sigma[:, None] * q.T).astype(np.complex64)).to(dev)
+    return (1e-6 * (w @ mix)).cpu()
+
+
+def virtual_coils_main(args):
+    import bench
+    from cine_hip import frontend as FE, synth
+    from cine_hip.pipeline import SlicePipeline
+    cfg = bench.CONFIGS[2]()
+    dev = torch.device("cuda:0")
+    V, S, n, warm, reps = args.virtual_coils, args.slots, args.slices or 40, args.warmup if args.warmup is not None else 8, args.repeats
+    net = cfg["hip"]().eval()
+    synth.fill_parameters_(net, cfg["wseed"], keep=cfg["keep"])
+    net = net.to(dev)
+    commit, csrc = _stamp(args.commit)
+    doc = {"metric": "cine slices/sec from raw k-space with per-slice coil compression (SlicePipeline.submit_raw)", "config": 2,
+           "name": cfg["name"], "virtual_coils": V, "cc_region": 24, "slots": S, "slices_per_region": n, "warmup_slices": warm,
+           "regions": reps, "statistic": "median of the regions; spread = max - min of the regions",
+           "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "device": torch.cuda.get_device_name(dev), "commit": commit,
+           "csrc_sha256": csrc, "lines": {"in_flight": "submit_raw(pinned, virtual_coils=V)",
+                                          "todays_way": "per slice: pinned.cuda(), coil_compression_matrix (eigh), submit_raw(device, coil_matrix=A)",
+                                          "ceiling": "submit_raw(pinned, coil_matrix=A), one matrix per scan computed beforehand"},
+           "coil_matrix_kernel": [], "scans": []}
+
+    for c in (15, 30, 64):                                       # the kernel alone, on the Gram matrix of a designed input
+        g = FE.coil_gram(_designed((2, 24, 24, c), 9, dev).to(dev), 2, 24)[None].contiguous()
+        v = min(V, c)
+        outs = FE._coil_matrix_jacobi(g, v)
+        ms = _event_ms(lambda: FE._coil_matrix_jacobi(g, v, *outs), 20)
+        info = outs[2][0].tolist()
+        doc["coil_matrix_kernel"].append({"coils": c, "virtual_coils": v, "median_ms": _median(ms), "min_ms": min(ms), "launches": len(ms),
+                                          "sweeps": int(info[1]), "residual": info[0]})
+    print(json.dumps(doc["coil_matrix_kernel"]), flush=True)
+
+    n_raws = 4
+    for name, shape in (("line_384x144x30", (FRAMES, 384, 144, 30)), ("window_416x208x30", (FRAMES, 416, 208, 30))):
+        t, nx, ny, c = shape
+        crop = (min(200, nx), min(200, ny))
+        rng = np.random.default_rng(nx + c)
+        pinned = [_designed(shape, 100 + nx + j, dev).pin_memory() for j in range(n_raws)]
+        dmasks = []
+        for j in range(n_raws):
+            m = (rng.uniform(size=(1, FRAMES, 1, crop[0], 1, 1)) < 0.25).astype(np.uint8)
+            m[:, :, :, crop[0] // 2 - 8 - j:crop[0] // 2 + 8 + j] = 1
+            dmasks.append(torch.from_numpy(m).to(dev))
+        scan_matrix = FE.coil_compression_matrix(pinned[0].to(dev), V, FRAMES)[0]
+        kw = dict(crop_shape=crop, n_frames=FRAMES, filter_size=FILTER, scaling=SCALING)
+        row = {"scan": name, "raw_shape": list(shape), "crop": list(crop), "frames": FRAMES, "h2d_bytes_per_slice": pinned[0].numel() * 8}
+
+        def submit(line, pipe, j):
+            if line == "in_flight":
+                pipe.submit_raw(pinned[j], dmasks[j], virtual_coils=V, **kw)
+            elif line == "ceiling":
+                pipe.submit_raw(pinned[j], dmasks[j], coil_matrix=scan_matrix, **kw)
+            else:
+                y = pinned[j].cuda()
+                a, _ = FE.coil_compression_matrix(y, V, FRAMES)
+                pipe.submit_raw(y, dmasks[j], coil_matrix=a, **kw)
+
+        def run(line, pipe, count):
+            got = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(count):
+                submit(line, pipe, k % n_raws)
+                for _ in pipe.results():
+                    got += 1
+            for _ in pipe.drain():
+                got += 1
+            torch.cuda.synchronize()
+            assert got == count
+            return count / (time.perf_counter() - t0)
+
+        with torch.no_grad():
+            a0 = FE.coil_matrix_from_gram(FE.coil_gram(pinned[0].to(dev), FRAMES, 24), V, method="jacobi")[0]
+            want = net(FE.prepare_masked_slice(pinned[0].to(dev), dmasks[0], crop, FRAMES, FILTER, SCALING, coil_matrix=a0), dmasks[0]).cpu()
+        for line in ("in_flight", "todays_way", "ceiling"):
+            with SlicePipeline(net, slots=S) as pipe:
+                if line == "in_flight":
+                    pipe.submit_raw(pinned[0], dmasks[0], virtual_coils=V, **kw)
+                    (_, o0), = list(pipe.drain())
+                    row["bit_identical_to_sequential"] = bool(torch.equal(o0.cpu(), want))
+                run(line, pipe, warm)
+                rs = [run(line, pipe, n) for _ in range(reps)]
+                assert pipe.set_builds == 1
+                row[f"value_{line}"], row[f"regions_{line}"], row[f"spread_{line}"] = _median(rs), rs, max(rs) - min(rs)
+                if line == "in_flight":
+                    recs = list(pipe.last_coil_info.values())
+                    row["sweeps_min"], row["sweeps_max"] = min(r.sweeps for r in recs), max(r.sweeps for r in recs)
+                    row["kept_share_min"], row["residual_max"] = min(r.kept for r in recs), max(r.residual for r in recs)
+        row["in_flight_over_todays_way"] = row["value_in_flight"] / row["value_todays_way"]
+        row["in_flight_over_ceiling"] = row["value_in_flight"] / row["value_ceiling"]
+        row["in_flight_not_below_todays_way_by_more_than_the_spread"] = bool(
+            row["value_in_flight"] >= row["value_todays_way"] - max(row["spread_in_flight"], row["spread_todays_way"]))
+        doc["scans"].append(row)
+        print(json.dumps(row), flush=True)
+        del pinned, dmasks
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+    print(json.dumps({k: v for k, v in doc.items() if k != "scans"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5))
@@ -246,9 +369,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="--raw: timed regions per input form")
     ap.add_argument("--out", default=None, help="--raw: also write the whole result to this JSON file")
     ap.add_argument("--commit", default=None, help="--raw: the commit to stamp the result with (default: git rev-parse HEAD)")
+    ap.add_argument("--virtual-coils", type=int, default=None, help="--raw: per-slice coil compression to this many virtual coils, in flight "
+                    "beside today's way and the coil_matrix= ceiling (see the module docstring)")
     args = ap.parse_args()
+    if args.virtual_coils is not None and not args.raw:
+        ap.error("--virtual-coils goes with --raw")
     if args.raw:
-        return raw_main(args)
+        return virtual_coils_main(args) if args.virtual_coils is not None else raw_main(args)
     args.slices = 300 if args.slices is None else args.slices
     args.warmup = 20 if args.warmup is None else args.warmup
     import bench
