@@ -10,6 +10,12 @@
                     calibration.  ``prepare_slice(..., virtual_coils=V)`` runs it in place.  ``method="jacobi"`` takes the eigenvectors
                     from cine_coil_matrix (a Jacobi eigensolver in LDS) instead of torch.linalg.eigh: no host read, capturable, what
                     ``prepare_masked_slice(..., virtual_coils=V)`` and ``SlicePipeline.submit_raw(..., virtual_coils=V)`` run per slice.
+``noise_covariance`` / ``noise_whitener``
+                    noise pre-whitening, the first step of a raw-data front-end (Gadgetron, BART): from a scan's noise samples the
+                    covariance Psi = L L^H and the whitener W = s L^-1, once per scan.  ``whitener=W`` folds it into the compression
+                    matrix (``coil_matrix_from_gram``; "jacobi": cine_coil_matrix_whitened, per slice, no host read), so the one
+                    pass of ``compress_coils`` whitens and compresses: SVD compression, ESPIRiT's threshold and the least-squares
+                    data terms behind it all assume white noise.
 ``prepare_masked_slice``
                     prepare_slice's k-space with the row mask applied, device in, device out, capturable by a hipGraph: what
                     ``SlicePipeline.submit_raw`` runs per slice.  Line-engine raw sizes enter through ops.raw_ingest (kept frames only).
@@ -159,9 +165,10 @@ def _cc_method(method) -> str:
 
 
 def _coil_matrix_jacobi(gram: torch.Tensor, v: int, matrix: Optional[torch.Tensor] = None, lam: Optional[torch.Tensor] = None,
-                        info: Optional[torch.Tensor] = None):
+                        info: Optional[torch.Tensor] = None, whitener: Optional[torch.Tensor] = None):
     """cine_coil_matrix on gram (n, c, c) complex128, contiguous, on the GPU -> (matrix (n, V, c, 2) float32, lam (n, c) float64, info
-    (n, COIL_MATRIX_INFO) float64), written into the given contiguous tensors where they are passed.  No host read."""
+    (n, COIL_MATRIX_INFO) float64), written into the given contiguous tensors where they are passed.  No host read.
+    ``whitener`` (c, c) complex128, contiguous, on the same GPU: cine_coil_matrix_whitened, one whitener for all n matrices."""
     if not (isinstance(gram, torch.Tensor) and gram.is_cuda and gram.dtype == torch.complex128 and gram.dim() == 3
             and gram.shape[1] == gram.shape[2] and gram.is_contiguous()):
         raise CineHipError("coil_matrix_from_gram(method='jacobi'): gram must be a contiguous complex128 GPU tensor (no CPU fallback)")
@@ -176,12 +183,107 @@ def _coil_matrix_jacobi(gram: torch.Tensor, v: int, matrix: Optional[torch.Tenso
         elif not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and tuple(x.shape) == shape and x.is_contiguous()):
             raise CineHipError(f"coil_matrix_from_gram: {name} must be a contiguous {dtype} GPU tensor of shape {shape}")
         outs.append(x)
+    if whitener is not None:
+        if not (isinstance(whitener, torch.Tensor) and whitener.is_cuda and whitener.device == dev and whitener.dtype == torch.complex128
+                and tuple(whitener.shape) == (c, c) and whitener.is_contiguous()):
+            raise CineHipError(f"coil_matrix_from_gram: whitener must be a contiguous complex128 tensor of shape {(c, c)} on {dev}")
+        check(lib().cine_coil_matrix_whitened(gram.data_ptr(), whitener.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(),
+                                              outs[2].data_ptr(), n, c, v, ops._stream()), "cine_coil_matrix_whitened")
+        return tuple(outs)
     check(lib().cine_coil_matrix(gram.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), n, c, v, ops._stream()),
           "cine_coil_matrix")
     return tuple(outs)
 
 
-def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int, method: str = "eigh"):
+NOISE_MAX_COILS = 128           # cine_coil_gram's limit
+
+
+def noise_covariance(noise: torch.Tensor) -> torch.Tensor:
+    """Noise samples (..., coil) complex64 on the GPU (the noise scan of a raw file, any leading axes) -> their covariance Psi (coil,
+    coil) complex128, Psi[i, j] = 1/n sum_s eta_s[i] conj(eta_s[j]) (the index convention of coil_gram): ``coil_gram`` of the samples
+    viewed as (1, n, 1, coil) with region 0, divided by n -- float64 sums of exact products in a fixed order, exactly Hermitian,
+    bit-identical from call to call.  At most 128 coils."""
+    if not isinstance(noise, torch.Tensor) or not noise.is_complex() or noise.dim() < 1 or noise.shape[-1] < 1 or noise.numel() < 1:
+        raise ValueError("noise_covariance: noise must be a complex tensor (..., coil) with at least one sample")
+    if not noise.is_cuda:
+        raise CineHipError("noise_covariance: the HIP path needs a GPU tensor (no CPU fallback)")
+    c = noise.shape[-1]
+    if c > NOISE_MAX_COILS:
+        raise CineHipError(f"noise_covariance: {c} coils, at most {NOISE_MAX_COILS}")
+    x = noise.to(torch.complex64).reshape(-1, c)
+    n = x.shape[0]
+    return coil_gram(x.view(1, n, 1, c), None, 0) / n
+
+
+def _lower_real_diag(w: torch.Tensor) -> torch.Tensor:
+    """What the kernel reads of a whitener: its lower triangle, the diagonal's imaginary part taken as 0 (a copy)."""
+    w = torch.tril(w).contiguous()
+    torch.view_as_real(w)[..., 1].diagonal().zero_()
+    return w
+
+
+def noise_whitener(noise: Optional[torch.Tensor] = None, *, cov: Optional[torch.Tensor] = None, preserve_scale: bool = True) -> torch.Tensor:
+    """The whitener of a scan's noise, W (coil, coil) complex128 on the input's device: with Psi = ``noise_covariance(noise)`` (or ``cov``,
+    a covariance computed elsewhere, GPU or CPU) = L L^H, L lower-triangular with a real positive diagonal, W = s L^-1 -- lower-triangular
+    with a real positive diagonal, W Psi W^H = s^2 I.  ``preserve_scale`` (the default): s = sqrt(trace(Psi) / coil), so the whitened data
+    d' = W d keep their overall level; otherwise s = 1 (unit noise variance per channel).  Once per scan: a small dense step
+    (torch.linalg.cholesky_ex, solve_triangular in complex128) that waits for the device, like ``method="eigh"``.  Pass W as
+    ``whitener=`` to coil_matrix_from_gram / coil_compression_matrix / prepare_slice / prepare_masked_slice /
+    SlicePipeline.submit_raw.  ValueError when Psi is not finite or not positive definite."""
+    if (noise is None) == (cov is None):
+        raise ValueError("noise_whitener: pass the noise samples or cov=, one of the two")
+    if cov is None:
+        psi = noise_covariance(noise)
+    else:
+        if not isinstance(cov, torch.Tensor) or cov.dim() != 2 or cov.shape[0] != cov.shape[1] or cov.shape[0] < 1:
+            raise ValueError("noise_whitener: cov must be a square matrix (coil, coil)")
+        psi = cov.to(torch.complex128)
+    c = psi.shape[0]
+    short = ("the noise covariance is not positive definite: too few noise samples is the usual cause (fewer samples than coils give a "
+             "rank-deficient matrix); pass more of the noise scan")
+    if not bool(torch.isfinite(torch.view_as_real(psi)).all()):
+        raise ValueError("noise_whitener: the noise covariance is not finite (NaN or Inf in the noise samples)")
+    if float((psi - psi.conj().transpose(0, 1)).abs().max()) > 1e-12 * float(psi.abs().max()):
+        raise ValueError("noise_whitener: the noise covariance is not Hermitian")
+    low, info = torch.linalg.cholesky_ex(psi)
+    if int(info) != 0:
+        raise ValueError(f"noise_whitener: {short}")
+    # A pivot L[i, i]^2 = Psi[i, i] - sum_k |L[i, k]|^2 carries the rounding of its c terms, about c eps Psi[i, i]: one that is no larger
+    # is zero at float64 resolution, and rounding alone lets the factorisation of a rank-deficient matrix run through.
+    d = low.diagonal().real
+    if bool((d * d <= c * torch.finfo(torch.float64).eps * psi.diagonal().real).any()):
+        raise ValueError(f"noise_whitener: {short}")
+    w = torch.linalg.solve_triangular(low, torch.eye(c, dtype=torch.complex128, device=psi.device), upper=False)
+    if preserve_scale:
+        w = w * torch.sqrt(psi.diagonal().real.sum() / c)
+    return _lower_real_diag(w)
+
+
+def _whitener_for(whitener, c: int, device) -> torch.Tensor:
+    """A given whitener as (c, c) complex128 on `device`."""
+    if not isinstance(whitener, torch.Tensor) or whitener.dim() != 2 or tuple(whitener.shape) != (c, c):
+        raise ValueError(f"whitener must be a ({c}, {c}) tensor for {c} coils (frontend.noise_whitener)")
+    return whitener.to(device=device, dtype=torch.complex128)
+
+
+def _hermitian_from_upper(g: torch.Tensor) -> torch.Tensor:
+    """The Hermitian matrix the kernel makes of g: its upper triangle mirrored, the diagonal's imaginary part dropped."""
+    up = torch.triu(g, 1)
+    return up + up.conj().transpose(0, 1) + torch.diag(g.diagonal().real).to(g.dtype)
+
+
+def _phase_rows(a: torch.Tensor) -> torch.Tensor:
+    """Every row of a (V, c) complex128 times the unit phase that makes its largest-magnitude entry (the first of equal maxima) real and
+    positive; that entry exactly real."""
+    mag = a.abs()
+    idx = mag.argmax(dim=1, keepdim=True)                                    # the first of equal maxima
+    peak = a.gather(1, idx)
+    a = a * (peak.conj() / peak.abs())
+    a.scatter_(1, idx, mag.gather(1, idx).to(a.dtype))                       # exactly real there
+    return a
+
+
+def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int, method: str = "eigh", whitener: Optional[torch.Tensor] = None):
     """G (c, c) Hermitian -> (A (V, c) complex64, lam (c,) float64 descending): G = U diag(lam) U^H, A[v] = conj(U[:, v]) times the unit
     phase that makes its largest-magnitude entry (lowest index on a tie) real and positive, rounded once to complex64.  Rows are
     orthonormal and A G A^H = diag(lam[:V]).  G (n, c, c): n matrices at once, every result with a leading n.
@@ -191,7 +293,13 @@ def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int, method: str = 
     (CineHipError beyond).  It reads the upper triangle of G only, so there is nothing to check; no host read, capturable, bit-identical
     from call to call.  Returns (A, lam, info) with info (COIL_MATRIX_INFO,) float64 ON THE DEVICE: the residual max |off-diagonal| /
     max |diagonal| the eigensolver reached (at most 1e-14 unless its sweep cap was hit or G holds a NaN), the sweeps used, the kept
-    share sum(lam[:V]) / sum(lam), lam[0]."""
+    share sum(lam[:V]) / sum(lam), lam[0].
+    ``whitener=W`` (c, c), from ``noise_whitener``: noise pre-whitening folded into the matrix.  The decomposition is that of the
+    whitened data's Gram matrix G' = W G W^H = U diag(lam) U^H, and A[v] = sum_k conj(U[k, v]) W[k, :], phased and rounded as above:
+    ``compress_coils(raw, A)`` whitens and compresses in one pass.  A Psi A^H = s^2 I and A G A^H = diag(lam[:V]); the rows are no
+    longer orthonormal.  Only the lower triangle of W is used, its diagonal taken as real.  "jacobi": cine_coil_matrix_whitened, one W
+    for all n matrices; "eigh": the same mathematics with torch in complex128 on the tensor's own device.  ``whitener=None``: as
+    before, bit for bit."""
     _cc_method(method)
     if gram.dim() not in (2, 3) or gram.shape[-2] != gram.shape[-1] or gram.shape[-1] < 1 or gram.shape[0] < 1:
         raise ValueError("coil_matrix_from_gram: gram must be a square matrix or a stack of them")
@@ -203,33 +311,35 @@ def coil_matrix_from_gram(gram: torch.Tensor, virtual_coils: int, method: str = 
         if not gram.is_cuda:
             raise CineHipError("coil_matrix_from_gram(method='jacobi'): the HIP path needs a GPU tensor (no CPU fallback)")
         g = gram.to(torch.complex128).contiguous()
-        a, lam, info = _coil_matrix_jacobi(g if g.dim() == 3 else g[None], v)
+        w = None if whitener is None else _whitener_for(whitener, c, g.device).contiguous()
+        a, lam, info = _coil_matrix_jacobi(g if g.dim() == 3 else g[None], v, whitener=w)
         a = torch.view_as_complex(a)
         return (a, lam, info) if gram.dim() == 3 else (a[0], lam[0], info[0])
     if gram.dim() == 3:
-        each = [coil_matrix_from_gram(g, v) for g in gram]
+        each = [coil_matrix_from_gram(g, v, whitener=whitener) for g in gram]
         return torch.stack([a for a, _ in each]), torch.stack([lam for _, lam in each])
     g = gram.to(torch.complex128)
     if float((g - g.conj().transpose(0, 1)).abs().max()) > 1e-12 * float(g.abs().max()):
         raise ValueError("coil_matrix_from_gram: gram is not Hermitian")
+    w = None
+    if whitener is not None:
+        w = _lower_real_diag(_whitener_for(whitener, c, g.device))
+        g = _hermitian_from_upper(w @ _hermitian_from_upper(g) @ w.conj().transpose(0, 1))     # G' = W G W^H
     try:
         ev, vec = torch.linalg.eigh(g)                                       # ascending
     except RuntimeError as e:                                                # no silent host fallback
         raise CineHipError(f"coil_matrix_from_gram: torch.linalg.eigh failed on {g.device}: {e}") from e
     lam = ev.flip(0).contiguous()
     a = vec.flip(1)[:, :v].conj().transpose(0, 1).contiguous()               # (V, c)
-    mag = a.abs()
-    idx = mag.argmax(dim=1, keepdim=True)                                    # the first of equal maxima
-    peak = a.gather(1, idx)
-    a = a * (peak.conj() / peak.abs())
-    a.scatter_(1, idx, mag.gather(1, idx).to(a.dtype))                       # exactly real there
-    return a.to(torch.complex64), lam
+    if w is not None:
+        a = a @ w                                                            # U^H W
+    return _phase_rows(a).to(torch.complex64), lam
 
 
 def coil_compression_matrix(raw: torch.Tensor, virtual_coils: int, n_frames: Optional[int] = None,
-                            region: int = 24, cc_method: str = "eigh"):
-    """coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils, cc_method): (A, lam), with "jacobi" (A, lam, info)."""
-    return coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils, _cc_method(cc_method))
+                            region: int = 24, cc_method: str = "eigh", whitener: Optional[torch.Tensor] = None):
+    """coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils, cc_method, whitener): (A, lam), with "jacobi" (A, lam, info)."""
+    return coil_matrix_from_gram(coil_gram(raw, n_frames, region), virtual_coils, _cc_method(cc_method), whitener)
 
 
 def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -252,10 +362,35 @@ def compress_coils(raw: torch.Tensor, matrix: torch.Tensor, n_frames: Optional[i
     return torch.view_as_complex(out)
 
 
-def _compressed(kspace_txyc: torch.Tensor, n_slices: int, virtual_coils, coil_matrix, cc_region: int, cc_method: str = "eigh") -> torch.Tensor:
+WHITENER_WITH_MATRIX = ("whitener and coil_matrix: a given matrix is applied as it is; fold the whitener into it, "
+                        "coil_matrix_from_gram(..., whitener=W), and pass that matrix alone")
+
+
+def _whitener_alone(whitener: torch.Tensor, c: int) -> torch.Tensor:
+    """The whitener as the (c, c) complex64 matrix compress_coils applies when no compression is asked for."""
+    if c > 32:
+        raise CineHipError(f"whitener alone keeps all {c} channels, compress_coils writes at most 32: pass virtual_coils= as well (the "
+                           f"whitener is then folded into the compression matrix)")
+    return whitener.to(torch.complex64)
+
+
+def _compressed(kspace_txyc: torch.Tensor, n_slices: int, virtual_coils, coil_matrix, cc_region: int, cc_method: str = "eigh",
+                whitener=None) -> torch.Tensor:
     """The coil-compression leg of prepare_slice: the raw data on virtual coils (kept frames only), or the input itself where
     nothing is to be done."""
     _cc_method(cc_method)
+    if whitener is not None:
+        if coil_matrix is not None:
+            raise ValueError(WHITENER_WITH_MATRIX)
+        c = kspace_txyc.shape[3]
+        w = _whitener_for(whitener, c, kspace_txyc.device)
+        if virtual_coils is None:
+            return compress_coils(kspace_txyc, _whitener_alone(w, c), n_slices)
+        v = int(virtual_coils)
+        if v < 1 or v > c:
+            raise ValueError(f"virtual_coils must be in 1..{c} (the coil count of this scan)")
+        a = coil_compression_matrix(kspace_txyc, v, n_slices, cc_region, cc_method, w)[0]      # V == c too: the data are whitened
+        return compress_coils(kspace_txyc, a, n_slices)
     if virtual_coils is None and coil_matrix is None:
         return kspace_txyc
     c = kspace_txyc.shape[3]
@@ -276,7 +411,8 @@ def _compressed(kspace_txyc: torch.Tensor, n_slices: int, virtual_coils, coil_ma
 
 def prepare_slice(kspace_txyc: torch.Tensor, crop_shape=(200, 200), n_slices: int = 15,
                   filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, virtual_coils: Optional[int] = None,
-                  coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, cc_method: str = "eigh"):
+                  coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, cc_method: str = "eigh",
+                  whitener: Optional[torch.Tensor] = None):
     """reference data/mri_data.py:283-293 on the device.  kspace_txyc: raw (t, x, y, coil) complex64 (the HDF5 ``y`` array)
     on the GPU.  Returns (kspace (t, coil, X, Y, 2) float32 of the filtered crop, filtered images (t, coil, X, Y, 2)).  Raw sizes the FFT
     line engines take go through the full-image cine_fft2c; any other raw size through the windowed transform (ops.raw_window_ifft2c),
@@ -284,10 +420,14 @@ def prepare_slice(kspace_txyc: torch.Tensor, crop_shape=(200, 200), n_slices: in
     ``virtual_coils=V``: the coils are first compressed to V virtual coils with the matrix of this slice's kept frames
     (coil_compression_matrix, calibration block cc_region), and everything runs on V coils; V equal to the coil count passes the data
     through.  ``coil_matrix=A`` (V, coil): use a given matrix instead, e.g. one matrix for all slices of a scan.  ``cc_method``:
-    ``coil_matrix_from_gram``'s ``method`` for the matrix of ``virtual_coils=``."""
+    ``coil_matrix_from_gram``'s ``method`` for the matrix of ``virtual_coils=``.
+    ``whitener=W`` (coil, coil), from ``noise_whitener`` on the scan's noise samples: noise pre-whitening in front of everything.  With
+    ``virtual_coils=V`` the whitened compression matrix of this slice's own calibration block (``coil_matrix_from_gram(...,
+    whitener=W)``: one pass over the data, V equal to the coil count included); alone, ``compress_coils(raw, W)`` (at most 32 coils).
+    Together with ``coil_matrix`` it raises: fold it into that matrix."""
     if not kspace_txyc.is_cuda:
         raise CineHipError("prepare_slice: the HIP path needs a GPU tensor (no CPU fallback)")
-    kspace_txyc = _compressed(kspace_txyc, n_slices, virtual_coils, coil_matrix, cc_region, cc_method)
+    kspace_txyc = _compressed(kspace_txyc, n_slices, virtual_coils, coil_matrix, cc_region, cc_method, whitener)
     t, nx, ny = kspace_txyc.shape[0], kspace_txyc.shape[1], kspace_txyc.shape[2]
     if ops.fft_line_supported(nx) and ops.fft_line_supported(ny):
         k = _c2r((kspace_txyc.to(torch.complex64) * scaling).permute(0, 3, 1, 2).contiguous())
@@ -323,7 +463,7 @@ def _to_kspace_hip(filt: torch.Tensor) -> torch.Tensor:
 def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_shape=(200, 200), n_slices: int = 15,
                          filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix: Optional[torch.Tensor] = None,
                          apply_mask: bool = True, out: Optional[torch.Tensor] = None, virtual_coils: Optional[int] = None,
-                         cc_region: int = 24) -> torch.Tensor:
+                         cc_region: int = 24, whitener: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Raw k-space of one cine slice -> the model's input, device in, device out: ``ops.apply_mask(prepare_slice(raw, ...)[0], mask)[None]``
     bit for bit, without a host synchronisation, a data-dependent shape or a launch outside the current stream, so that
     ``torch.cuda.graph`` captures it on any stream (run it once eagerly on that stream first, like a model's forward).  This is what
@@ -342,6 +482,9 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
           method="jacobi")[0]`` (cine_coil_matrix: no host read), then as with ``coil_matrix``; at most 64 coils, V <= 32.  Unlike
           prepare_slice, V equal to the coil count is not passed through: the data change to the eigenbasis.  With ``coil_matrix``
           also given its V rows are checked against ``virtual_coils`` (ValueError) and it is used.
+    whitener  W (coil, coil) complex128 ON THE GPU (``noise_whitener``): noise pre-whitening.  With ``virtual_coils=V`` the matrix is
+          ``coil_matrix_from_gram(coil_gram(raw, n_slices, cc_region), V, method="jacobi", whitener=W)[0]`` (cine_coil_matrix_whitened: no
+          host read, capturable); alone, ``coil_matrix=W.to(torch.complex64)`` (at most 32 coils).  With ``coil_matrix`` it raises.
     out   a contiguous float32 (1, T, C, X, Y, 2) GPU tensor to write the result into (the pipeline's static buffer).
     Returns masked k-space (1, T, C, X, Y, 2) float32."""
     x = torch.view_as_real(raw) if isinstance(raw, torch.Tensor) and raw.is_complex() and raw.dtype == torch.complex64 else raw
@@ -358,6 +501,16 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
     if not (0 < cx <= nx and 0 < cy <= ny):
         raise ValueError("Invalid shapes.")                                  # transforms.py:206-207
     n = _kept_frames(n_slices, t)
+    if whitener is not None:
+        if coil_matrix is not None:
+            raise ValueError(WHITENER_WITH_MATRIX)
+        if not isinstance(whitener, torch.Tensor) or whitener.dim() != 2 or tuple(whitener.shape) != (c, c):
+            raise ValueError(f"whitener must be a ({c}, {c}) tensor for {c} coils (frontend.noise_whitener)")
+        if not whitener.is_cuda or whitener.dtype != torch.complex128 or not whitener.is_contiguous():
+            raise CineHipError("prepare_masked_slice: whitener must be a contiguous complex128 GPU tensor (a host matrix would be copied "
+                               "synchronously)")
+        if virtual_coils is None:
+            coil_matrix = _whitener_alone(whitener, c)
     if coil_matrix is not None:
         if not isinstance(coil_matrix, torch.Tensor) or coil_matrix.dim() != 2 or coil_matrix.shape[1] != c:
             raise ValueError(f"coil_matrix must be (V, {c})")
@@ -371,7 +524,7 @@ def prepare_masked_slice(raw: torch.Tensor, mask: Optional[torch.Tensor], crop_s
         v = int(virtual_coils)
         if v < 1 or v > c:
             raise ValueError(f"virtual_coils must be in 1..{c} (the coil count of this scan)")
-        a = _coil_matrix_jacobi(coil_gram(x, n, cc_region)[None], v)[0][0]   # (V, c, 2); refuses more than 64 coils / 32 virtual coils
+        a = _coil_matrix_jacobi(coil_gram(x, n, cc_region)[None], v, whitener=whitener)[0][0]      # (V, c, 2); refuses more than 64 coils / 32 virtual coils
         x = torch.view_as_real(compress_coils(x, torch.view_as_complex(a), n))
         c = v
     if ops.fft_line_supported(nx) and ops.fft_line_supported(ny):
@@ -515,7 +668,8 @@ def ecalib(time_avg_kspace, *, r: int, method: str = "eigh"):
 
 def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(200, 200), crop_target=(180, 180), n_slices: int = 15,
                     filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, ecalib_r: int = 200, virtual_coils: Optional[int] = None,
-                    coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, espirit_method: str = "eigh", cc_method: str = "eigh"):
+                    coil_matrix: Optional[torch.Tensor] = None, cc_region: int = 24, espirit_method: str = "eigh", cc_method: str = "eigh",
+                    whitener: Optional[torch.Tensor] = None):
     """``SliceDataset.__getitem__`` of the reference (data/mri_data.py:267-311) in one piece, on the device: scale -> IFFT2 -> crop +
     frame selection + Gaussian filter -> FFT2 (k-space of the filtered crop) -> sensitivity maps from the time-averaged k-space
     (ESPIRiT, where the reference shells out to ``bart ecalib -r 200``; pass ``sens`` (coil, X, Y) complex to use given maps) ->
@@ -525,7 +679,7 @@ def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(2
     as numpy arrays, like the reference (the ``*DataTransform`` classes take it from there, data/transforms.py:300-352).
     ``virtual_coils`` / ``coil_matrix`` / ``cc_region``: as in prepare_slice; k-space, the calibration and ``sens`` are then on the V
     virtual coils, so raw data with more than 32 coils calibrates whenever V <= 32.  ``espirit_method``: ``espirit_maps``' ``method``;
-    ``cc_method``: ``coil_matrix_from_gram``'s."""
+    ``cc_method``: ``coil_matrix_from_gram``'s.  ``whitener``: as in prepare_slice (the calibration then sees white noise)."""
     import numpy as np
     if hasattr(source, "keys") and "y" in source:
         raw = np.asarray(source["y"])
@@ -536,7 +690,8 @@ def prepare_example(source, mask=None, sens=None, fname: str = "", crop_shape=(2
     if not torch.cuda.is_available():
         raise CineHipError("prepare_example: the front-end kernels need a GPU (no CPU fallback)")
     y = torch.as_tensor(raw).to(torch.complex64).cuda()
-    kspace, filt = prepare_slice(y, crop_shape, n_slices, filter_size, scaling, virtual_coils, coil_matrix, cc_region, cc_method)   # (t, c, X, Y, 2) each
+    kspace, filt = prepare_slice(y, crop_shape, n_slices, filter_size, scaling, virtual_coils, coil_matrix, cc_region, cc_method,
+                                 whitener)                                   # (t, c, X, Y, 2) each
     if sens is not None and (virtual_coils is not None or coil_matrix is not None) and tuple(sens.shape)[0] != kspace.shape[1]:
         raise ValueError(f"sens has {tuple(sens.shape)[0]} coils, the compressed data {kspace.shape[1]}")
     if sens is None:

@@ -87,6 +87,16 @@ memory with the outputs: ``results`` / ``drain`` raise ``CineHipError`` naming t
 exceeds the solver's own stopping bar 1e-14 (its sweep cap was hit, or the raw data hold a NaN), and file the record of every slice they
 hand out under ``pipe.last_coil_info[tag]`` (``CoilInfo(residual, sweeps, kept, lam0)``; the last ``COIL_INFO_KEPT`` slices).
 
+``submit_raw(..., whitener=W)``: noise pre-whitening with the scan's whitener W (coil, coil) complex128 from
+``frontend.noise_whitener`` -- numpy, pinned or device memory.  With ``virtual_coils=V`` W is copied with the raw data into a static buffer
+of the (slot, parity) and the slot's stream runs cine_coil_matrix_whitened where it ran cine_coil_matrix: the matrix is that of the
+whitened calibration block composed with W, ``compress_coils`` whitens and compresses in its one pass, and the result is bit for bit
+``model(prepare_masked_slice(raw, mask, ..., coil_matrix=A), mask)`` with ``A = coil_matrix_from_gram(coil_gram(raw, n_frames,
+cc_region), V, method="jacobi", whitener=W)[0]``.  The set key ends with ``("virtual", V, cc_region, "whitened")``; the coil count stays
+out of it, and ``last_coil_info`` and the residual check hold for the whitened Gram matrix.  ``whitener`` alone is
+``coil_matrix=W.to(torch.complex64)`` (at most 32 coils); together with ``coil_matrix=`` it raises.  ``sens_maps="espirit"`` then
+calibrates on the whitened virtual coils.
+
 ``graphs=False`` is the explicit eager mode: same slots, streams, buffers, copies and events, with the launch sequence
 enqueued on the slot's stream for every slice.  A failure raises ``CineHipError``; nothing falls back to eager launches.
 
@@ -340,25 +350,29 @@ CoilInfo = collections.namedtuple("CoilInfo", "residual sweeps kept lam0")
 
 
 def raw_set_key(raw_shape, n_frames, crop_shape, filter_size, scaling, apply_mask, mask_shape, sens_shape, coil_matrix_shape=None,
-                espirit=None, virtual_coils=None):
+                espirit=None, virtual_coils=None, whitened=False):
     """The key of the graph set that serves a ``submit_raw`` call, from shapes and settings alone: kind, kept raw shape, virtual coils,
     crop, filter, scaling, apply_mask, mask shape, sens shape.  With a coil matrix the raw coil count is NOT part of it: the compression
     runs in front of the graph, so scans with different coil counts and one V share a set.  ``espirit``: ``espirit_key(ecalib_r,
     sign_iters)`` for ``sens_maps="espirit"``; it takes the place of the sens shape.  ``virtual_coils``: ``(V, cc_region)`` for
     ``submit_raw(..., virtual_coils=V, cc_region=...)``; the key then ends with ``("virtual", V, cc_region)`` and, as with a coil matrix,
-    leaves the coil count out.  Without it the key is what it was."""
+    leaves the coil count out.  Without it the key is what it was.  ``whitened``: ``submit_raw(..., virtual_coils=V, whitener=W)``; the
+    marker then reads ``("virtual", V, cc_region, "whitened")`` (another launch sequence in front of the graph).  A whitener without
+    ``virtual_coils`` is a coil matrix: describe it by ``coil_matrix_shape``."""
     t, nx, ny, c = (int(v) for v in tuple(raw_shape)[:4])
     n = min(int(n_frames), t)
     if n < 1 or nx < 1 or ny < 1 or c < 1:
         raise ValueError("Invalid shapes.")
     if virtual_coils is not None and coil_matrix_shape is not None:
         raise ValueError("raw_set_key: virtual_coils or coil_matrix_shape, not both")
+    if whitened and virtual_coils is None:
+        raise ValueError("raw_set_key: whitened marks a virtual_coils set; a whitener alone is a coil matrix (coil_matrix_shape)")
     kept = (n, nx, ny, c) if coil_matrix_shape is None and virtual_coils is None else (n, nx, ny)
     v = None if coil_matrix_shape is None else int(tuple(coil_matrix_shape)[0])
     tail = ()
     if virtual_coils is not None:
         v, region = (int(q) for q in virtual_coils)
-        tail = (("virtual", v, region),)
+        tail = (("virtual", v, region) + (("whitened",) if whitened else ()),)
     return ("raw", kept, v, (int(crop_shape[0]), int(crop_shape[1])), tuple(float(f) for f in filter_size), float(scaling),
             bool(apply_mask), tuple(int(m) for m in mask_shape),
             tuple(espirit) if espirit is not None else None if sens_shape is None else tuple(int(m) for m in sens_shape)) + tail
@@ -367,10 +381,10 @@ def raw_set_key(raw_shape, n_frames, crop_shape, filter_size, scaling, apply_mas
 class _RawSource:
     """One raw slice's validated inputs (``submit_raw``): the kept frames of the raw data in their original place, mask, sens, the coil
     matrix, the front-end's settings, the set key."""
-    input_names = ("raw", "mask", "sens", "cmat")
+    input_names = ("raw", "mask", "sens", "cmat", "wh")
 
     def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask, ecalib_r=15,
-                 sign_iters=60, virtual_coils=None, cc_region=24):
+                 sign_iters=60, virtual_coils=None, cc_region=24, whitener=None):
         if not isinstance(raw, (np.ndarray, torch.Tensor)):
             raise CineHipError(f"raw: expected a torch tensor or a numpy array, got {type(raw).__name__}")
         if raw.ndim < 4 or raw.shape[0] < 1 or int(n_frames) < 1:
@@ -390,6 +404,19 @@ class _RawSource:
         self.scaling, self.apply_mask = float(scaling), bool(apply_mask)
         self.cmat, self.cmat_kind = None, None
         self.vc, self.cc_region = None, None                                 # virtual_coils=: the matrix is computed in flight
+        self.wh, self.wh_kind = None, None                                   # whitener= with virtual_coils=: W (c, c, 2) float64 pairs
+        if whitener is not None:
+            if coil_matrix is not None:
+                raise CineHipError("whitener and coil_matrix: a given matrix is applied as it is; fold the whitener into it, "
+                                   "frontend.coil_matrix_from_gram(..., whitener=W), and pass that matrix alone")
+            w, kind = _whitener_pairs(whitener, c)
+            if virtual_coils is None:                                        # the whitener alone: a (c, c) coil matrix
+                if c > _CC_MAX_VIRTUAL:
+                    raise CineHipError(f"whitener alone keeps all {c} channels, the compression writes at most {_CC_MAX_VIRTUAL}: pass "
+                                       "virtual_coils= as well (the whitener is then folded into every slice's matrix)")
+                coil_matrix = torch.view_as_complex(w).to(torch.complex64)
+            else:
+                self.wh, self.wh_kind = w, kind
         if virtual_coils is not None:
             if coil_matrix is not None:
                 raise CineHipError("virtual_coils computes every slice's own matrix, coil_matrix brings one: pass one of the two")
@@ -421,12 +448,13 @@ class _RawSource:
         self.espirit = None
         if isinstance(self.sens, str):                                       # calibrated in flight, on the V virtual coils with a coil matrix
             self.sens, self.espirit = None, espirit_key(ecalib_r, sign_iters)
-        _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat)))
+        _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat),
+                            ("whitener", self.wh)))
         self.raw_nbytes = x.numel() * 4
         self.gram_nbytes = 0                                                 # asked of the library when a buffer is needed (_submit, alloc)
         self.key = raw_set_key((n, nx, ny, c), n, self.crop, self.filter, self.scaling, self.apply_mask, self.mask_shape,
                                None if self.sens is None else self.sens.shape, None if self.cmat is None else self.cmat.shape, self.espirit,
-                               None if self.vc is None else (self.vc, self.cc_region))
+                               None if self.vc is None else (self.vc, self.cc_region), self.wh is not None)
 
     def gram_bytes(self) -> int:
         """Workspace of this slice's coil_gram (virtual_coils=), 0 otherwise."""
@@ -438,7 +466,8 @@ class _RawSource:
     def alloc(self, pipe):
         """raw: a byte buffer (with a coil matrix it may be replaced by a larger one later: no graph holds its address).  cc: what the
         eager compression writes and the graph reads.  mk: written and read inside the graph.  virtual_coils=: gram, lam and cinfo for
-        the largest coil count cine_coil_matrix takes, gws (coil_gram's workspace) replaced by a larger one like raw."""
+        the largest coil count cine_coil_matrix takes, gws (coil_gram's workspace) replaced by a larger one like raw; wh, the copied
+        whitener, for that coil count too."""
         dev = pipe.device
         n, nx, ny = self.raw.shape[:3]
         b = {"raw": torch.empty(self.raw_nbytes, device=dev, dtype=torch.uint8),
@@ -448,6 +477,7 @@ class _RawSource:
              "mask": torch.empty(self.mask_shape, device=dev, dtype=torch.uint8),
              "sens": None if self.sens is None else torch.empty(self.sens.shape, device=dev, dtype=torch.float32)}
         b["front"] = b["cc"] if self.v is not None else self.raw_view(b)
+        b["wh"] = None if self.wh is None else torch.empty(_CM_MAX_COILS * _CM_MAX_COILS, device=dev, dtype=torch.complex128)
         if self.vc is not None:
             b["gram"] = torch.empty(_CM_MAX_COILS * _CM_MAX_COILS, device=dev, dtype=torch.complex128)
             b["lam"] = torch.empty(_CM_MAX_COILS, device=dev, dtype=torch.float64)
@@ -463,13 +493,37 @@ class _RawSource:
         v, c, _ = self.cmat_shape
         return b["cmat"][:v * c * 8].view(torch.float32).view(self.cmat_shape)
 
+    def wh_view(self, b):
+        c = self.c
+        return b["wh"][:c * c].view(c, c)
+
     def items(self, b):
         it = [("raw", self.raw_view(b), self.raw, self.raw_kind), ("mask", b["mask"], self.mask, self.mask_kind)]
         if self.sens is not None:
             it.append(("sens", b["sens"], self.sens, self.sens_kind))
         if self.cmat is not None:
             it.append(("cmat", self.cmat_view(b), self.cmat, self.cmat_kind))
+        if self.wh is not None:
+            it.append(("wh", torch.view_as_real(self.wh_view(b)), self.wh, self.wh_kind))
         return it
+
+
+def _whitener_pairs(whitener, c: int):
+    """A whitener (c, c) complex128 -- torch tensor or numpy array, device, pinned or pageable -- as float64 (c, c, 2) pairs, and its kind."""
+    if isinstance(whitener, np.ndarray):
+        if whitener.dtype != np.complex128:
+            raise CineHipError(f"whitener: numpy dtype {whitener.dtype}; expected complex128 (frontend.noise_whitener)")
+        whitener = torch.from_numpy(np.ascontiguousarray(whitener))
+    elif not isinstance(whitener, torch.Tensor):
+        raise CineHipError(f"whitener: expected a torch tensor or a numpy array, got {type(whitener).__name__}")
+    if whitener.dtype != torch.complex128:
+        raise CineHipError(f"whitener: dtype {whitener.dtype}; expected complex128 (frontend.noise_whitener)")
+    if tuple(whitener.shape) != (c, c):
+        raise CineHipError(f"whitener: shape {tuple(whitener.shape)}; expected ({c}, {c}) for this scan's {c} coils")
+    w = torch.view_as_real(whitener if whitener.is_contiguous() else whitener.contiguous())
+    if w.is_cuda:
+        return w, "device"
+    return w, ("pinned" if w.is_pinned() else "pageable")
 
 
 def _settings_only(src: "_RawSource"):
@@ -493,7 +547,7 @@ class _Set:
 
     def __init__(self, key):
         self.key = key
-        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front" in a raw set; "gram", "gws", "lam", "cinfo" with virtual_coils=)
+        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front", "wh" in a raw set; "gram", "gws", "lam", "cinfo" with virtual_coils=)
         self.raw = None         # the front-end's settings when the graphs start from raw data (the _RawSource that built the set)
         self.raw_bytes = 0      # capacity of each raw byte buffer
         self.gram_bytes = 0     # capacity of each Gram workspace (virtual_coils=)
@@ -555,7 +609,8 @@ class SlicePipeline:
 
     def submit_raw(self, raw, mask, sens_maps=None, tag=None, *, crop_shape=(200, 200), n_frames: int = 15,
                    filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True,
-                   ecalib_r: int = 15, sign_iters: int = 60, virtual_coils: Optional[int] = None, cc_region: int = 24) -> SliceHandle:
+                   ecalib_r: int = 15, sign_iters: int = 60, virtual_coils: Optional[int] = None, cc_region: int = 24,
+                   whitener=None) -> SliceHandle:
         """Enqueue one slice from its RAW k-space (t, x, y, coil) -- complex64 or float32 pairs, in any of the four places ``submit`` takes
         its input from.  Only ``raw[:min(n_frames, t)]`` is copied to the device.  ``frontend.prepare_masked_slice`` and the model run on
         the slot's stream inside the slot's graph; see the module docstring.  ``mask``: the mask on the crop grid, a row mask or one that varies along w under the
@@ -564,11 +619,14 @@ class SlicePipeline:
         graph, behind the front-end, from the masked k-space it wrote (``ecalib_r``, ``sign_iters`` as in ``submit``).
         ``virtual_coils=V`` (with ``cc_region``, and without ``coil_matrix``): the slice is compressed to V virtual coils with the matrix
         of its own kept frames, computed on the slot's stream (at most 64 coils, V <= 32; see the module docstring).  The kept share of
-        the slice is ``pipe.last_coil_info[tag].kept`` once ``results`` / ``drain`` have handed it out; ``tag`` must then be hashable."""
+        the slice is ``pipe.last_coil_info[tag].kept`` once ``results`` / ``drain`` have handed it out; ``tag`` must then be hashable.
+        ``whitener=W`` (coil, coil) complex128 from ``frontend.noise_whitener`` on the scan's noise samples, from numpy, pinned or device
+        memory: noise pre-whitening.  With ``virtual_coils=V`` it is folded into every slice's matrix on the slot's stream
+        (cine_coil_matrix_whitened); alone it is ``coil_matrix=W.to(torch.complex64)``; with ``coil_matrix`` it raises."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit_raw after close()")
         src = _RawSource(self, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask,
-                         ecalib_r, sign_iters, virtual_coils, cc_region)
+                         ecalib_r, sign_iters, virtual_coils, cc_region, whitener)
         if src.vc is not None:
             try:
                 hash(tag)
@@ -694,13 +752,14 @@ class SlicePipeline:
     def _pre(self, b, src) -> None:
         """What runs eagerly on the slot's stream in front of the graph: with a coil matrix, the compression of this scan's raw data
         (any coil count) into the static (T, x, y, V) buffer the graph starts from; with virtual_coils= the Gram matrix and the
-        matrix of this slice in front of it."""
+        matrix of this slice in front of it (with whitener= the whitened matrix, from the copied whitener)."""
         if src.raw is not None and src.v is not None:
             with torch.no_grad():
                 if src.vc is not None:                       # this slice's own matrix, where coil_matrix= has the copied one
                     c = src.c
                     g = frontend.coil_gram(src.raw_view(b), src.n, src.cc_region, out=b["gram"][:c * c].view(c, c), ws=b["gws"])
-                    frontend._coil_matrix_jacobi(g[None], src.vc, src.cmat_view(b)[None], b["lam"][:c][None], b["cinfo"])
+                    frontend._coil_matrix_jacobi(g[None], src.vc, src.cmat_view(b)[None], b["lam"][:c][None], b["cinfo"],
+                                                 whitener=None if src.wh is None else src.wh_view(b))
                 frontend.compress_coils(src.raw_view(b), torch.view_as_complex(src.cmat_view(b)), src.n, out=b["cc"])
 
     def _body(self, b):

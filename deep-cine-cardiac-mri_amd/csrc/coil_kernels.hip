@@ -19,6 +19,12 @@
 //                        Jacobi eigensolver of the singular-value-thresholding kernels (ls_jacobi in ls_jacobi.h, unchanged).  Only the
 //                        upper triangle of G is read (mirrored, the diagonal's imaginary part dropped): Hermitian by construction, so
 //                        no check on the host.  No host read, no atomics: capturable, repeated calls are bit-identical.
+//   cine_coil_matrix_whitened
+//                        noise pre-whitening folded into that matrix: with the lower-triangular whitener W = s L^-1 of the noise
+//                        covariance Psi = L L^H (one per scan, computed by the caller) the same kernel decomposes G' = W G W^H =
+//                        U diag(lam) U^H and writes A = U^H W, phased like the rows above: A Psi A^H = s^2 I, A G A^H = diag(lam).
+//                        Three more c^3 float64 products in the same LDS, W read from global memory (its lower triangle only);
+//                        cine_coil_compress then whitens and compresses in its one pass over the samples.
 #include <cstdint>
 #include <mutex>
 #include "common.h"
@@ -262,6 +268,7 @@ __global__ __launch_bounds__(cc::kThreads) void coil_compress_kernel(const float
 // ------------------------------------------------------------------ compression matrix from the Gram matrix
 struct CoilMatrixArgs {
     const double2* gram;
+    const double2* whitener;                   // coil_matrix_kernel<true> only
     float2* matrix;
     double* lam;
     double* info;
@@ -277,8 +284,21 @@ __device__ __forceinline__ bool cm_before(double a, int ia, double b, int ib) {
     return ia < ib;
 }
 
+// entry [i][k], k <= i, of the lower-triangular whitener: the diagonal's imaginary part is taken as 0
+__device__ __forceinline__ double2 cm_whitener(const double2* __restrict__ W, int T, int i, int k) {
+    double2 w = W[i * T + k];
+    if (i == k) w.y = 0.0;
+    return w;
+}
+
 // LDS (dynamic): A [c][c] | U [c][c] double2, rot [kLsRotDoubles], red [kLsRedDoubles] doubles.  After ls_jacobi red is reused:
 // [c] eigenvalues in rank order, then [c] ints, the column of every rank.
+// kWhiten: the eigen-decomposition is that of G' = W G W^H, W the lower-triangular whitener (read from global memory: c x c doubles
+// shared by every workgroup stay in L2), within the same two slots: B = W G into U, G' = B W^H back into A (the upper triangle,
+// mirrored: exactly Hermitian with a real diagonal), then U = W^H in place of the identity.  ls_jacobi multiplies U by its rotations
+// from the right, so U ends as W^H U' and the extraction below writes conj((W^H U')[:, r]) = the rows of U'^H W.  With W = I every
+// product is one with 1 or 0 and every sum one with 0: the bits of the plain kernel.
+template <bool kWhiten>
 __global__ __launch_bounds__(kLsThreads) void coil_matrix_kernel(CoilMatrixArgs a) {
     extern __shared__ __align__(16) unsigned char cm_lds[];
     const int T = a.c, nv = a.v, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -293,9 +313,54 @@ __global__ __launch_bounds__(kLsThreads) void coil_matrix_kernel(CoilMatrixArgs 
         double2 g = i <= j ? G[e] : G[j * T + i];             // the upper triangle only
         g.y = i < j ? g.y : (i == j ? 0.0 : -g.y);
         A[e] = g;
-        U[e] = make_double2(i == j ? 1.0 : 0.0, 0.0);
+        if constexpr (!kWhiten) U[e] = make_double2(i == j ? 1.0 : 0.0, 0.0);
     }
     __syncthreads();
+    if constexpr (kWhiten) {
+        const double2* __restrict__ W = a.whitener;
+        for (int e = tid; e < T * T; e += kLsThreads) {        // B[i][j] = sum_{k <= i} W[i][k] G[k][j]
+            const int i = e / T, j = e - i * T;
+            double re = 0.0, im = 0.0;
+            for (int k = 0; k <= i; ++k) {
+                const double2 w = cm_whitener(W, T, i, k), g = A[k * T + j];
+                re = fma(w.x, g.x, re);
+                re = fma(-w.y, g.y, re);
+                im = fma(w.x, g.y, im);
+                im = fma(w.y, g.x, im);
+            }
+            U[e] = make_double2(re, im);
+        }
+        __syncthreads();
+        for (int e = tid; e < T * T; e += kLsThreads) {        // G'[i][j] = sum_{k <= j} B[i][k] conj(W[j][k]), i <= j, and its mirror
+            const int i = e / T, j = e - i * T;
+            if (i > j) continue;
+            double re = 0.0, im = 0.0;
+            for (int k = 0; k <= j; ++k) {
+                const double2 b = U[i * T + k], w = cm_whitener(W, T, j, k);
+                re = fma(b.x, w.x, re);
+                re = fma(b.y, w.y, re);
+                im = fma(b.y, w.x, im);
+                im = fma(-b.x, w.y, im);
+            }
+            if (i == j) {
+                A[e] = make_double2(re, 0.0);
+            } else {
+                A[e] = make_double2(re, im);
+                A[j * T + i] = make_double2(re, -im);
+            }
+        }
+        __syncthreads();                                       // every thread is done with B
+        for (int e = tid; e < T * T; e += kLsThreads) {        // U = W^H
+            const int i = e / T, j = e - i * T;
+            double2 u = make_double2(0.0, 0.0);
+            if (i <= j) {
+                const double2 w = cm_whitener(W, T, j, i);
+                u = make_double2(w.x, 0.0 - w.y);
+            }
+            U[e] = u;
+        }
+        __syncthreads();
+    }
     double off, diag;
     const int sweeps = ls_jacobi(A, U, rot, red, T, tid, off, diag);     // ends behind a barrier: rot and red are free
     double* lams = red;
@@ -463,30 +528,51 @@ extern "C" int cine_coil_compress(const float* raw, const float* matrix, float* 
     return v <= 16 ? launch_compress<1, 16>(r, m, o, g, st) : launch_compress<2, 16>(r, m, o, g, st);
 }
 
-extern "C" int cine_coil_matrix(const double* gram, float* matrix, double* lam, double* info, int nb, int c, int v, void* stream) {
-    const char* what = "cine_coil_matrix";
-    CINE_REQUIRE(gram && matrix && lam && info, CINE_EINVAL, "%s: null pointer", what);
+namespace {
+
+// cine_coil_matrix (whitener == nullptr, whitened == false) and cine_coil_matrix_whitened: every check, then the one launch
+int coil_matrix_run(const char* what, bool whitened, const double* gram, const double* whitener, float* matrix, double* lam, double* info,
+                    int nb, int c, int v, void* stream) {
+    CINE_REQUIRE(gram && matrix && lam && info && (whitener || !whitened), CINE_EINVAL, "%s: null pointer", what);
     {
-        const void* g = gram; const void* m = matrix; const void* l = lam; const void* f = info;
+        const void* g = gram; const void* m = matrix; const void* l = lam; const void* f = info; const void* w = whitener;
         CINE_REQUIRE(g != m && g != l && g != f && m != l && m != f && l != f, CINE_EINVAL, "%s: aliased pointers", what);
+        CINE_REQUIRE(!whitened || (w != g && w != m && w != l && w != f), CINE_EINVAL, "%s: aliased pointers", what);
     }
     CINE_REQUIRE(nb >= 1 && c >= 1 && v >= 1 && v <= c, CINE_EINVAL, "%s: Invalid shapes. (matrices %d, coils %d, virtual coils %d)", what, nb, c, v);
     CINE_REQUIRE(c <= kLsMaxT, CINE_EUNSUPPORTED, "%s: %d coils, at most %d", what, c, kLsMaxT);
     CINE_REQUIRE(v <= cc::kMaxVirtual, CINE_EUNSUPPORTED, "%s: %d virtual coils, at most %d", what, v, cc::kMaxVirtual);
-    CINE_REQUIRE(aligned16(gram) && (reinterpret_cast<uintptr_t>(matrix) & 7u) == 0 && (reinterpret_cast<uintptr_t>(lam) & 7u) == 0 &&
-                     (reinterpret_cast<uintptr_t>(info) & 7u) == 0,
-                 CINE_EINVAL, "%s: gram must be 16-byte aligned, matrix, lam and info 8-byte aligned", what);
+    const bool outs8 = (reinterpret_cast<uintptr_t>(matrix) & 7u) == 0 && (reinterpret_cast<uintptr_t>(lam) & 7u) == 0 &&
+                       (reinterpret_cast<uintptr_t>(info) & 7u) == 0;
+    if (whitened)
+        CINE_REQUIRE(aligned16(gram) && aligned16(whitener) && outs8, CINE_EINVAL,
+                     "%s: gram and whitener must be 16-byte aligned, matrix, lam and info 8-byte aligned", what);
+    else
+        CINE_REQUIRE(aligned16(gram) && outs8, CINE_EINVAL, "%s: gram must be 16-byte aligned, matrix, lam and info 8-byte aligned", what);
     const size_t lds = (size_t)2 * c * c * sizeof(double2) + (size_t)(kLsRotDoubles + kLsRedDoubles) * sizeof(double);
+    auto kern = whitened ? coil_matrix_kernel<true> : coil_matrix_kernel<false>;
     if (lds >= 64 * 1024) {
-        static std::once_flag once[64];
-        static hipError_t status[64];
-        if (int e = ls_large_lds(reinterpret_cast<const void*>(coil_matrix_kernel), "coil_matrix_kernel", once, status)) return e;
+        static std::once_flag once[2][64];
+        static hipError_t status[2][64];
+        if (int e = ls_large_lds(reinterpret_cast<const void*>(kern), "coil_matrix_kernel", once[whitened], status[whitened])) return e;
     }
     CoilMatrixArgs a{};
-    a.gram = reinterpret_cast<const double2*>(gram); a.matrix = reinterpret_cast<float2*>(matrix); a.lam = lam; a.info = info;
+    a.gram = reinterpret_cast<const double2*>(gram); a.whitener = reinterpret_cast<const double2*>(whitener);
+    a.matrix = reinterpret_cast<float2*>(matrix); a.lam = lam; a.info = info;
     a.c = c; a.v = v;
     hipStream_t st = as_stream(stream);
     ProfScope prof(F_MISC, st);
-    hipLaunchKernelGGL(coil_matrix_kernel, dim3((unsigned)nb), dim3(kLsThreads), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(kLsThreads), lds, st, a);
     return check_launch("coil_matrix_kernel");
+}
+
+}  // namespace
+
+extern "C" int cine_coil_matrix(const double* gram, float* matrix, double* lam, double* info, int nb, int c, int v, void* stream) {
+    return coil_matrix_run("cine_coil_matrix", false, gram, nullptr, matrix, lam, info, nb, c, v, stream);
+}
+
+extern "C" int cine_coil_matrix_whitened(const double* gram, const double* whitener, float* matrix, double* lam, double* info,
+                                         int nb, int c, int v, void* stream) {
+    return coil_matrix_run("cine_coil_matrix_whitened", true, gram, whitener, matrix, lam, info, nb, c, v, stream);
 }

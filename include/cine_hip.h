@@ -599,6 +599,23 @@ int cine_coil_compress(const float* raw, const float* matrix, float* out, int t_
  * CINE_EUNSUPPORTED, the limit is in the message).  Every argument is checked before the launch; no allocation, no host read, no
  * atomics: capturable, and the same bits on every call. */
 int cine_coil_matrix(const double* gram, float* matrix, double* lam, double* info, int nb, int c, int v, void* stream);
+/* Noise pre-whitening folded into the compression matrix.  Noise samples eta_s (c channels, s < n) have the covariance
+ * Psi[i][j] = 1/n sum_s eta_s[i] conj(eta_s[j]) (the index convention of cine_coil_gram) = L L^H, L lower-triangular with a real positive
+ * diagonal; the whitener is W = s L^-1 (s = sqrt(trace(Psi) / c) keeps the data's overall level, or s = 1), so W Psi W^H = s^2 I.  A
+ * whitened sample is d' = W d and its calibration Gram matrix G' = W G W^H.  cine_coil_matrix_whitened is cine_coil_matrix of G' composed
+ * with W: with G' = U diag(lam) U^H (lam descending, equal values by column index),
+ *     matrix[r][:] = p_r sum_k conj(U[k][r]) W[k][:],  r < v,
+ * p_r the unit phase that makes the row's largest-magnitude entry real and positive (float64 magnitudes, the lowest index among equal
+ * ones; stored with imaginary part 0; every entry rounded once to complex64).  matrix Psi matrix^H = s^2 I_v and matrix G matrix^H =
+ * diag(lam[:v]); the rows are not orthonormal.  cine_coil_compress with this matrix whitens and compresses in its one pass.
+ * gram (nb, c, c) complex128 as cine_coil_gram writes it (the upper triangle is read); whitener (c, c) complex128 row-major, shared by
+ * all nb matrices (one scan, many slices): only its lower triangle with the diagonal is read, the diagonal's imaginary part is taken as
+ * 0.  Outputs, info, limits and checks as cine_coil_matrix, info for G'; whitener non-null, 16-byte aligned, aliasing nothing.  The same
+ * kernel: B = W G, G' = B W^H (one triangle, mirrored: exactly Hermitian with a real diagonal) and the eigenvector accumulator started
+ * at W^H instead of the identity, all within the two c x c float64 matrices in LDS; the identity as whitener gives the bits of
+ * cine_coil_matrix.  No allocation, no host read, no atomics: capturable, and the same bits on every call. */
+int cine_coil_matrix_whitened(const double* gram, const double* whitener, float* matrix, double* lam, double* info,
+                              int nb, int c, int v, void* stream);
 /* One axis pass of scipy.ndimage.gaussian_filter as transforms.py:216-217 calls it (mode 'reflect', truncate 4.0, weights and
  * accumulation in float64, float32 result) over a (outer, n, inner) array of complex pairs: the real and imaginary parts
  * are filtered alike.  The caller runs one pass per axis with sigma > 0, in axis order (mri_data.py:279: [0.7, 0, 0.3, 0.3]). */

@@ -29,7 +29,15 @@ spectrum, every slice its own): ``submit_raw(..., virtual_coils=V)`` ("in flight
 device, ``frontend.coil_compression_matrix`` (torch.linalg.eigh behind a host check), ``submit_raw(..., coil_matrix=A)`` -- and, as the
 ceiling, ``coil_matrix=`` with one matrix per scan computed beforehand.  Medians of --repeats regions, warm-up outside the clock; the
 spread of a line is max - min of its regions.  Also cine_coil_matrix alone (hipEvent, median of 20) at 15, 30 and 64 coils, and the
-Jacobi sweeps every slice took."""
+Jacobi sweeps every slice took.
+
+    python tools/pipeline_rate.py --raw --virtual-coils 15 --whiten [--out profiles/noise_whitening_rate.json]
+
+Noise pre-whitening folded into the per-slice matrix, in ONE session: ``submit_raw(pinned, virtual_coils=V)`` with and without
+``whitener=W`` (W from ``frontend.noise_whitener`` on a synthetic noise scan with a designed covariance of condition number 100) on the
+two scans above, interleaved region by region, medians of --repeats regions; and cine_coil_matrix_whitened beside cine_coil_matrix alone
+(hipEvent, median of 20) at 15, 30 and 64 coils.  What to hold the result against: the whitened kernel adds three c^3 float64 products
+to a Jacobi solve of 8-11 sweeps, and the pass over the data is unchanged."""
 import argparse
 import json
 import os
@@ -357,6 +365,117 @@ def virtual_coils_main(args):
     print(json.dumps({k: v for k, v in doc.items() if k != "scans"}), flush=True)
 
 
+def _noise_scan(c, seed, dev, n=16384):
+    """Noise samples (n, c) complex64 on the device with the covariance Q diag(1e-12 100^(-k / (c - 1))) Q^H: unequal, correlated channels at
+    the amplitude of the raw data above."""
+    rs = np.random.RandomState(1000 + seed)
+    q, _ = np.linalg.qr(rs.standard_normal((c, c)) + 1j * rs.standard_normal((c, c)))
+    d = 1e-12 * 100.0 ** (-np.arange(c) / max(c - 1, 1))
+    low = np.linalg.cholesky((q * d) @ q.conj().T)
+    g = torch.Generator(device=dev).manual_seed(seed)
+    z = torch.view_as_complex(torch.randn((n, c, 2), generator=g, device=dev, dtype=torch.float32)) * (0.5 ** 0.5)
+    return z @ torch.from_numpy(low.T.astype(np.complex64)).to(dev)
+
+
+def whitened_main(args):
+    import bench
+    from cine_hip import frontend as FE, synth
+    from cine_hip.pipeline import SlicePipeline
+    cfg = bench.CONFIGS[2]()
+    dev = torch.device("cuda:0")
+    V, S, n, warm, reps = args.virtual_coils, args.slots, args.slices or 40, args.warmup if args.warmup is not None else 8, args.repeats
+    net = cfg["hip"]().eval()
+    synth.fill_parameters_(net, cfg["wseed"], keep=cfg["keep"])
+    net = net.to(dev)
+    commit, csrc = _stamp(args.commit)
+    doc = {"metric": "cine slices/sec from raw k-space with per-slice coil compression, with and without noise pre-whitening "
+                     "(SlicePipeline.submit_raw)", "config": 2, "name": cfg["name"], "virtual_coils": V, "cc_region": 24, "slots": S,
+           "slices_per_region": n, "warmup_slices": warm, "regions": reps,
+           "statistic": "median of the regions, the two lines interleaved region by region; spread = max - min of the regions",
+           "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "device": torch.cuda.get_device_name(dev), "commit": commit,
+           "csrc_sha256": csrc, "lines": {"plain": "submit_raw(pinned, virtual_coils=V)",
+                                          "whitened": "submit_raw(pinned, virtual_coils=V, whitener=W), W on the device"},
+           "coil_matrix_kernel": [], "scans": []}
+
+    for c in (15, 30, 64):                                       # the two kernels alone, on the Gram matrix of a designed input
+        g = FE.coil_gram(_designed((2, 24, 24, c), 9, dev).to(dev), 2, 24)[None].contiguous()
+        w = FE.noise_whitener(_noise_scan(c, 9, dev))
+        v = min(V, c)
+        outs, outs_w = FE._coil_matrix_jacobi(g, v), FE._coil_matrix_jacobi(g, v, whitener=w)
+        ms = _event_ms(lambda: FE._coil_matrix_jacobi(g, v, *outs), 20)
+        ms_w = _event_ms(lambda: FE._coil_matrix_jacobi(g, v, *outs_w, whitener=w), 20)
+        info, info_w = outs[2][0].tolist(), outs_w[2][0].tolist()
+        doc["coil_matrix_kernel"].append({"coils": c, "virtual_coils": v, "launches": len(ms),
+                                          "plain_median_ms": _median(ms), "plain_min_ms": min(ms), "plain_sweeps": int(info[1]),
+                                          "whitened_median_ms": _median(ms_w), "whitened_min_ms": min(ms_w), "whitened_sweeps": int(info_w[1]),
+                                          "whitened_residual": info_w[0], "whitened_over_plain": _median(ms_w) / _median(ms)})
+    print(json.dumps(doc["coil_matrix_kernel"]), flush=True)
+
+    n_raws = 4
+    for name, shape in (("line_384x144x30", (FRAMES, 384, 144, 30)), ("window_416x208x30", (FRAMES, 416, 208, 30))):
+        t, nx, ny, c = shape
+        crop = (min(200, nx), min(200, ny))
+        rng = np.random.default_rng(nx + c)
+        pinned = [_designed(shape, 100 + nx + j, dev).pin_memory() for j in range(n_raws)]
+        dmasks = []
+        for j in range(n_raws):
+            m = (rng.uniform(size=(1, FRAMES, 1, crop[0], 1, 1)) < 0.25).astype(np.uint8)
+            m[:, :, :, crop[0] // 2 - 8 - j:crop[0] // 2 + 8 + j] = 1
+            dmasks.append(torch.from_numpy(m).to(dev))
+        w = FE.noise_whitener(_noise_scan(c, nx, dev))
+        kw = dict(crop_shape=crop, n_frames=FRAMES, filter_size=FILTER, scaling=SCALING)
+        row = {"scan": name, "raw_shape": list(shape), "crop": list(crop), "frames": FRAMES, "h2d_bytes_per_slice": pinned[0].numel() * 8}
+        extra = {"plain": {}, "whitened": {"whitener": w}}
+
+        def run(line, pipe, count):
+            got = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(count):
+                pipe.submit_raw(pinned[k % n_raws], dmasks[k % n_raws], virtual_coils=V, **extra[line], **kw)
+                for _ in pipe.results():
+                    got += 1
+            for _ in pipe.drain():
+                got += 1
+            torch.cuda.synchronize()
+            assert got == count
+            return count / (time.perf_counter() - t0)
+
+        with torch.no_grad():
+            a0 = FE.coil_matrix_from_gram(FE.coil_gram(pinned[0].to(dev), FRAMES, 24), V, method="jacobi", whitener=w)[0]
+            want = net(FE.prepare_masked_slice(pinned[0].to(dev), dmasks[0], crop, FRAMES, FILTER, SCALING, coil_matrix=a0), dmasks[0]).cpu()
+        pipes = {line: SlicePipeline(net, slots=S) for line in extra}        # one set each, alive side by side
+        try:
+            pipes["whitened"].submit_raw(pinned[0], dmasks[0], virtual_coils=V, whitener=w, **kw)
+            (_, o0), = list(pipes["whitened"].drain())
+            row["bit_identical_to_sequential"] = bool(torch.equal(o0.cpu(), want))
+            rs = {line: [] for line in extra}
+            for line in extra:
+                run(line, pipes[line], warm)
+            for _ in range(reps):
+                for line in extra:
+                    rs[line].append(run(line, pipes[line], n))
+            for line in extra:
+                assert pipes[line].set_builds == 1
+                row[f"value_{line}"], row[f"regions_{line}"], row[f"spread_{line}"] = _median(rs[line]), rs[line], max(rs[line]) - min(rs[line])
+                recs = list(pipes[line].last_coil_info.values())
+                row[f"sweeps_{line}"] = [min(r.sweeps for r in recs), max(r.sweeps for r in recs)]
+                row[f"residual_max_{line}"] = max(r.residual for r in recs)
+        finally:
+            for pipe in pipes.values():
+                pipe.close()
+        row["whitened_over_plain"] = row["value_whitened"] / row["value_plain"]
+        doc["scans"].append(row)
+        print(json.dumps(row), flush=True)
+        del pinned, dmasks, pipes
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+    print(json.dumps({k: v for k, v in doc.items() if k != "scans"}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5))
@@ -371,9 +490,16 @@ def main():
     ap.add_argument("--commit", default=None, help="--raw: the commit to stamp the result with (default: git rev-parse HEAD)")
     ap.add_argument("--virtual-coils", type=int, default=None, help="--raw: per-slice coil compression to this many virtual coils, in flight "
                     "beside today's way and the coil_matrix= ceiling (see the module docstring)")
+    ap.add_argument("--whiten", action="store_true", help="--raw --virtual-coils V: the in-flight rate with and without noise pre-whitening "
+                    "(whitener=W) in one session, and the two matrix kernels alone (see the module docstring)")
     args = ap.parse_args()
     if args.virtual_coils is not None and not args.raw:
         ap.error("--virtual-coils goes with --raw")
+    if args.whiten and args.virtual_coils is None:
+        ap.error("--whiten goes with --raw --virtual-coils V")
+    if args.raw and args.whiten:
+        args.out = args.out or os.path.join(ROOT, "profiles", "noise_whitening_rate.json")
+        return whitened_main(args)
     if args.raw:
         return virtual_coils_main(args) if args.virtual_coils is not None else raw_main(args)
     args.slices = 300 if args.slices is None else args.slices
