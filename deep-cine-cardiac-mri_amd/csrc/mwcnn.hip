@@ -54,24 +54,28 @@ Feat alloc(Bump& b, int n, int c, int h, int w) {
 
 void build(Plan& p, Bump& b, int n, int h, int w) {
     p.first_feat = alloc(b, n, p.first, h, w);
-    size_t big = 0, bigc = 0; int bigh = 0, bigw = 0;
+    // the scratch buffers hold any conv output of the pass: the largest feature map, and the most statistics records -- which depend on the
+    // tiling the dispatcher picks for (co, hs, ws), so they are taken from the plan, conv by conv, not from one scale
+    size_t big = 0, bigp = 1;
     for (int s = 0; s < p.S; ++s) {
         const int hs = h >> (s + 1), ws = w >> (s + 1);
         p.skip[s] = alloc(b, n, p.nf[s], hs, ws);
         for (int i = 0; i < 2 * p.nc[s]; ++i) {
             int ci, co; chans(p, s, i, ci, co);
-            const size_t e = (size_t)co * hs * ws;
-            if (e > big) { big = e; }
-            if ((size_t)co > bigc) bigc = co;
-            if (hs > bigh) { bigh = hs; bigw = ws; }
+            const int np = cine_conv_stat_partials(co, hs, ws, 0);
+            big = std::max(big, (size_t)co * hs * ws);
+            bigp = std::max(bigp, (size_t)((co + 15) / 16 * 16) * (np > 0 ? np : 1));
         }
     }
-    const int npmax = cine_conv_stat_partials(16, bigh, bigw, 0);      // most tiles per plane occur at the finest scale
     for (int i = 0; i < 3; ++i) {
         p.scr[i].x = b.take((size_t)n * big);
-        p.scr[i].part = b.take((size_t)n * bigc * (npmax > 0 ? npmax : 1) * 3 * 4);
+        p.scr[i].part = b.take((size_t)n * bigp * 3);
     }
 }
+
+// out_ch > first_filters: the reference builds the network (scale 0's last conv gets max(4 first, 4 out_ch) outputs, mwcnn.py:124-128) but its
+// forward adds tensors of out_ch and first_filters channels (:172) and raises; there is no result to reproduce
+bool widths_ok(int out_ch, int first) { return out_ch <= first; }
 
 int check_topology(int n_scales, const int* nf, const int* nc, int n_first_convs, int res) {
     CINE_REQUIRE(n_scales >= 1 && n_scales <= kMaxScales, CINE_EUNSUPPORTED, "cine_mwcnn: n_scales %d", n_scales);
@@ -85,7 +89,9 @@ int check_topology(int n_scales, const int* nf, const int* nc, int n_first_convs
 
 extern "C" size_t cine_mwcnn_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int n_scales, const int* n_filters,
                                       const int* n_convs, int first_filters) {
-    if (n <= 0 || h <= 0 || w <= 0 || n_scales < 1 || n_scales > kMaxScales || !n_filters || !n_convs) return 0;
+    if (n <= 0 || h <= 0 || w <= 0 || n_scales < 1 || n_scales > kMaxScales || !n_filters || !n_convs || in_ch <= 0 || out_ch <= 0 || first_filters <= 0 ||
+        !widths_ok(out_ch, first_filters)) return 0;
+    for (int s = 0; s < n_scales; ++s) if (n_filters[s] <= 0 || n_convs[s] < 1 || 2 * n_convs[s] > kMaxConvs) return 0;
     Plan p{}; p.S = n_scales; p.first = first_filters; p.out_ch = out_ch; p.in_ch = in_ch;
     for (int s = 0; s < n_scales; ++s) { p.nf[s] = n_filters[s]; p.nc[s] = n_convs[s]; }
     Bump b{nullptr, 0};
@@ -122,6 +128,7 @@ static int mwcnn_impl(const float* x, float* y, const void* const* weights, cons
     CINE_REQUIRE(x && y && weights && ws && n_filters && n_convs, CINE_EINVAL, "cine_mwcnn_forward: null pointer");
     CINE_REQUIRE(kSlope >= 0.f && kSlope <= 1.f, CINE_EINVAL, "cine_mwcnn_forward: LeakyReLU slope %g outside [0, 1]", (double)kSlope);
     CINE_REQUIRE(n > 0 && h > 0 && w > 0 && in_ch > 0 && out_ch > 0 && first_filters > 0, CINE_EINVAL, "cine_mwcnn_forward: bad sizes");
+    CINE_REQUIRE(widths_ok(out_ch, first_filters), CINE_EINVAL, "cine_mwcnn_forward: out_ch %d > first_filters %d (the reference's forward raises, mwcnn.py:172)", out_ch, first_filters);
     if (int e = check_topology(n_scales, n_filters, n_convs, n_first_convs, res)) return e;
     CINE_REQUIRE(h % (1 << n_scales) == 0 && w % (1 << n_scales) == 0, CINE_EINVAL,
                  "cine_mwcnn_forward: %dx%d is not a multiple of 2^%d (pad_for_mwcnn first)", h, w, n_scales);
@@ -134,26 +141,21 @@ static int mwcnn_impl(const float* x, float* y, const void* const* weights, cons
     // pointer index of conv_blocks_per_scale[s][i] in module order (after first_convs[0])
     int woff[kMaxScales + 1]; woff[0] = 1;
     for (int s = 0; s < p.S; ++s) woff[s + 1] = woff[s] + 2 * p.nc[s];
-    auto WB = [&](int s, int i) { return reinterpret_cast<const float*>(weights[woff[s] + i]); };
     for (int i = 0; i < woff[p.S] + 2; ++i) CINE_REQUIRE(weights[i] && (!weights2 || weights2[i]), CINE_EINVAL, "cine_mwcnn_forward: weights[%d] is null", i);
-    // the second set's pointer for the same slot (weights and weights2 are parallel arrays)
-    auto second = [&](const float* first) -> const float* {
-        if (!weights2 || !first) return nullptr;
-        for (int i = 0; i < woff[p.S] + 2; ++i) if (weights[i] == first) return reinterpret_cast<const float*>(weights2[i]);
-        return nullptr;
-    };
-    auto conv = [&](const Feat& s0, int mode0, const Feat* s1, int mode1, int add, const float* wp, const float* bias,
+    // the second set's pointer of the same SLOT (weights and weights2 are parallel arrays; a pointer may sit in several slots of one set)
+    auto W = [&](int idx, int set) { return reinterpret_cast<const float*>((set ? weights2 : weights)[idx]); };
+    auto conv = [&](const Feat& s0, int mode0, const Feat* s1, int mode1, int add, int widx, bool bias,
                     float* yo, float* po, int cout, int ho, int wo) {
         return cine_conv3x3_ex2(s0.x, s0.part, s0.np, s0.c, mode0, s0.h, s0.w,
                                 s1 ? s1->x : nullptr, s1 ? s1->part : nullptr, s1 ? s1->np : 0, s1 ? s1->c : 0, mode1,
-                                s1 ? s1->h : 0, s1 ? s1->w : 0, add, wp, bias, second(wp), second(bias), set_split,
+                                s1 ? s1->h : 0, s1 ? s1->w : 0, add, W(widx, 0), bias ? W(widx + 1, 0) : nullptr,
+                                weights2 ? W(widx, 1) : nullptr, (bias && weights2) ? W(widx + 1, 1) : nullptr, set_split,
                                 nullptr, 0, yo, po, n, cout, ho, wo, kEps, kSlope, stream);
     };
     int e;
     // first conv block (mwcnn.py:143-146): in_ch -> first filters at full resolution
     Feat in{const_cast<float*>(x), nullptr, in_ch, h, w, 0};
-    if ((e = conv(in, M_PLAIN, nullptr, 0, 0, reinterpret_cast<const float*>(weights[0]), nullptr, p.first_feat.x,
-                  p.first_feat.part, p.first, h, w))) return e;
+    if ((e = conv(in, M_PLAIN, nullptr, 0, 0, 0, false, p.first_feat.x, p.first_feat.part, p.first, h, w))) return e;
     // ---- analysis path (:148-154): DWT on load, n_convs blocks per scale
     Feat cur = p.first_feat;
     int scr_i = 0;
@@ -164,7 +166,7 @@ static int mwcnn_impl(const float* x, float* y, const void* const* weights, cons
             const bool last = i == p.nc[s] - 1;
             Feat out = last ? p.skip[s] : p.scr[scr_i];
             out.c = co; out.h = hs; out.w = wsz; out.np = cine_conv_stat_partials(co, hs, wsz, 0);
-            if ((e = conv(cur, i == 0 ? M_DWT_ACT : M_ACT, nullptr, 0, 0, WB(s, i), nullptr, out.x, out.part, co, hs, wsz))) return e;
+            if ((e = conv(cur, i == 0 ? M_DWT_ACT : M_ACT, nullptr, 0, 0, woff[s] + i, false, out.x, out.part, co, hs, wsz))) return e;
             if (!last) scr_i = (scr_i + 1) % 3;
             cur = out;
         }
@@ -177,18 +179,16 @@ static int mwcnn_impl(const float* x, float* y, const void* const* weights, cons
             Feat out = p.scr[scr_i];
             out.c = co; out.h = hs; out.w = wsz; out.np = cine_conv_stat_partials(co, hs, wsz, 0);
             if (i == p.nc[s] && s != p.S - 1)   // IWT of the coarser scale + this scale's last analysis feature
-                e = conv(cur, M_IWT_ACT, &p.skip[s], M_ACT, 1, WB(s, i), nullptr, out.x, out.part, co, hs, wsz);
+                e = conv(cur, M_IWT_ACT, &p.skip[s], M_ACT, 1, woff[s] + i, false, out.x, out.part, co, hs, wsz);
             else
-                e = conv(cur, M_ACT, nullptr, 0, 0, WB(s, i), nullptr, out.x, out.part, co, hs, wsz);
+                e = conv(cur, M_ACT, nullptr, 0, 0, woff[s] + i, false, out.x, out.part, co, hs, wsz);
             if (e) return e;
             scr_i = (scr_i + 1) % 3;
             cur = out;
         }
     }
     // ---- final IWT + first feature, last conv with bias and no norm (:170-174, 77-83)
-    const float* wl = reinterpret_cast<const float*>(weights[woff[p.S]]);
-    const float* bl = reinterpret_cast<const float*>(weights[woff[p.S] + 1]);
-    return conv(cur, M_IWT_ACT, &p.first_feat, M_ACT, 1, wl, bl, y, nullptr, out_ch, h, w);
+    return conv(cur, M_IWT_ACT, &p.first_feat, M_ACT, 1, woff[p.S], true, y, nullptr, out_ch, h, w);
 }
 
 // ---------------------------------------------------------------- training: forward that keeps every feature map, and the backward pass
@@ -232,7 +232,9 @@ ConvIn conv_input(const TrainPlan& t, int s, int i) {
 
 extern "C" size_t cine_mwcnn_train_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int n_scales, const int* n_filters,
                                             const int* n_convs, int first_filters) {
-    if (n <= 0 || h <= 0 || w <= 0 || n_scales < 1 || n_scales > kMaxScales || !n_filters || !n_convs) return 0;
+    if (n <= 0 || h <= 0 || w <= 0 || n_scales < 1 || n_scales > kMaxScales || !n_filters || !n_convs || in_ch <= 0 || out_ch <= 0 || first_filters <= 0 ||
+        !widths_ok(out_ch, first_filters)) return 0;
+    for (int s = 0; s < n_scales; ++s) if (n_filters[s] <= 0 || n_convs[s] < 1 || 2 * n_convs[s] > kMaxConvs) return 0;
     TrainPlan t{}; plan_from(t.p, in_ch, out_ch, n_scales, n_filters, n_convs, first_filters);
     Bump b{nullptr, 0};
     build_train(t, b, n, h, w);
@@ -245,6 +247,7 @@ extern "C" int cine_mwcnn_forward_train(const float* x, float* y, const void* co
     CINE_REQUIRE(x && y && weights && ws && n_filters && n_convs, CINE_EINVAL, "cine_mwcnn_forward_train: null pointer");
     CINE_REQUIRE(kSlope >= 0.f && kSlope <= 1.f, CINE_EINVAL, "cine_mwcnn_forward_train: LeakyReLU slope %g outside [0, 1]", (double)kSlope);
     CINE_REQUIRE(n > 0 && h > 0 && w > 0 && in_ch > 0 && out_ch > 0 && first_filters > 0, CINE_EINVAL, "cine_mwcnn_forward_train: bad sizes");
+    CINE_REQUIRE(widths_ok(out_ch, first_filters), CINE_EINVAL, "cine_mwcnn_forward_train: out_ch %d > first_filters %d (the reference's forward raises, mwcnn.py:172)", out_ch, first_filters);
     if (int e = check_topology(n_scales, n_filters, n_convs, n_first_convs, res)) return e;
     CINE_REQUIRE(h % (1 << n_scales) == 0 && w % (1 << n_scales) == 0, CINE_EINVAL, "cine_mwcnn_forward_train: %dx%d is not a multiple of 2^%d", h, w, n_scales);
     CINE_REQUIRE(ws_bytes >= cine_mwcnn_train_ws_bytes(n, h, w, in_ch, out_ch, n_scales, n_filters, n_convs, first_filters), CINE_EWORKSPACE,
@@ -297,7 +300,9 @@ static size_t mwcnn_mat_floats(const Plan& p, int n, int h, int w, int in_ch) {
 
 extern "C" size_t cine_mwcnn_backward_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int n_scales, const int* n_filters,
                                                const int* n_convs, int first_filters) {
-    if (n <= 0 || h <= 0 || w <= 0 || n_scales < 1 || n_scales > kMaxScales || !n_filters || !n_convs) return 0;
+    if (n <= 0 || h <= 0 || w <= 0 || n_scales < 1 || n_scales > kMaxScales || !n_filters || !n_convs || in_ch <= 0 || out_ch <= 0 || first_filters <= 0 ||
+        !widths_ok(out_ch, first_filters)) return 0;
+    for (int s = 0; s < n_scales; ++s) if (n_filters[s] <= 0 || n_convs[s] < 1 || 2 * n_convs[s] > kMaxConvs) return 0;
     Plan p; plan_from(p, in_ch, out_ch, n_scales, n_filters, n_convs, first_filters);
     Bump b{nullptr, 0};
     size_t big = (size_t)n * p.first * h * w, wg = wgrad_ws_floats(p.first, in_ch, 9, n);
@@ -326,7 +331,10 @@ extern "C" int cine_mwcnn_backward(const float* x, const float* gy, const void* 
     CINE_REQUIRE(x && gy && wdgrad && grads && fwd_ws && ws && n_filters && n_convs, CINE_EINVAL, "cine_mwcnn_backward: null pointer");
     CINE_REQUIRE(kSlope >= 0.f && kSlope <= 1.f, CINE_EINVAL, "cine_mwcnn_backward: LeakyReLU slope %g outside [0, 1]", (double)kSlope);
     CINE_REQUIRE(n > 0 && n <= 65535 && h > 0 && w > 0, CINE_EINVAL, "cine_mwcnn_backward: bad sizes");
+    CINE_REQUIRE(in_ch > 0 && out_ch > 0 && first_filters > 0, CINE_EINVAL, "cine_mwcnn_backward: bad channel counts");
+    CINE_REQUIRE(widths_ok(out_ch, first_filters), CINE_EINVAL, "cine_mwcnn_backward: out_ch %d > first_filters %d (the reference's forward raises, mwcnn.py:172)", out_ch, first_filters);
     if (int e = check_topology(n_scales, n_filters, n_convs, 1, 0)) return e;
+    CINE_REQUIRE(h % (1 << n_scales) == 0 && w % (1 << n_scales) == 0, CINE_EINVAL, "cine_mwcnn_backward: %dx%d is not a multiple of 2^%d", h, w, n_scales);
     const bool two = wdgrad2 != nullptr;
     CINE_REQUIRE(!two || (grads2 && set_split > 0 && set_split < n), CINE_EINVAL, "cine_mwcnn_backward: second weight set");
     CINE_REQUIRE(fwd_ws_bytes >= cine_mwcnn_train_ws_bytes(n, h, w, in_ch, out_ch, n_scales, n_filters, n_convs, first_filters) &&

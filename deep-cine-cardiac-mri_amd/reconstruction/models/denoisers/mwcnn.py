@@ -99,6 +99,11 @@ class MWCNN(nn.Module):
             # which is then the depth axis).  There is no reference behaviour to reproduce; XPDNet never builds it (xpdnet.py:251-262).
             raise NotImplementedError("MWCNN(dims=3).forward: the reference's forward raises for every input (its IWT unpacks four dimensions, "
                                       "mwcnn.py:252); only dims = 2 has a defined result")
+        if self.out_chans > self.first_conv_n_filters and self.n_first_convs > 0:
+            # the reference constructs this network (scale 0's last conv gets max(4 first, 4 out) filters, mwcnn.py:124-128) but its forward adds the
+            # IWT's out_chans channels to the first block's first_conv_n_filters (:172) and raises; the HIP entry points refuse it (CINE_EINVAL)
+            raise ValueError(f"MWCNN.forward: out_chans {self.out_chans} > first_conv_n_filters {self.first_conv_n_filters}: the reference's forward "
+                             "raises for this network (mwcnn.py:172 adds tensors of those two channel counts)")
         if torch.is_grad_enabled() and (inputs.requires_grad or any(p.requires_grad for p in self.parameters())):
             from cine_hip import autograd as ag          # training: forward keeps every feature map, backward = cine_mwcnn_backward
             return ag.mwcnn(inputs, self.hip_weights())

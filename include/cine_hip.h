@@ -434,7 +434,12 @@ int cine_normunet3d_unpack(const float* planes, const float* stats, float* y, in
  * multiples of 2^n_scales (utils/padding.py pads before the call).  Handles the topology XPDNet builds
  * (n_first_convs = 1, res = False, xpdnet.py:251-262); others return CINE_EUNSUPPORTED.
  * `weights` (host array of device pointers, all 3x3 packed with cine_pack_conv3x3):
- *   first_convs[0]; conv_blocks_per_scale[s][i] for s, i in module order; first_convs[1] weight, bias. */
+ *   first_convs[0]; conv_blocks_per_scale[s][i] for s, i in module order; first_convs[1] weight, bias.
+ * A pointer may sit in several slots (tied modules); a second set is read slot by slot, whatever the first set ties.
+ * Limits: 1 <= n_scales <= 6, 1 <= n_convs[s] <= 4, n_filters[s] > 0 (else CINE_EUNSUPPORTED), and out_ch <= first_filters: the reference
+ * constructs a network with out_ch > first_filters (mwcnn.py:124-128) but its forward adds tensors of out_ch and first_filters channels
+ * (:172) and raises, so there is nothing to reproduce -- every cine_mwcnn_* entry point returns CINE_EINVAL naming the two counts.  The
+ * *_ws_bytes queries return 0 for any argument their entry point refuses by value (sizes, limits, out_ch > first_filters). */
 size_t cine_mwcnn_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int n_scales, const int* n_filters,
                            const int* n_convs, int first_filters);
 int cine_mwcnn_forward(const float* x, float* y, const void* const* weights, int n, int h, int w,
@@ -810,7 +815,9 @@ int cine_unet3d_backward(const float* x, const float* gy, const void* const* wdg
  * LeakyReLU backward with the Haar DWT / IWT adjoints (the transforms are orthogonal: each one's adjoint is the other) and the additive
  * skips gathered on load, input gradients on the forward conv kernel, weight gradients with the wavelet / summed sources re-staged.
  * weights / weights2, set_split as cine_mwcnn_forward2 (weights2 NULL: one network); wdgrad*: the cine_pack_conv3x3_dgrad packings in the
- * order of `weights` (bias slot ignored); grads*: the parameters' own layouts, accumulated into. */
+ * order of `weights` (bias slot ignored); grads*: the parameters' own layouts, accumulated into.  cine_mwcnn_backward: n <= 65535, h and w
+ * multiples of 2^n_scales and out_ch <= first_filters as in the forward (CINE_EINVAL otherwise, before anything is launched); gx may be NULL;
+ * x, gy and fwd_ws are only read. */
 size_t cine_mwcnn_train_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int n_scales, const int* n_filters,
                                  const int* n_convs, int first_filters);
 int cine_mwcnn_forward_train(const float* x, float* y, const void* const* weights, const void* const* weights2, int set_split,
