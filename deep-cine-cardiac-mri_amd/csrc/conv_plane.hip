@@ -25,7 +25,8 @@
 namespace cine {
 namespace {
 
-thread_local int g_plane_on = 7;          // bit 0: plane-wide 3x3 convs, bit 1: transpose convs, bit 2: wide planes / volumes
+thread_local int g_plane_on = 7;          // bit 0: plane-wide 3x3 convs, bit 1: transpose convs, bit 2: wide planes / volumes,
+                                          // bit 3 SET: the 2-wide planes sweep all nine taps (the form before the column-pure sweep)
 
 struct PlaneArgs {
     const float* x0; const float* part0; int c0, np0;
@@ -55,9 +56,17 @@ __device__ __forceinline__ float add_xor32(float x) {
 // 4: Haar IWT of source 0 (4 cin channels at half the extent, mwcnn.py:252-261) PLUS source 1 (cin channels of the plane's extent), both
 //    InstanceNorm + LeakyReLU on load (the additive skips of mwcnn.py:164,172): source 1 rides in the register prefetch, the IWT inputs are
 //    read when the chunk is committed
-template <int CK, int CT, int WM, int WN, int MT, int TW, int MODE>
+// COLP 1 (2-wide planes, even MT): the COLUMN-PURE sweep.  A canonical fragment is 8 rows x both columns, so every dx = -1 tap reads the zero
+// halo for its column-0 positions and every dx = +1 tap for its column-1 positions: a third of the products are fma(0, w, acc).  Here the wave
+// sweeps fragment (column c, rows 16 g .. 16 g + 15) instead and issues dx = -1 for the column-1 fragments only, dx = +1 for the column-0
+// fragments only -- 8 MFMAs per (dy, ks, ct) for 12 -- and the A operand of (column 1, dx - 1) IS the one of (column 0, dx): two LDS reads per
+// (dy, ks, g) for six.  Each accumulator sees its remaining products in the old order, and the dropped ones were exact zeros added to a sum that
+// is never -0 (it starts at +0): the same bits.  After the last chunk two lane swaps per register pair put the sums back where the epilogue
+// expects them.  The halo columns of the LDS tile are never read and not zeroed.
+template <int CK, int CT, int WM, int WN, int MT, int TW, int MODE, int COLP = 0>
 __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::MINW)) void conv_plane_kernel(PlaneArgs a) {
     using C = ConvCfg<CK, CT, WM, WN, MT, TW, 9>;
+    static_assert(!COLP || (TW == 2 && MT % 2 == 0), "column-pure sweep: 2-wide planes, fragments in pairs");
     constexpr int PW = C::PW, NT = C::NT, PR = C::PR, RP = C::RP, G = C::G, NCI = C::NCI, NWT = C::NWT;
     static_assert(C::KR == 1, "one (row, piece) slot per thread");
     typedef typename Piece<PW>::T piece_t;
@@ -202,9 +211,11 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
     if (a.cin % CK != 0) {
         for (int e = tid; e < C::IN_FLOATS; e += NT) in_lds[e] = 0.f;
     } else {
-        for (int e = tid; e < CK * C::ROWS * 2; e += NT) {
-            const int ck = e / (C::ROWS * 2), rem = e % (C::ROWS * 2);
-            in_lds[ck * C::PS + (rem >> 1) * C::COLS + ((rem & 1) ? C::COLS - 1 : TW)] = 0.f;
+        if constexpr (!COLP) {
+            for (int e = tid; e < CK * C::ROWS * 2; e += NT) {
+                const int ck = e / (C::ROWS * 2), rem = e % (C::ROWS * 2);
+                in_lds[ck * C::PS + (rem >> 1) * C::COLS + ((rem & 1) ? C::COLS - 1 : TW)] = 0.f;
+            }
         }
         if (slot && !rowok) {
             piece_t z;
@@ -377,7 +388,46 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
         if (chunk + 1 < a.nchunks) issue(chunk + 1);
         __builtin_amdgcn_sched_barrier(0);
         // ---- MFMA sweep: 9 taps x CK/4 operand groups, software-pipelined one group ahead (as conv_tile: same accumulation order)
-        {
+        if constexpr (COLP) {
+            // acc[ct][2 g + c] = fragment (column c, rows 16 g + q).  x0 / x1[ks][g]: columns 0 / 1 of row 16 g + q + dy, channel 4 ks + kk --
+            // column 0 feeds (c 1, dx 0) and (c 0, dx 1), column 1 feeds (c 1, dx 1) and (c 0, dx 2).  Weights one group ahead as below; column 1
+            // of a dy is read during its dx = 0 groups, column 0 of the next dy during this dy's dx = 2 groups (KS groups ahead of their use).
+            constexpr int KS = CK / 4, NG = 9 * KS, MG = MT / 2;
+            const int base_cp = kk * C::PS + (wn * MT * C::RPF + q) * C::COLS;
+            float af[2][CT], x0[KS][MG], x1[KS][MG];
+            auto load_w = [&](int g, float (&wa)[CT]) {
+                const int tap = g / KS, ks = g % KS;
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) wa[ct] = w_lds[base_w + (tap * CK + 4 * ks) * C::COTP + 16 * ct];
+            };
+            auto load_col = [&](int dy, int ks, int c, float (&xa)[MG]) {
+#pragma unroll
+                for (int gq = 0; gq < MG; ++gq) xa[gq] = in_lds[base_cp + (4 * ks) * C::PS + (16 * gq + dy) * C::COLS + c];
+            };
+            __builtin_amdgcn_s_setprio(0);
+            load_w(0, af[0]);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) load_col(0, ks, 0, x0[ks]);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                const int tap = g / KS, ks = g % KS;
+                const int dy = tap / 3, dx = tap % 3;
+                if (g + 1 < NG) load_w(g + 1, af[(g + 1) & 1]);
+                if (dx == 0) load_col(dy, ks, 1, x1[ks]);
+                if (dx == 2 && dy < 2) load_col(dy + 1, ks, 0, x0[ks]);
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int gq = 0; gq < MG; ++gq) {
+                        if (dx <= 1)
+                            acc[ct][2 * gq + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(dx == 0 ? x0[ks][gq] : x1[ks][gq], af[g & 1][ct], acc[ct][2 * gq + 1], 0, 0, 0);
+                        if (dx >= 1)
+                            acc[ct][2 * gq] = __builtin_amdgcn_mfma_f32_16x16x4f32(dx == 1 ? x0[ks][gq] : x1[ks][gq], af[g & 1][ct], acc[ct][2 * gq], 0, 0, 0);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_s_setprio(2);
+        } else {
             constexpr int KS = CK / 4, NG = 9 * KS;
             float af[2][CT], bf[2][MT];
             auto load_group = [&](int g, float (&wa)[CT], float (&xa)[MT]) {
@@ -403,6 +453,27 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
             __builtin_amdgcn_s_setprio(2);
         }
         if (chunk == 0) CINE_STAMP(5);
+    }
+    if constexpr (COLP) {
+        // back to the canonical slots: register j of fragment (c, g) in lane row kk is plane row 16 g + 4 kk + j of column c; the epilogue wants
+        // fragment f, lane row kk', register j' = row 8 f + 2 kk' + j' / 2, column j' % 2.  With j = 2 h + b that is (kk bit 1, kk bit 0, h) ->
+        // (f bit 0, kk' bit 1, kk' bit 0) = (kk bit 1 -> register pair, kk bit 0 -> lane bit 5, h -> lane bit 4): permlane16_swap trades h for
+        // lane bit 4, permlane32_swap then trades the register for lane bit 5
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int gq = 0; gq < MT / 2; ++gq) {
+                f32x4 k0, k1;
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int b = 0; b < 2; ++b) {
+                        const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[ct][2 * gq + c][b]), __float_as_uint(acc[ct][2 * gq + c][2 + b]), false, false);
+                        const auto t = __builtin_amdgcn_permlane32_swap(r[0], r[1], false, false);
+                        k0[2 * b + c] = __uint_as_float(t[0]); k1[2 * b + c] = __uint_as_float(t[1]);
+                    }
+                acc[ct][2 * gq] = k0; acc[ct][2 * gq + 1] = k1;
+            }
     }
     CINE_STAMP(6);
 
@@ -548,10 +619,10 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
     CINE_STAMP_RT(10);
 }
 
-template <int CK, int CT, int WM, int WN, int MT, int TW, int MODE>
+template <int CK, int CT, int WM, int WN, int MT, int TW, int MODE, int COLP = 0>
 int launch_plane(const PlaneArgs& p, int n, hipStream_t st) {
     using C = ConvCfg<CK, CT, WM, WN, MT, TW, 9>;
-    auto kern = conv_plane_kernel<CK, CT, WM, WN, MT, TW, MODE>;
+    auto kern = conv_plane_kernel<CK, CT, WM, WN, MT, TW, MODE, COLP>;
     const size_t lds = C::lds_bytes(p.c0 + p.c1) + (WN > 1 ? C::RED_FLOATS * sizeof(float) : 0);      // + the statistics exchange of the epilogue
     static std::once_flag once[64];
     static hipError_t status[64];
@@ -620,6 +691,7 @@ int launch_conv_plane(const ConvArgs& a, int ck, int ct, int wm, int wn, int mt,
     if (ck == CK_ && ct == CT_ && wm == WM_ && wn == WN_ && mt == MT_ && tw == TW_ && mode == MODE_ && (whole || !(NEEDWHOLE))) { \
         *handled = true;                                                                                                  \
         diag_count(D_CONV_PLANE);                                                                                         \
+        if (TW_ == 2 && !(g_plane_on & 8)) return launch_plane<CK_, CT_, WM_, WN_, MT_, TW_, MODE_, TW_ == 2>(p, a.n, st);  \
         return launch_plane<CK_, CT_, WM_, WN_, MT_, TW_, MODE_>(p, a.n, st);                                              \
     }
     CINE_PLANE_CASE(4, 1, 1, 4, 13, 16, 0, false)
@@ -661,7 +733,8 @@ int launch_conv_plane(const ConvArgs& a, int ck, int ct, int wm, int wn, int mt,
 // enqueued by other threads keep their own setting (default 7).
 extern "C" int cine_set_conv_plane(int on) {
     cine::set_wgrad_plane((on & 16) ? 0 : 1);       // bit 4 SET: the plane-wide weight gradients (training) on the general kernel
-    cine::g_plane_on = on & 7;       // bit 0 plane-wide 3x3 convs, bit 1 transpose convs, bit 2 wide planes / volumes (7 = all, the default)
+    cine::g_plane_on = on & 15;      // bit 0 plane-wide 3x3 convs, bit 1 transpose convs, bit 2 wide planes / volumes (7 = all, the default);
+                                     // bit 3 SET: the nine-tap sweep on the 2-wide planes
     return CINE_OK;
 }
 

@@ -772,7 +772,9 @@ int cine_pad2d(const float* x, float* out, long planes, int h, int w, int top, i
  * wider planes and volumes in 16-wide column
  * tiles (sensitivity network, CRNN cells, 3-D U-Net); `on` is a mask -- bit 0 the plane-wide 3x3 convolutions, bit 1 the
  * transpose convolutions, bit 2 the wide planes / volumes; a cleared bit routes that kind through the general kernel (the
- * bit-identity tests, A/B timing).  Bit 4 SET routes the plane-wide weight gradients of training (grad_kernels.hip:
+ * bit-identity tests, A/B timing).  Bit 3 SET makes the plane-wide 3x3 convolutions of 2-wide planes (the U-Net bottleneck, the MWCNN's
+ * coarsest scale) sweep all nine taps over fragments of 8 rows x both columns, the form before the column-pure sweep that skips the taps
+ * which only read the zero halo column (bit-identical; 15 = every lean kernel in that older form).  Bit 4 SET routes the plane-wide weight gradients of training (grad_kernels.hip:
  * wgrad_plane_kernel, also bit-identical) through the general weight-gradient kernel.  A setting of the CALLING THREAD (default 7
  * in every thread): it selects kernels for the launches that thread enqueues afterwards and changes no result but for that
  * summation order. */
