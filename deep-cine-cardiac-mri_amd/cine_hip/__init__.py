@@ -46,4 +46,7 @@ def __getattr__(name):
     if name in _CLASSICAL:
         from . import classical
         return getattr(classical, name)
+    if name == "noise":                           # cine_hip.noise: pseudo-replica noise maps, imported on first use as well
+        import importlib
+        return importlib.import_module(".noise", __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

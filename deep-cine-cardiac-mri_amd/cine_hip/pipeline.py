@@ -97,6 +97,12 @@ out of it, and ``last_coil_info`` and the residual check hold for the whitened G
 ``coil_matrix=W.to(torch.complex64)`` (at most 32 coils); together with ``coil_matrix=`` it raises.  ``sens_maps="espirit"`` then
 calibrates on the whitened virtual coils.
 
+``submit(..., noise=noise.NoiseSpec(chol, scale, seed, replica))``: one pseudo replica (``cine_hip.noise``).  The slot's stream runs
+cine_noise_add in place on the slot's copy of the k-space, between the wait for the copy and the replay, so the result is bit for bit
+``model(noise.add_noise(masked_kspace, mask, chol, scale=scale, seed=seed, replica=replica), mask[, sens_maps])``.  The spec is not part of
+the set key and no graph holds it: replicas and plain slices share one set, and ``noise=None`` is the path as it was.  ``submit_raw`` has no
+such keyword: noise in front of the crop and the filter would be coloured by them.
+
 ``graphs=False`` is the explicit eager mode: same slots, streams, buffers, copies and events, with the launch sequence
 enqueued on the slot's stream for every slice.  A failure raises ``CineHipError``; nothing falls back to eager launches.
 
@@ -299,12 +305,28 @@ def _same_device(pipe, named):
             raise CineHipError(f"{name} is on {x.device}, the pipeline's device is {pipe.device}")
 
 
+def _check_noise(pipe, spec, masked_kspace):
+    """``submit(..., noise=)`` validated: a noise.NoiseSpec with its factor as float32 pairs on the pipeline's device, or None."""
+    if spec is None:
+        return None
+    from . import noise as N
+    if not isinstance(spec, N.NoiseSpec):
+        raise CineHipError(f"noise: expected a cine_hip.noise.NoiseSpec(chol, scale, seed, replica), got {type(spec).__name__}")
+    c = masked_kspace.shape[2] if isinstance(masked_kspace, torch.Tensor) and masked_kspace.dim() >= 5 else 0
+    if c > N.NOISE_MAX_COILS:
+        raise CineHipError(f"noise: {c} coils, at most {N.NOISE_MAX_COILS}")
+    if isinstance(spec.replica, bool) or not isinstance(spec.replica, int) or not 0 <= spec.replica < 1 << 32:
+        raise CineHipError(f"noise: replica {spec.replica!r} is not an integer in [0, 2^32)")
+    return spec._replace(chol=N._chol_pairs(spec.chol, c, pipe.device), scale=float(spec.scale), seed=int(spec.seed))
+
+
 class _Source:
     """One slice's validated inputs: torch views in their original place, the canonical mask, the set key."""
     raw = None                                      # no front-end in this set's graphs
     input_names = ("mk", "mask", "sens")
 
-    def __init__(self, pipe, masked_kspace, mask, sens_maps, ecalib_r=15, sign_iters=60):
+    def __init__(self, pipe, masked_kspace, mask, sens_maps, ecalib_r=15, sign_iters=60, noise=None):
+        self.noise = _check_noise(pipe, noise, masked_kspace)                # not part of the key: the graphs do not hold it
         mk, self.mk_kind = _pairs(masked_kspace, "masked_kspace")
         if mk.dim() != 6:
             raise CineHipError(f"masked_kspace: shape {tuple(mk.shape)}; expected (b, t, c, h, w, 2) or complex (b, t, c, h, w)")
@@ -382,6 +404,7 @@ class _RawSource:
     """One raw slice's validated inputs (``submit_raw``): the kept frames of the raw data in their original place, mask, sens, the coil
     matrix, the front-end's settings, the set key."""
     input_names = ("raw", "mask", "sens", "cmat", "wh")
+    noise = None                                    # submit(noise=) is for prepared k-space only
 
     def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask, ecalib_r=15,
                  sign_iters=60, virtual_coils=None, cc_region=24, whitener=None):
@@ -598,14 +621,20 @@ class SlicePipeline:
         self.streams, self.copy_stream = pipeline_streams(device, slots)
 
     # ---- public ----------------------------------------------------------------------------------------------------------
-    def submit(self, masked_kspace, mask, sens_maps=None, tag=None, *, ecalib_r: int = 15, sign_iters: int = 60) -> SliceHandle:
+    def submit(self, masked_kspace, mask, sens_maps=None, tag=None, *, ecalib_r: int = 15, sign_iters: int = 60,
+               noise=None) -> SliceHandle:
         """Enqueue one slice.  Returns at once, unless 2 x slots slices are pending: then it waits for the oldest one.
         ``sens_maps="espirit"``: the maps of every batch element are calibrated inside the slot's graph from the time average of its masked
         k-space, ``frontend.espirit_maps(frontend.time_average(mk[i]), r=ecalib_r, method="sign", sign_iters=sign_iters)`` (the
-        reference's ``bart ecalib -r 15``, data/transforms.py:425-432)."""
+        reference's ``bart ecalib -r 15``, data/transforms.py:425-432).
+        ``noise=noise.NoiseSpec(chol, scale, seed, replica)``: one pseudo replica -- the slot's stream runs cine_noise_add in place on
+        the slot's copy of the k-space, between the copy and the replay, so the slice is reconstructed from
+        ``noise.add_noise(masked_kspace, mask, chol, scale=scale, seed=seed, replica=replica)``, bit for bit.  The spec is not part of
+        the set key; ``noise=None`` takes the path it always took.  It describes noise on the PREPARED k-space: ``submit_raw`` has
+        no such keyword (the crop and the filter of the front-end would colour noise injected in front of them)."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit after close()")
-        return self._submit(_Source(self, masked_kspace, mask, sens_maps, ecalib_r, sign_iters), tag)
+        return self._submit(_Source(self, masked_kspace, mask, sens_maps, ecalib_r, sign_iters, noise), tag)
 
     def submit_raw(self, raw, mask, sens_maps=None, tag=None, *, crop_shape=(200, 200), n_frames: int = 15,
                    filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True,
@@ -924,6 +953,10 @@ class SlicePipeline:
         with torch.cuda.stream(s):
             s.wait_event(st.ready[key])
             self._pre(st.bufs[key], src)
+            if src.noise is not None:               # a pseudo replica: in place on the slot's k-space, in front of the replay
+                from . import noise as N
+                b, ns = st.bufs[key], src.noise
+                N.add_noise(b["mk"], b["mask"], ns.chol, scale=ns.scale, seed=ns.seed, replica=ns.replica, out=b["mk"])
             if self.graphs:
                 g, static = st.graphs[key]
                 g.replay()

@@ -1126,6 +1126,60 @@ int cine_llr_solve(float* x, const float* zf, const float* sens, const float* se
                    float* rec, double* info, int b, int t, int c, int h, int w, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * noise propagation by pseudo multiple replicas (no reference counterpart; Robson et al., MRM 60:895-907, 2008: add synthetic noise
+ * of the scanner's covariance to the measured k-space, reconstruct N times, take the per-pixel standard deviation).
+ *
+ * The noise source is Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), and its definition is part of this interface -- the tests
+ * restate it independently (tests/noise_reference.py); csrc/philox.h is its one implementation, for the device and the host.
+ *
+ *   multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57
+ *   Weyl increments W0 = 0x9E3779B9, W1 = 0xBB67AE85
+ *
+ *   (c0,c1,c2,c3) -> (hi(M1*c2)^c1^k0, lo(M1*c2), hi(M0*c0)^c3^k1, lo(M0*c0))
+ *   (k0,k1) += (W0,W1) after every round                                          ten rounds
+ *
+ *   key     = (seed & 0xffffffff, seed >> 32)                                     the 64 bits of the long, the shift logical
+ *   counter = (p & 0xffffffff, p >> 32, replica, j)
+ *   p = point0 + ((bt * h + y) * w + x)      // 64-bit index of the k-space point
+ *   j = coil pair index
+ *
+ * One call yields x0..x3.  Coil 2j uses (x0, x1) and coil 2j+1 uses (x2, x3).  An odd last coil discards the second half.
+ * From words to a complex normal with E|z|^2 = 1, for the words (a, b) of one coil:
+ *
+ *   u1 = ((a >> 9) + 0.5f) * 2^-23     // in [2^-24, 1 - 2^-24], every step exact in float32
+ *   u2 = (b >> 8) * 2^-24              // in [0, 1), exact
+ *   z  = sqrtf(-logf(u1)) * (cospif(2 u2) + i sinpif(2 u2))
+ *
+ * with logf, sqrtf and sincospif, not their fast forms.  Correlated noise: eta_i = scale * sum_{k <= i} L[i,k] z_k, ascending k, an
+ * fmaf chain from 0 (per term: re = fmaf(L.re, z.re, re), re = fmaf(-L.im, z.im, re), im = fmaf(L.re, z.im, im), im = fmaf(L.im, z.re,
+ * im)); L is lower-triangular complex64 with Psi = L L^H, Psi as frontend.noise_covariance defines it (Psi[i, j] = E eta_i conj(eta_j)).
+ * A value depends only on (seed, replica, p, coil), never on grid, tile or launch shape.
+ * ------------------------------------------------------------------------------------------ */
+/* out = kspace + eta at the sampled points, out = kspace at the others.  kspace, out: (bt, c, h, w, 2); out == kspace is allowed (in
+ * place: nothing is read or written at a point that is not sampled), any other overlap of the two is CINE_EINVAL.  mask: uint8 (bt, h)
+ * for mask_w == 1 or (bt, h, w) for mask_w == w, the convention of cine_kt_fista; NULL: every point (mask_w is still checked: pass 1).
+ * chol: (c, c) complex64 pairs, the lower triangle read, the diagonal as stored; NULL: white noise, eta = scale * z.  replica in
+ * [0, 2^32); replica_dev, if non-NULL, is a device long the kernel reads in its place, so that a captured graph draws fresh noise on
+ * every replay once the caller bumps the counter.  point0 >= 0 places the call's first point on the 64-bit point axis: a stack of
+ * frames equals its frames noised one by one with point0 advanced by h * w each.  At most 64 coils (CINE_EUNSUPPORTED).
+ * CINE_EINVAL: null kspace / out, non-positive sizes, mask_w outside {1, w}, replica outside its range, a negative point0, a pointer
+ * off its 8-byte alignment.  Every argument is checked before the launch; no allocation, no host read, no atomics: capturable, and
+ * the same bits on every call. */
+int cine_noise_add(const float* kspace, float* out, const uint8_t* mask, int mask_w, const float* chol, float scale,
+                   long seed, long replica, const long* replica_dev, long point0, long bt, int c, int h, int w, void* stream);
+/* Welford's update of (mean, m2) with the k-th sample x, k >= 1, element-wise over n floats, in float64:
+ *   d = x - mean;  mean += d / k;  m2 += d * (x - mean)
+ * k == 1 initialises both buffers (they are not read and need not be zeroed).  Null pointers, n <= 0, k < 1, mean == m2: CINE_EINVAL. */
+int cine_replica_accum(const float* x, double* mean, double* m2, long n, int k, void* stream);
+/* The maps of k >= 2 accumulated samples: var = m2 / (k - 1), std = sqrt(var), mean_out = mean, snr = |mean| / std (0 where std == 0),
+ * g = std / (ref_std * sqrt(accel)) (0 where ref_std == 0).  pairs != 0: the n floats are n / 2 complex values, var = var_re + var_im,
+ * the mean's magnitude |mean| takes the place of the mean, and every map (ref_std too) has n / 2 elements; n must then be even.  Any
+ * output may be NULL; g_out needs ref_std and accel > 0.  Computed in float64, rounded once.  CINE_EINVAL for what is stated above,
+ * null mean / m2, n <= 0 and k < 2. */
+int cine_replica_finish(const double* mean, const double* m2, long n, int k, int pairs, const float* ref_std, float accel,
+                        float* mean_out, float* std_out, float* snr_out, float* g_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * measurement aid (no reference counterpart; the reference only wraps time.time() around the
  * model call, traintest_scripts/run_inference.py:53-61)
  * ------------------------------------------------------------------------------------------ */
