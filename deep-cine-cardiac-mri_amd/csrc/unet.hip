@@ -131,9 +131,13 @@ void build(Plan& p, Bump& b, int n, int h, int w, int chans, int pools, bool pri
 
 }  // namespace
 
+// What every entry point of this file accepts; the size queries return 0 for anything else (a size query refuses what its entry point refuses)
+static bool shape_ok(int n, int h, int w, int in_ch, int out_ch, int chans, int pools) {
+    return n > 0 && h > 0 && w > 0 && in_ch > 0 && out_ch > 0 && chans > 0 && pools > 0 && pools <= 6 && (h >> pools) >= 1 && (w >> pools) >= 1;
+}
+
 extern "C" size_t cine_unet2d_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int chans, int pools) {
-    if (n <= 0 || h <= 0 || w <= 0 || chans <= 0 || pools <= 0 || pools > 6) return 0;
-    (void)in_ch; (void)out_ch;
+    if (!shape_ok(n, h, w, in_ch, out_ch, chans, pools)) return 0;
     Plan p; Bump b{nullptr, 0};
     build(p, b, n, h, w, chans, pools, false);
     return b.off;
@@ -141,8 +145,7 @@ extern "C" size_t cine_unet2d_ws_bytes(int n, int h, int w, int in_ch, int out_c
 
 // training: every layer output keeps its own memory (the backward pass reads all of them)
 extern "C" size_t cine_unet2d_train_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int chans, int pools) {
-    if (n <= 0 || h <= 0 || w <= 0 || chans <= 0 || pools <= 0 || pools > 6) return 0;
-    (void)in_ch; (void)out_ch;
+    if (!shape_ok(n, h, w, in_ch, out_ch, chans, pools)) return 0;
     Plan p; Bump b{nullptr, 0};
     build(p, b, n, h, w, chans, pools, true);
     return b.off;
@@ -450,7 +453,7 @@ void build_bwd(BwdPlan& q, const Plan& p, Bump& b, int n, int in_ch, int out_ch)
 }  // namespace
 
 extern "C" size_t cine_unet2d_backward_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int chans, int pools) {
-    if (n <= 0 || h <= 0 || w <= 0 || chans <= 0 || pools <= 0 || pools > 6 || in_ch <= 0 || out_ch <= 0) return 0;
+    if (!shape_ok(n, h, w, in_ch, out_ch, chans, pools) || n > 65535) return 0;
     Plan p; Bump b0{nullptr, 0};
     build(p, b0, n, h, w, chans, pools, true);
     BwdPlan q; Bump b{nullptr, 0};
@@ -480,6 +483,7 @@ extern "C" int cine_unet2d_backward_drop(const float* x, const float* gy, const 
     CINE_REQUIRE(nsets == 1 || nsets == 2, CINE_EINVAL, "cine_unet2d_backward: nsets must be 1 or 2");
     CINE_REQUIRE(n > 0 && n % nsets == 0 && n <= 65535, CINE_EINVAL, "cine_unet2d_backward: n=%d", n);
     CINE_REQUIRE(h > 0 && w > 0 && in_ch > 0 && out_ch > 0 && chans > 0 && pools > 0 && pools <= 6, CINE_EINVAL, "cine_unet2d_backward: bad sizes");
+    CINE_REQUIRE((h >> pools) >= 1 && (w >> pools) >= 1, CINE_EUNSUPPORTED, "cine_unet2d_backward: %dx%d too small for %d pools", h, w, pools);
     CINE_REQUIRE(fwd_ws_bytes >= cine_unet2d_train_ws_bytes(n, h, w, in_ch, out_ch, chans, pools), CINE_EWORKSPACE,
                  "cine_unet2d_backward: forward workspace too small");
     CINE_REQUIRE(ws_bytes >= cine_unet2d_backward_ws_bytes(n, h, w, in_ch, out_ch, chans, pools), CINE_EWORKSPACE,

@@ -98,18 +98,20 @@ void build(Plan& p, Bump& b, int n, int d, int h, int w, int chans, int pools, b
 }
 bool sizes_ok(int n, int d, int h, int w, int chans, int pools) { return n > 0 && d > 0 && h > 0 && w > 0 && chans > 0 && pools > 0 && pools <= 6; }
 }  // namespace
+// What every entry point of this file accepts; the size queries return 0 for anything else (a size query refuses what its entry point refuses)
+static bool shape_ok(int n, int d, int h, int w, int in_ch, int out_ch, int chans, int pools) {
+    return sizes_ok(n, d, h, w, chans, pools) && in_ch > 0 && out_ch > 0 && (d >> pools) >= 1 && (h >> pools) >= 1 && (w >> pools) >= 1;
+}
 
 extern "C" size_t cine_unet3d_ws_bytes(int n, int d, int h, int w, int in_ch, int out_ch, int chans, int pools) {
-    if (!sizes_ok(n, d, h, w, chans, pools)) return 0;
-    (void)in_ch; (void)out_ch;
+    if (!shape_ok(n, d, h, w, in_ch, out_ch, chans, pools)) return 0;
     Plan p; Bump b{nullptr, 0};
     build(p, b, n, d, h, w, chans, pools, false);
     return b.off;
 }
 // training: every layer output keeps its own memory (cine_unet3d_backward reads all of them)
 extern "C" size_t cine_unet3d_train_ws_bytes(int n, int d, int h, int w, int in_ch, int out_ch, int chans, int pools) {
-    if (!sizes_ok(n, d, h, w, chans, pools)) return 0;
-    (void)in_ch; (void)out_ch;
+    if (!shape_ok(n, d, h, w, in_ch, out_ch, chans, pools)) return 0;
     Plan p; Bump b{nullptr, 0};
     build(p, b, n, d, h, w, chans, pools, true);
     return b.off;
@@ -306,7 +308,7 @@ void build_bwd(BwdPlan& q, const Plan& p, Bump& b, int n, int in_ch, int out_ch)
 }  // namespace
 
 extern "C" size_t cine_unet3d_backward_ws_bytes(int n, int d, int h, int w, int in_ch, int out_ch, int chans, int pools) {
-    if (!sizes_ok(n, d, h, w, chans, pools) || in_ch <= 0 || out_ch <= 0) return 0;
+    if (!shape_ok(n, d, h, w, in_ch, out_ch, chans, pools) || n > 65535) return 0;
     Plan p; Bump b0{nullptr, 0};
     build(p, b0, n, d, h, w, chans, pools, true);
     BwdPlan q; Bump b{nullptr, 0};

@@ -383,7 +383,10 @@ int cine_instnorm_lrelu_apply(const float* x, const float* part, int np, float* 
  * i.e. 2*pools + 2 + 3*pools + 2 pointers.
  * `nsets` == 2 runs two weight sets over the two halves of the n planes in the SAME launches
  * (the xf and yf U-Nets of one cascade, varnet.py:224-226); `weights` then holds two such arrays
- * back to back. */
+ * back to back.
+ * Every cine_unet2d_* / cine_unet3d_* entry point accepts n, h, w (d), in_ch, out_ch, chans > 0, 1 <= pools <= 6 and extents that leave at least
+ * one element after `pools` halvings (CINE_EUNSUPPORTED otherwise); the backward passes n <= 65535.  A *_ws_bytes query returns 0 for exactly
+ * the shapes its entry point refuses. */
 size_t cine_unet2d_ws_bytes(int n, int h, int w, int in_ch, int out_ch, int chans, int pools);
 int cine_unet2d_forward(const float* x, float* y, const void* const* weights, int nsets,
                         int n, int h, int w, int in_ch, int out_ch, int chans, int pools, float slope,
@@ -802,7 +805,10 @@ int cine_unet2d_backward(const float* x, const float* gy, const void* const* wdg
  * cine_unet3d_forward with every raw layer output and its merged statistics record kept in `ws` (cine_unet3d_train_ws_bytes), and
  * cine_unet3d_backward walks it in reverse.  `wdgrad` (order of `weights`, bias slot ignored): cine_pack_conv3d of each 3x3x3 weight with its taps
  * flipped and (cout, cin) transposed; cine_pack_conv1x1 of a transpose conv's weight (cin, cout, 2, 2, 2) read as the (cin, 8 cout) matrix;
- * cine_pack_conv1x1 of the final conv's matrix transposed (chans, out_ch).  `grads`: the parameters' own layouts ((cout, cin, 3, 3, 3) /
+ * cine_pack_conv1x1 of the final conv's matrix transposed (chans, out_ch).  The pack calls take the ROWS of the packed matrix first: for a 3x3x3
+ * weight (cout, cin, 3, 3, 3) cine_pack_conv3d(flipped and transposed weight (cin, cout, 3, 3, 3), packed, cin, cout); for a transpose conv (cin, cout,
+ * 2, 2, 2) cine_pack_conv1x1(w, packed, cin, 8 cout); for the final conv cine_pack_conv1x1(transposed matrix, packed, chans, out_ch); sizes from
+ * cine_conv3d_packed_floats / cine_conv1x1_packed_floats with the same two counts.  `grads`: the parameters' own layouts ((cout, cin, 3, 3, 3) /
  * (cin, cout, 2, 2, 2) / (out_ch, chans) / (out_ch)), accumulated into.  One weight set.  gx (n, in_ch, d, h, w) may be NULL.
  * Weight gradients run on the calling thread's side stream (cine_set_side_stream) when it has one. */
 size_t cine_unet3d_train_ws_bytes(int n, int d, int h, int w, int in_ch, int out_ch, int chans, int pools);
