@@ -26,7 +26,8 @@ namespace cine {
 namespace {
 
 thread_local int g_plane_on = 7;          // bit 0: plane-wide 3x3 convs, bit 1: transpose convs, bit 2: wide planes / volumes,
-                                          // bit 3 SET: the 2-wide planes sweep all nine taps (the form before the column-pure sweep)
+                                          // bit 3 SET: the 2-wide planes and the one-wave-per-plane 4-wide shape <8, 1, 4, 1, 13, 4> sweep all nine
+                                          // taps (the form before the column-pure sweeps)
 
 struct PlaneArgs {
     const float* x0; const float* part0; int c0, np0;
@@ -63,10 +64,24 @@ __device__ __forceinline__ float add_xor32(float x) {
 // (dy, ks, g) for six.  Each accumulator sees its remaining products in the old order, and the dropped ones were exact zeros added to a sum that
 // is never -0 (it starts at +0): the same bits.  After the last chunk two lane swaps per register pair put the sums back where the epilogue
 // expects them.  The halo columns of the LDS tile are never read and not zeroed.
+// COLP 1 on the 4-wide planes (MT 13, WN 1: one wave holds all 52 rows): a canonical fragment is 4 rows x all 4 columns, so dx = -1 reads the
+// zero halo for column 0 and dx = +1 for column 3: 2 of every 12 (column, dx) products.  Fragments 0 .. 11 (rows 0 .. 47) are swept as 12
+// column-pure ones, acc[ct][4 g + c] = (column c, rows 16 g + q); fragment 12 (rows 48 .. 51) stays canonical with all nine taps.  Column 0
+// takes dx in {1, 2}, columns 1 and 2 all three, column 3 dx in {0, 1}: 30 + 3 = 33 MFMAs per (dy, ks) for 39.  Image column x is ONE register
+// for (c = x + 1, dx 0), (c = x, dx 1) and (c = x - 1, dx 2): 12 + 3 LDS reads per (dy, ks) for 39.  Same order of the remaining products per
+// accumulator, the dropped ones exact zeros: the same bits.  After the last chunk a 4 x 4 transpose between lane row and register (two
+// permlane16_swap + two permlane32_swap per (g, c)) restores the canonical slots.  Only the mixed fragment reads halo columns (LDS rows
+// 48 .. 53), so only those are zeroed.  The channel pitch of this branch is 436 floats (not ConvCfg's 464): a pure read's 32 lanes are 16 rows
+// x 2 channels at one column, rows 8 floats apart, and 436 = 20 (mod 32) puts the second channel on the banks the first leaves free -- 4 lanes
+// per bank, the floor while all addresses of a column are equal (mod 4); at 464 = 16 (mod 32) it would be 8.
 template <int CK, int CT, int WM, int WN, int MT, int TW, int MODE, int COLP = 0>
 __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::MINW)) void conv_plane_kernel(PlaneArgs a) {
     using C = ConvCfg<CK, CT, WM, WN, MT, TW, 9>;
-    static_assert(!COLP || (TW == 2 && MT % 2 == 0), "column-pure sweep: 2-wide planes, fragments in pairs");
+    static_assert(!COLP || (TW == 2 && MT % 2 == 0) || (TW == 4 && MT == 13 && WN == 1 && CK == 8),
+                  "column-pure sweep: 2-wide planes with fragments in pairs, or the one-wave-per-plane 4-wide shape");
+    constexpr bool COL2 = COLP && TW == 2, COL4 = COLP && TW == 4;
+    constexpr int PS = COL4 ? 436 : C::PS;           // channel pitch of the LDS tile (COL4: see above; 16-byte pieces need a multiple of 4)
+    static_assert(PS >= C::ZS && PS % 4 == 0 && PS <= C::PS, "channel pitch");
     constexpr int PW = C::PW, NT = C::NT, PR = C::PR, RP = C::RP, G = C::G, NCI = C::NCI, NWT = C::NWT;
     static_assert(C::KR == 1, "one (row, piece) slot per thread");
     typedef typename Piece<PW>::T piece_t;
@@ -85,7 +100,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
     int base_in[3];
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
-        base_in[dx] = kk * C::PS + (wn * MT * C::RPF + qr) * C::COLS + (qc + dx - 1 + C::COLS) % C::COLS;
+        base_in[dx] = kk * PS + (wn * MT * C::RPF + qr) * C::COLS + (qc + dx - 1 + C::COLS) % C::COLS;
     const int base_w = kk * C::COTP + 16 * (wm * CT) + q;
 
     __builtin_amdgcn_s_setprio(2);
@@ -101,7 +116,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
     // modes 0 / 1: both sources have the plane's extent, so one channel stride; my byte offset inside a chunk's first channel
     const unsigned cstride = (unsigned)(a.H * TW) * 4u;
     const unsigned voff = (unsigned)(min(max(gy, 0), a.H - 1) * TW + PW * sj) * 4u + (unsigned)sgc * cstride;
-    float* const lrow = in_lds + sgc * C::PS + srow * C::COLS + PW * sj;
+    float* const lrow = in_lds + sgc * PS + srow * C::COLS + PW * sj;
 
     float4 wraw[NWT];
     constexpr bool HALF = MODE == 2 || MODE == 3;          // the source has twice the plane's extent: 2 x 2 input values per staged value
@@ -211,10 +226,16 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
     if (a.cin % CK != 0) {
         for (int e = tid; e < C::IN_FLOATS; e += NT) in_lds[e] = 0.f;
     } else {
-        if constexpr (!COLP) {
+        if constexpr (COL4) {                  // the mixed fragment's rows (48 .. 51 and their row halo) only
+            constexpr int R0 = 12 * C::RPF, NR = C::ROWS - R0;
+            for (int e = tid; e < CK * NR * 2; e += NT) {
+                const int ck = e / (NR * 2), rem = e % (NR * 2);
+                in_lds[ck * PS + (R0 + (rem >> 1)) * C::COLS + ((rem & 1) ? C::COLS - 1 : TW)] = 0.f;
+            }
+        } else if constexpr (!COLP) {
             for (int e = tid; e < CK * C::ROWS * 2; e += NT) {
                 const int ck = e / (C::ROWS * 2), rem = e % (C::ROWS * 2);
-                in_lds[ck * C::PS + (rem >> 1) * C::COLS + ((rem & 1) ? C::COLS - 1 : TW)] = 0.f;
+                in_lds[ck * PS + (rem >> 1) * C::COLS + ((rem & 1) ? C::COLS - 1 : TW)] = 0.f;
             }
         }
         if (slot && !rowok) {
@@ -223,7 +244,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
 #pragma unroll
             for (int u = 0; u < PW; ++u) zf[u] = 0.f;
 #pragma unroll
-            for (int i = 0; i < NCI; ++i) *reinterpret_cast<piece_t*>(lrow + i * G * C::PS) = z;
+            for (int i = 0; i < NCI; ++i) *reinterpret_cast<piece_t*>(lrow + i * G * PS) = z;
         }
     }
 
@@ -252,7 +273,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
                 const float* ib = a.x0 + (((long)n * a.c0 + ci0 + sg4c) * hs + sy4) * (TW / 2) + ((PW * sj4) >> 1);
                 const float* stp = st_lds + 2 * (a.c0 + ci0 + sg4c);
                 const bool w0 = ps4 >= 1, w1 = 2 * ps4 < C::ROWS;                 // which of my two LDS rows exist in this tile
-                float* const l0 = in_lds + sg4c * C::PS + (2 * ps4 - 1) * C::COLS + PW * sj4;
+                float* const l0 = in_lds + sg4c * PS + (2 * ps4 - 1) * C::COLS + PW * sj4;
 #pragma unroll
                 for (int i = 0; i < NCI4; ++i) {
                     float v[4][NS];
@@ -274,8 +295,8 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
                         a1[2 * e] = (v[0][e] - v[1][e] + v[2][e] - v[3][e]) + act(a1[2 * e], ss.x, ss.y, a.slope);
                         a1[2 * e + 1] = (v[0][e] + v[1][e] + v[2][e] + v[3][e]) + act(a1[2 * e + 1], ss.x, ss.y, a.slope);
                     }
-                    if (w0) *reinterpret_cast<piece_t*>(l0 + i * G4 * C::PS) = o0;
-                    if (w1) *reinterpret_cast<piece_t*>(l0 + C::COLS + i * G4 * C::PS) = o1;
+                    if (w0) *reinterpret_cast<piece_t*>(l0 + i * G4 * PS) = o0;
+                    if (w1) *reinterpret_cast<piece_t*>(l0 + C::COLS + i * G4 * PS) = o1;
                 }
             }
         } else if constexpr (!HALF) {
@@ -292,7 +313,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
                         const float2 ss = *reinterpret_cast<const float2*>(stp + 2 * i * G);
                         act_piece<PW>(reinterpret_cast<float*>(&o), ss.x, ss.y, a.slope);
                     }
-                    *reinterpret_cast<piece_t*>(lrow + i * G * C::PS) = o;
+                    *reinterpret_cast<piece_t*>(lrow + i * G * PS) = o;
                 }
             }
         } else {
@@ -326,7 +347,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
                             float* ov = reinterpret_cast<float*>(&o);
 #pragma unroll
                             for (int u = 0; u < PW; ++u) ov[u] = fmaf(s3, x3[u], fmaf(s2, x2[u], s1 * x1[u])) + x4[u];      // ((+-x1 +- x2) +- x3) + x4: fetch_scalar's order
-                            *reinterpret_cast<piece_t*>(lrow + i * G * C::PS) = o;
+                            *reinterpret_cast<piece_t*>(lrow + i * G * PS) = o;
                         }
                     }
                 }
@@ -351,7 +372,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
                                              act(t1[2 * u], ss.x, ss.y, a.slope) + act(t1[2 * u + 1], ss.x, ss.y, a.slope));
                         }
                     }
-                    *reinterpret_cast<piece_t*>(lrow + i * G * C::PS) = o;
+                    *reinterpret_cast<piece_t*>(lrow + i * G * PS) = o;
                 };
 #pragma unroll
                 for (int i = 0; i < NPRE; ++i) {
@@ -388,12 +409,60 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
         if (chunk + 1 < a.nchunks) issue(chunk + 1);
         __builtin_amdgcn_sched_barrier(0);
         // ---- MFMA sweep: 9 taps x CK/4 operand groups, software-pipelined one group ahead (as conv_tile: same accumulation order)
-        if constexpr (COLP) {
+        if constexpr (COL4) {
+            // acc[0][4 r + c] = fragment (column c, rows 16 r + q), r < 3; acc[0][12] the canonical fragment of rows 48 .. 51.  xc[ks][x][r]:
+            // image column x of row 16 r + q + dy, channel 4 ks + kk.  Weights and the mixed fragment's operand one group ahead.  Rolling
+            // column loads, each into a register no MFMA of the same group reads: column 3 of a dy during its dx = 0 group (first used at
+            // dx = 1), column 0 of the next dy during this dy's dx = 2 group (last used at dx = 1), columns 1 and 2 of the next dy in the
+            // group after this dy's dx = 2 group of the same ks (one group ahead of their first use)
+            static_assert(CT == 1, "one row block per wave");
+            constexpr int KS = CK / 4, NG = 9 * KS, NR = 3;
+            const int base_cp = kk * PS + q * C::COLS;
+            float af[2], bm[2], xc[KS][4][NR];
+            auto load_w = [&](int g, float& wa, float& xm) {
+                const int tap = g / KS, ks = g % KS;
+                const int dy = tap / 3, dx = tap % 3;
+                wa = w_lds[base_w + (tap * CK + 4 * ks) * C::COTP];
+                xm = in_lds[base_in[dx] + (4 * ks) * PS + (12 * C::RPF + dy) * C::COLS];
+            };
+            auto load_col = [&](int dy, int ks, int x, float (&xa)[NR]) {
+#pragma unroll
+                for (int r = 0; r < NR; ++r) xa[r] = in_lds[base_cp + (4 * ks) * PS + (16 * r + dy) * C::COLS + x];
+            };
+            __builtin_amdgcn_s_setprio(0);
+            load_w(0, af[0], bm[0]);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                for (int x = 0; x < 3; ++x) load_col(0, ks, x, xc[ks][x]);
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                const int tap = g / KS, ks = g % KS;
+                const int dy = tap / 3, dx = tap % 3;
+                if (g + 1 < NG) load_w(g + 1, af[(g + 1) & 1], bm[(g + 1) & 1]);
+                if (dx == 0) load_col(dy, ks, 3, xc[ks][3]);
+                if (dx == 2 && dy < 2) load_col(dy + 1, ks, 0, xc[ks][0]);
+                if (g >= 1) {
+                    const int tp = (g - 1) / KS, kp = (g - 1) % KS;
+                    if (tp % 3 == 2 && tp / 3 < 2) { load_col(tp / 3 + 1, kp, 1, xc[kp][1]); load_col(tp / 3 + 1, kp, 2, xc[kp][2]); }
+                }
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (c + dx < 1 || c + dx > 4) continue;             // image column c + dx - 1 is the zero halo
+                        acc[0][4 * r + c] = __builtin_amdgcn_mfma_f32_16x16x4f32(xc[ks][c + dx - 1][r], af[g & 1], acc[0][4 * r + c], 0, 0, 0);
+                    }
+                acc[0][12] = __builtin_amdgcn_mfma_f32_16x16x4f32(bm[g & 1], af[g & 1], acc[0][12], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __builtin_amdgcn_s_setprio(2);
+        } else if constexpr (COL2) {
             // acc[ct][2 g + c] = fragment (column c, rows 16 g + q).  x0 / x1[ks][g]: columns 0 / 1 of row 16 g + q + dy, channel 4 ks + kk --
             // column 0 feeds (c 1, dx 0) and (c 0, dx 1), column 1 feeds (c 1, dx 1) and (c 0, dx 2).  Weights one group ahead as below; column 1
             // of a dy is read during its dx = 0 groups, column 0 of the next dy during this dy's dx = 2 groups (KS groups ahead of their use).
             constexpr int KS = CK / 4, NG = 9 * KS, MG = MT / 2;
-            const int base_cp = kk * C::PS + (wn * MT * C::RPF + q) * C::COLS;
+            const int base_cp = kk * PS + (wn * MT * C::RPF + q) * C::COLS;
             float af[2][CT], x0[KS][MG], x1[KS][MG];
             auto load_w = [&](int g, float (&wa)[CT]) {
                 const int tap = g / KS, ks = g % KS;
@@ -402,7 +471,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
             };
             auto load_col = [&](int dy, int ks, int c, float (&xa)[MG]) {
 #pragma unroll
-                for (int gq = 0; gq < MG; ++gq) xa[gq] = in_lds[base_cp + (4 * ks) * C::PS + (16 * gq + dy) * C::COLS + c];
+                for (int gq = 0; gq < MG; ++gq) xa[gq] = in_lds[base_cp + (4 * ks) * PS + (16 * gq + dy) * C::COLS + c];
             };
             __builtin_amdgcn_s_setprio(0);
             load_w(0, af[0]);
@@ -436,7 +505,7 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) wa[ct] = w_lds[base_w + (tap * CK + 4 * ks) * C::COTP + 16 * ct];
 #pragma unroll
-                for (int f = 0; f < MT; ++f) xa[f] = in_lds[base_in[dx] + (4 * ks) * C::PS + (f * C::RPF + dy) * C::COLS];
+                for (int f = 0; f < MT; ++f) xa[f] = in_lds[base_in[dx] + (4 * ks) * PS + (f * C::RPF + dy) * C::COLS];
             };
             __builtin_amdgcn_s_setprio(0);
             load_group(0, af[0], bf[0]);
@@ -454,7 +523,27 @@ __global__ __launch_bounds__(64 * WM * WN, (ConvCfg<CK, CT, WM, WN, MT, TW, 9>::
         }
         if (chunk == 0) CINE_STAMP(5);
     }
-    if constexpr (COLP) {
+    if constexpr (COL4) {
+        // back to the canonical slots: register j of fragment (c, r) in lane row kk is plane row 16 r + 4 kk + j of column c; the epilogue wants
+        // it in fragment 4 r + kk, lane row j, register c -- per (r, c) a 4 x 4 transpose between lane row and register.  permlane16_swap
+        // trades a register pair's index bit for lane bit 4 (j bit 0 <-> kk bit 0), permlane32_swap for lane bit 5 (j bit 1 <-> kk bit 1)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            f32x4 k[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const f32x4 p = acc[0][4 * r + c];
+                const auto u01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[0]), __float_as_uint(p[1]), false, false);
+                const auto u23 = __builtin_amdgcn_permlane16_swap(__float_as_uint(p[2]), __float_as_uint(p[3]), false, false);
+                const auto v02 = __builtin_amdgcn_permlane32_swap(u01[0], u23[0], false, false);
+                const auto v13 = __builtin_amdgcn_permlane32_swap(u01[1], u23[1], false, false);
+                k[0][c] = __uint_as_float(v02[0]); k[1][c] = __uint_as_float(v13[0]);
+                k[2][c] = __uint_as_float(v02[1]); k[3][c] = __uint_as_float(v13[1]);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[0][4 * r + i] = k[i];
+        }
+    } else if constexpr (COL2) {
         // back to the canonical slots: register j of fragment (c, g) in lane row kk is plane row 16 g + 4 kk + j of column c; the epilogue wants
         // fragment f, lane row kk', register j' = row 8 f + 2 kk' + j' / 2, column j' % 2.  With j = 2 h + b that is (kk bit 1, kk bit 0, h) ->
         // (f bit 0, kk' bit 1, kk' bit 0) = (kk bit 1 -> register pair, kk bit 0 -> lane bit 5, h -> lane bit 4): permlane16_swap trades h for
@@ -691,7 +780,8 @@ int launch_conv_plane(const ConvArgs& a, int ck, int ct, int wm, int wn, int mt,
     if (ck == CK_ && ct == CT_ && wm == WM_ && wn == WN_ && mt == MT_ && tw == TW_ && mode == MODE_ && (whole || !(NEEDWHOLE))) { \
         *handled = true;                                                                                                  \
         diag_count(D_CONV_PLANE);                                                                                         \
-        if (TW_ == 2 && !(g_plane_on & 8)) return launch_plane<CK_, CT_, WM_, WN_, MT_, TW_, MODE_, TW_ == 2>(p, a.n, st);  \
+        constexpr int COLP_ = TW_ == 2 || (TW_ == 4 && MT_ == 13 && WN_ == 1);                                            \
+        if (COLP_ && !(g_plane_on & 8)) return launch_plane<CK_, CT_, WM_, WN_, MT_, TW_, MODE_, COLP_>(p, a.n, st);       \
         return launch_plane<CK_, CT_, WM_, WN_, MT_, TW_, MODE_>(p, a.n, st);                                              \
     }
     CINE_PLANE_CASE(4, 1, 1, 4, 13, 16, 0, false)
@@ -734,7 +824,7 @@ int launch_conv_plane(const ConvArgs& a, int ck, int ct, int wm, int wn, int mt,
 extern "C" int cine_set_conv_plane(int on) {
     cine::set_wgrad_plane((on & 16) ? 0 : 1);       // bit 4 SET: the plane-wide weight gradients (training) on the general kernel
     cine::g_plane_on = on & 15;      // bit 0 plane-wide 3x3 convs, bit 1 transpose convs, bit 2 wide planes / volumes (7 = all, the default);
-                                     // bit 3 SET: the nine-tap sweep on the 2-wide planes
+                                     // bit 3 SET: the nine-tap sweep on the 2-wide planes and on the 4-wide <8, 1, 4, 1, 13, 4> shape
     return CINE_OK;
 }
 

@@ -777,7 +777,9 @@ int cine_pad2d(const float* x, float* out, long planes, int h, int w, int top, i
  * transpose convolutions, bit 2 the wide planes / volumes; a cleared bit routes that kind through the general kernel (the
  * bit-identity tests, A/B timing).  Bit 3 SET makes the plane-wide 3x3 convolutions of 2-wide planes (the U-Net bottleneck, the MWCNN's
  * coarsest scale) sweep all nine taps over fragments of 8 rows x both columns, the form before the column-pure sweep that skips the taps
- * which only read the zero halo column (bit-identical; 15 = every lean kernel in that older form).  Bit 4 SET routes the plane-wide weight gradients of training (grad_kernels.hip:
+ * which only read the zero halo column, and those of 4-wide planes with 33 .. 64 output rows (U-Net level 2: one wave per 52-row plane tile)
+ * sweep all nine taps over fragments of 4 rows x all four columns instead of 12 column-pure fragments of 16 rows + one canonical fragment
+ * (bit-identical; 15 = every lean kernel in that older form).  Bit 4 SET routes the plane-wide weight gradients of training (grad_kernels.hip:
  * wgrad_plane_kernel, also bit-identical) through the general weight-gradient kernel.  A setting of the CALLING THREAD (default 7
  * in every thread): it selects kernels for the launches that thread enqueues afterwards and changes no result but for that
  * summation order. */
