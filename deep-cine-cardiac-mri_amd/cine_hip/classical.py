@@ -85,11 +85,51 @@ def fista_momentum(iters: int) -> np.ndarray:
     return out
 
 
-def _no_grad_inputs(what: str = "kt_sparse_sense", **tensors) -> None:
+def _iters(what: str, iters) -> int:
+    if int(iters) < 1:
+        raise ValueError(f"{what}: iters = {iters}")
+    return int(iters)
+
+
+def _no_grad_inputs(what: str, **tensors) -> None:
     for name, v in tensors.items():
         if isinstance(v, torch.Tensor) and v.requires_grad:
             raise CineHipError(f"{what}: {name} requires grad, but the solver is not differentiable (it runs under torch.no_grad(), "
                                f"gradients through the iterations are not built); pass {name}.detach()")
+
+
+def _device_float(value, device) -> torch.Tensor:
+    """A float or a one-element device tensor as one device float."""
+    return value if isinstance(value, torch.Tensor) else torch.full((1,), float(value), device=device, dtype=torch.float32)
+
+
+def _setup(what: str, masked_kspace, mask, sens_maps, step, step_scale: Optional[float] = None):
+    """What the four solvers do once their inputs passed ``_no_grad_inputs`` and their own settings are validated: refuse CPU tensors,
+    then (acq, zf, mask_u8, step) with zf (b, t, 1, h, w, 2) the zero-filled image and ``step`` one device float --
+    ``default_step(sens_maps)`` for None (times ``step_scale`` where one is given), a float or a one-element device tensor as given.
+    Call it under ``torch.no_grad()``."""
+    if not all(isinstance(v, torch.Tensor) and v.is_cuda for v in (masked_kspace, sens_maps, mask)):
+        raise CineHipError(f"{what}: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
+    mask = ops.as_mask_u8(mask, masked_kspace)
+    acq = dc.Acquisition(masked_kspace, mask, sens_maps)
+    zf = acq.zero_filled()
+    if step is None:
+        step = default_step(sens_maps)
+        if step_scale is not None:
+            step = step_scale * step
+    return acq, zf, mask, _device_float(step, zf.device)
+
+
+def _weight(value, peak_fn) -> torch.Tensor:
+    """A regularisation weight as one device float: a one-element device tensor is absolute and used as given, a float is a fraction
+    of the device peak ``peak_fn()``."""
+    return value if isinstance(value, torch.Tensor) else peak_fn() * float(value)
+
+
+def _finish(x: torch.Tensor, cplx: bool) -> torch.Tensor:
+    """(b, t, 1, h, w, 2) -> (b, t, h, w, 2), or its magnitude (b, t, h, w)."""
+    x = x.squeeze(2)
+    return x if cplx else ops.complex_abs(x)
 
 
 def default_step(sens_maps: torch.Tensor) -> torch.Tensor:
@@ -120,43 +160,39 @@ def kt_sparse_sense(masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: 
     floats sum |x_{k+1} - x_k|^2, sum |x_{k+1}|^2, sum_f w_f |F_t x_{k+1}|, 0 per iteration.
     Not differentiable; raises ``CineHipError`` for CPU tensors (no fallback) and for an input that requires grad."""
     cplx = ops.complex_output(output)
-    _no_grad_inputs(masked_kspace=masked_kspace, sens_maps=sens_maps, lam=lam, step=step)
-    if not (isinstance(masked_kspace, torch.Tensor) and masked_kspace.is_cuda and isinstance(sens_maps, torch.Tensor) and sens_maps.is_cuda
-            and isinstance(mask, torch.Tensor) and mask.is_cuda):
-        raise CineHipError("kt_sparse_sense: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
+    _no_grad_inputs("kt_sparse_sense", masked_kspace=masked_kspace, sens_maps=sens_maps, lam=lam, step=step)
     with torch.no_grad():
-        mask = ops.as_mask_u8(mask, masked_kspace)
-        acq = dc.Acquisition(masked_kspace, mask, sens_maps)
-        zf = acq.zero_filled()                                       # (b, t, 1, h, w, 2)
-        dev = zf.device
-        if step is None:
-            step = default_step(sens_maps)
-        elif not isinstance(step, torch.Tensor):
-            step = torch.full((1,), float(step), device=dev, dtype=torch.float32)
-        if not isinstance(lam, torch.Tensor):
-            lam = temporal_peak(zf) * float(lam)
+        acq, zf, mask, step = _setup("kt_sparse_sense", masked_kspace, mask, sens_maps, step)      # ops.kt_fista refuses iters < 1
+        lam = _weight(lam, lambda: temporal_peak(zf))
         out = ops.kt_fista(zf, sens_maps, mask, step, lam, iters, penalise_dc=penalise_dc, sens_tiled=acq.tiled, record=record)
-        x, rec = out if record else (out, None)
-        x = x.squeeze(2)
-        x = x if cplx else ops.complex_abs(x)
-    return (x, rec) if record else x
+        out = list(out) if record else [out]
+        out[0] = _finish(out[0], cplx)
+    return tuple(out) if record else out[0]
 
 
-class KtSparseSense(nn.Module):
-    """``kt_sparse_sense`` as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(KtSparseSense(...).eval())``
-    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included.  The settings are the function's; the default ``lam`` is
-    untuned (see there).  Not differentiable."""
+class _Solver(nn.Module):
+    """One of the solvers above as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(KtSparseSense(...).eval())``
+    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included.  The settings are the function's, kept as attributes and
+    handed on by ``forward``; the default weights are untuned (see the function).  Not differentiable."""
+    solve = None                     # the function
+
+    def __init__(self, **settings):
+        super().__init__()
+        self._settings = tuple(settings)
+        for name, v in settings.items():
+            setattr(self, name, v)
+
+    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
+        return type(self).solve(masked_kspace, mask, sens_maps, output=output, **{name: getattr(self, name) for name in self._settings})
+
+
+class KtSparseSense(_Solver):
+    """``kt_sparse_sense`` as a module (see ``_Solver``); the default ``lam`` is untuned (see the function)."""
+    solve = staticmethod(kt_sparse_sense)
 
     def __init__(self, iters: int = 30, lam: Union[float, torch.Tensor] = 0.02, step: Optional[Union[float, torch.Tensor]] = None,
                  penalise_dc: bool = True):
-        super().__init__()
-        if int(iters) < 1:
-            raise ValueError(f"KtSparseSense: iters = {iters}")
-        self.iters, self.lam, self.step, self.penalise_dc = int(iters), lam, step, bool(penalise_dc)
-
-    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
-        return kt_sparse_sense(masked_kspace, mask, sens_maps, iters=self.iters, lam=self.lam, step=self.step, penalise_dc=self.penalise_dc,
-                               output=output)
+        super().__init__(iters=_iters("KtSparseSense", iters), lam=lam, step=step, penalise_dc=bool(penalise_dc))
 
 
 def casorati_sigma_max(zf: torch.Tensor) -> torch.Tensor:
@@ -187,47 +223,26 @@ def low_rank_plus_sparse(masked_kspace: torch.Tensor, mask: torch.Tensor, sens_m
     Not differentiable; raises ``CineHipError`` for CPU tensors (no fallback) and for an input that requires grad."""
     cplx = ops.complex_output(output)
     _no_grad_inputs("low_rank_plus_sparse", masked_kspace=masked_kspace, sens_maps=sens_maps, lam_l=lam_l, lam_s=lam_s, step=step)
-    if int(iters) < 1:
-        raise ValueError(f"low_rank_plus_sparse: iters = {iters}")
-    if not (isinstance(masked_kspace, torch.Tensor) and masked_kspace.is_cuda and isinstance(sens_maps, torch.Tensor) and sens_maps.is_cuda
-            and isinstance(mask, torch.Tensor) and mask.is_cuda):
-        raise CineHipError("low_rank_plus_sparse: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
+    iters = _iters("low_rank_plus_sparse", iters)
     with torch.no_grad():
-        mask = ops.as_mask_u8(mask, masked_kspace)
-        acq = dc.Acquisition(masked_kspace, mask, sens_maps)
-        zf = acq.zero_filled()                                       # (b, t, 1, h, w, 2)
-        dev = zf.device
-        if step is None:
-            step = 0.5 * default_step(sens_maps)
-        elif not isinstance(step, torch.Tensor):
-            step = torch.full((1,), float(step), device=dev, dtype=torch.float32)
-        if not isinstance(lam_l, torch.Tensor):
-            lam_l = casorati_sigma_max(zf) * float(lam_l)
-        if not isinstance(lam_s, torch.Tensor):
-            lam_s = temporal_peak(zf) * float(lam_s)
-        out = ops.ls_solve(zf, sens_maps, mask, step, lam_l, lam_s, int(iters), sens_tiled=acq.tiled, components=components, record=record)
+        acq, zf, mask, step = _setup("low_rank_plus_sparse", masked_kspace, mask, sens_maps, step, step_scale=0.5)
+        lam_l = _weight(lam_l, lambda: casorati_sigma_max(zf))
+        lam_s = _weight(lam_s, lambda: temporal_peak(zf))
+        out = ops.ls_solve(zf, sens_maps, mask, step, lam_l, lam_s, iters, sens_tiled=acq.tiled, components=components, record=record)
         out = list(out) if isinstance(out, tuple) else [out]
-        for i in range(3 if components else 1):
-            out[i] = out[i].squeeze(2)
-        out[0] = out[0] if cplx else ops.complex_abs(out[0])
+        out[0] = _finish(out[0], cplx)
+        if components:
+            out[1], out[2] = out[1].squeeze(2), out[2].squeeze(2)
     return tuple(out) if len(out) > 1 else out[0]
 
 
-class LowRankPlusSparse(nn.Module):
-    """``low_rank_plus_sparse`` as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(LowRankPlusSparse(...).eval())``
-    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included.  The settings are the function's; the default ``lam_l`` and
-    ``lam_s`` are untuned (see there).  Not differentiable."""
+class LowRankPlusSparse(_Solver):
+    """``low_rank_plus_sparse`` as a module (see ``_Solver``); the default ``lam_l`` and ``lam_s`` are untuned (see the function)."""
+    solve = staticmethod(low_rank_plus_sparse)
 
     def __init__(self, iters: int = 50, lam_l: Union[float, torch.Tensor] = 0.01, lam_s: Union[float, torch.Tensor] = 0.01,
                  step: Optional[Union[float, torch.Tensor]] = None):
-        super().__init__()
-        if int(iters) < 1:
-            raise ValueError(f"LowRankPlusSparse: iters = {iters}")
-        self.iters, self.lam_l, self.lam_s, self.step = int(iters), lam_l, lam_s, step
-
-    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
-        return low_rank_plus_sparse(masked_kspace, mask, sens_maps, iters=self.iters, lam_l=self.lam_l, lam_s=self.lam_s, step=self.step,
-                                    output=output)
+        super().__init__(iters=_iters("LowRankPlusSparse", iters), lam_l=lam_l, lam_s=lam_s, step=step)
 
 
 def tv_peaks(zf: torch.Tensor, periodic: bool = True):
@@ -269,60 +284,37 @@ def total_variation(masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: 
     Not differentiable; raises ``CineHipError`` for CPU tensors (no fallback) and for an input that requires grad."""
     cplx = ops.complex_output(output)
     _no_grad_inputs("total_variation", masked_kspace=masked_kspace, sens_maps=sens_maps, lam_t=lam_t, lam_s=lam_s, step=step, sigma=sigma)
-    if int(iters) < 1:
-        raise ValueError(f"total_variation: iters = {iters}")
-    terms = (0 if not isinstance(lam_t, torch.Tensor) and float(lam_t) == 0.0 else ops.TV_TEMPORAL) | \
+    iters = _iters("total_variation", iters)
+    terms =(0 if not isinstance(lam_t, torch.Tensor) and float(lam_t) == 0.0 else ops.TV_TEMPORAL) | \
             (0 if not isinstance(lam_s, torch.Tensor) and float(lam_s) == 0.0 else ops.TV_SPATIAL)
     if terms == 0:
         raise ValueError("total_variation: lam_t and lam_s are both 0, no term is left")
-    if not (isinstance(masked_kspace, torch.Tensor) and masked_kspace.is_cuda and isinstance(sens_maps, torch.Tensor) and sens_maps.is_cuda
-            and isinstance(mask, torch.Tensor) and mask.is_cuda):
-        raise CineHipError("total_variation: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
     with torch.no_grad():
-        mask = ops.as_mask_u8(mask, masked_kspace)
-        acq = dc.Acquisition(masked_kspace, mask, sens_maps)
-        zf = acq.zero_filled()                                       # (b, t, 1, h, w, 2)
-        dev = zf.device
-        if step is None:
-            step = default_step(sens_maps)
-        elif not isinstance(step, torch.Tensor):
-            step = torch.full((1,), float(step), device=dev, dtype=torch.float32)
+        acq, zf, mask, step = _setup("total_variation", masked_kspace, mask, sens_maps, step)
         if sigma is None:
             bound = 4.0 * bool(terms & ops.TV_TEMPORAL) + 8.0 * bool(terms & ops.TV_SPATIAL)
             sigma = (step * (2.0 * bound)).reciprocal()
-        elif not isinstance(sigma, torch.Tensor):
-            sigma = torch.full((1,), float(sigma), device=dev, dtype=torch.float32)
+        sigma = _device_float(sigma, zf.device)
         if not (isinstance(lam_t, torch.Tensor) and isinstance(lam_s, torch.Tensor)):
             peak_t, peak_s = tv_peaks(zf, periodic)
-            if not isinstance(lam_t, torch.Tensor):
-                lam_t = peak_t * float(lam_t) if terms & ops.TV_TEMPORAL else None
-            if not isinstance(lam_s, torch.Tensor):
-                lam_s = peak_s * float(lam_s) if terms & ops.TV_SPATIAL else None
-        out = ops.tv_solve(zf, sens_maps, mask, step, sigma, lam_t, lam_s, int(iters), terms=terms, periodic=periodic, sens_tiled=acq.tiled,
+            lam_t = _weight(lam_t, lambda: peak_t) if terms & ops.TV_TEMPORAL else None
+            lam_s = _weight(lam_s, lambda: peak_s) if terms & ops.TV_SPATIAL else None
+        out = ops.tv_solve(zf, sens_maps, mask, step, sigma, lam_t, lam_s, iters, terms=terms, periodic=periodic, sens_tiled=acq.tiled,
                            record=record, dual=dual)
         out = list(out) if isinstance(out, tuple) else [out]
-        out[0] = out[0].squeeze(2)
+        out[0] = _finish(out[0], cplx)
         if dual:
             out[1] = out[1].squeeze(3)
-        out[0] = out[0] if cplx else ops.complex_abs(out[0])
     return tuple(out) if len(out) > 1 else out[0]
 
 
-class TotalVariation(nn.Module):
-    """``total_variation`` as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(TotalVariation(...).eval())``
-    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included.  The settings are the function's; the default ``lam_t``
-    and ``lam_s`` are untuned (see there).  Not differentiable."""
+class TotalVariation(_Solver):
+    """``total_variation`` as a module (see ``_Solver``); the default ``lam_t`` and ``lam_s`` are untuned (see the function)."""
+    solve = staticmethod(total_variation)
 
     def __init__(self, iters: int = 50, lam_t: Union[float, torch.Tensor] = 0.02, lam_s: Union[float, torch.Tensor] = 0.01,
                  step: Optional[Union[float, torch.Tensor]] = None, sigma: Optional[Union[float, torch.Tensor]] = None, periodic: bool = True):
-        super().__init__()
-        if int(iters) < 1:
-            raise ValueError(f"TotalVariation: iters = {iters}")
-        self.iters, self.lam_t, self.lam_s, self.step, self.sigma, self.periodic = int(iters), lam_t, lam_s, step, sigma, bool(periodic)
-
-    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
-        return total_variation(masked_kspace, mask, sens_maps, iters=self.iters, lam_t=self.lam_t, lam_s=self.lam_s, step=self.step,
-                               sigma=self.sigma, periodic=self.periodic, output=output)
+        super().__init__(iters=_iters("TotalVariation", iters), lam_t=lam_t, lam_s=lam_s, step=step, sigma=sigma, periodic=bool(periodic))
 
 
 def llr_shifts(iters: int, block: int, seed: int = 0) -> np.ndarray:
@@ -343,9 +335,7 @@ def block_sigma_max(zf: torch.Tensor, block: int) -> torch.Tensor:
 
 def _llr_settings(what: str, iters, block, shifts):
     """(iters, block, the (iters, 2) int32 host array or None) of ``locally_low_rank`` / ``LocallyLowRank``, validated on the host."""
-    if int(iters) < 1:
-        raise ValueError(f"{what}: iters = {iters}")
-    iters, block = int(iters), int(block)
+    iters, block = _iters(what, iters), int(block)
     if not ops.LLR_MIN_BLOCK <= block <= ops.LLR_MAX_BLOCK:
         raise ValueError(f"{what}: block = {block} is outside {ops.LLR_MIN_BLOCK} .. {ops.LLR_MAX_BLOCK}")
     if shifts is None or (isinstance(shifts, str) and shifts == "fixed"):
@@ -381,38 +371,21 @@ def locally_low_rank(masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps:
     cplx = ops.complex_output(output)
     _no_grad_inputs("locally_low_rank", masked_kspace=masked_kspace, sens_maps=sens_maps, lam=lam, step=step)
     iters, block, host_shifts = _llr_settings("locally_low_rank", iters, block, shifts)
-    if not (isinstance(masked_kspace, torch.Tensor) and masked_kspace.is_cuda and isinstance(sens_maps, torch.Tensor) and sens_maps.is_cuda
-            and isinstance(mask, torch.Tensor) and mask.is_cuda):
-        raise CineHipError("locally_low_rank: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
     with torch.no_grad():
-        mask = ops.as_mask_u8(mask, masked_kspace)
-        acq = dc.Acquisition(masked_kspace, mask, sens_maps)
-        zf = acq.zero_filled()                                       # (b, t, 1, h, w, 2)
-        dev = zf.device
-        if step is None:
-            step = default_step(sens_maps)
-        elif not isinstance(step, torch.Tensor):
-            step = torch.full((1,), float(step), device=dev, dtype=torch.float32)
-        if not isinstance(lam, torch.Tensor):
-            lam = block_sigma_max(zf, block) * float(lam)
+        acq, zf, mask, step = _setup("locally_low_rank", masked_kspace, mask, sens_maps, step)
+        lam = _weight(lam, lambda: block_sigma_max(zf, block))
         out = ops.llr_solve(zf, sens_maps, mask, step, lam, block, iters, shifts=host_shifts, sens_tiled=acq.tiled, record=record)
-        x, rec, info = out if record else (out, None, None)
-        x = x.squeeze(2)
-        x = x if cplx else ops.complex_abs(x)
-    return (x, rec, info) if record else x
+        out = list(out) if record else [out]
+        out[0] = _finish(out[0], cplx)
+    return tuple(out) if record else out[0]
 
 
-class LocallyLowRank(nn.Module):
-    """``locally_low_rank`` as a module with CineNet's ``forward`` signature and no parameters: ``SlicePipeline(LocallyLowRank(...).eval())``
-    reconstructs slices in flight, raw input and ``sens_maps="espirit"`` included (a replayed graph replays the same shift sequence, which
-    is intended).  The settings are the function's; the default ``lam`` is untuned (see there).  Not differentiable."""
+class LocallyLowRank(_Solver):
+    """``locally_low_rank`` as a module (see ``_Solver``); a replayed graph replays the same shift sequence, which is intended.  The
+    default ``lam`` is untuned (see the function)."""
+    solve = staticmethod(locally_low_rank)
 
     def __init__(self, iters: int = 30, lam: Union[float, torch.Tensor] = 0.005, block: int = 8, shifts="random",
                  step: Optional[Union[float, torch.Tensor]] = None):
-        super().__init__()
-        self.iters, self.block, self.shifts = _llr_settings("LocallyLowRank", iters, block, shifts)
-        self.lam, self.step = lam, step
-
-    def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: torch.Tensor, output: str = "magnitude") -> torch.Tensor:
-        return locally_low_rank(masked_kspace, mask, sens_maps, iters=self.iters, lam=self.lam, block=self.block, shifts=self.shifts,
-                                step=self.step, output=output)
+        iters, block, shifts = _llr_settings("LocallyLowRank", iters, block, shifts)
+        super().__init__(iters=iters, lam=lam, block=block, shifts=shifts, step=step)

@@ -712,11 +712,55 @@ def kt_prox_pixels() -> int:
     return int(lib().cine_kt_prox_pixels())
 
 
-def _kt_scalar(v: torch.Tensor, name: str) -> torch.Tensor:
+def _scalar(v: torch.Tensor, name: str) -> torch.Tensor:
     v = _dev(v, name)
     if v.numel() != 1:
         raise ValueError(f"{name}: expected one float on the device, got shape {tuple(v.shape)}")
     return v
+
+
+def _frames_image(x: torch.Tensor, name: str, what: str):
+    _pair(x)
+    x = _dev(x, name)
+    if x.dim() not in (5, 6) or (x.dim() == 6 and x.shape[2] != 1):
+        raise ValueError(f"{what}: {name} {tuple(x.shape)} is not (b, t, [1,] h, w, 2)")
+    return x, (x.shape[0], x.shape[1], x.shape[-3], x.shape[-2])
+
+
+def _solve_operands(what: str, zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, iters: int):
+    """What the four solve wrappers take alike: zf (b, t, [1,] h, w, 2), sens (b, 1, c, h, w, 2), ``mask`` in either layout of
+    ``as_mask_u8`` and ``iters`` >= 1.  Returns (zf, sens, mask, (b, t, c, h, w), mask_w, iters), mask_w = 1 for a row mask, w otherwise."""
+    _pair(zf); _pair(sens)
+    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
+    if sens.dim() != 6:
+        raise ValueError(f"{what}: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
+    b, _, c, h, w, _ = sens.shape
+    t = zf.shape[1]
+    layout = mask_layout(mask, sens, t)
+    if zf.numel() != b * t * h * w * 2 or layout is None:
+        raise ValueError(f"{what}: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError(f"{what}: iters = {iters}")
+    return zf, sens, mask, (b, t, c, h, w), 1 if layout == "row" else w, iters
+
+
+def _prox_outputs(what: str, like: torch.Tensor, like_name: str, **outs):
+    """The optional pre-allocated outputs of a prox wrapper, in the order given: one that is passed must be a contiguous GPU tensor of
+    ``like``'s dtype and size, one that is None is allocated."""
+    for name, o in outs.items():
+        if o is not None and (not o.is_cuda or o.dtype != like.dtype or not o.is_contiguous() or o.numel() != like.numel()):
+            raise CineHipError(f"{what}: {name} must be a contiguous float32 GPU tensor of {like_name}'s size")
+    return [torch.empty_like(like) if o is None else o for o in outs.values()]
+
+
+def _prox_record(record: bool, device: torch.device, n: int, ws_bytes, *sizes):
+    """``record`` -> (rec, ws, nbytes) of a prox wrapper: the ``n`` device floats of the record and the workspace of the per-workgroup
+    records, ``ws_bytes(*sizes)`` bytes (asked for only when recording), or (None, None, 0)."""
+    if not record:
+        return None, None, 0
+    nbytes = ws_bytes(*sizes)
+    return torch.empty(n, device=device, dtype=torch.float32), _general_ws(nbytes, device), nbytes
 
 
 def kt_prox(z: torch.Tensor, g: torch.Tensor, xprev: torch.Tensor, step: torch.Tensor, thresh: torch.Tensor, beta: float = 0.0,
@@ -725,25 +769,13 @@ def kt_prox(z: torch.Tensor, g: torch.Tensor, xprev: torch.Tensor, step: torch.T
     znew = xnew + beta (xnew - xprev).  z, g, xprev: (b, t, [1,] h, w, 2); ``step``, ``thresh``: one device float each.  ``xnew`` / ``znew``:
     where to write (``znew`` may be ``z`` and ``xnew`` may be ``xprev``: in place); new tensors of z's shape by default.
     Returns (xnew, znew), with ``record`` (xnew, znew, rec) with rec the ``KT_REC`` device floats of the record."""
-    _pair(z)
-    z = _dev(z, "z"); g = _dev(g, "g"); xprev = _dev(xprev, "xprev")
-    step = _kt_scalar(step, "step"); thresh = _kt_scalar(thresh, "thresh")
-    if z.dim() not in (5, 6) or (z.dim() == 6 and z.shape[2] != 1):
-        raise ValueError(f"kt_prox: z {tuple(z.shape)} is not (b, t, [1,] h, w, 2)")
-    b, t, h, w = z.shape[0], z.shape[1], z.shape[-3], z.shape[-2]
+    z, (b, t, h, w) = _frames_image(z, "z", "kt_prox")
+    g = _dev(g, "g"); xprev = _dev(xprev, "xprev")
+    step = _scalar(step, "step"); thresh = _scalar(thresh, "thresh")
     if g.numel() != z.numel() or xprev.numel() != z.numel():
         raise ValueError(f"kt_prox: g {tuple(g.shape)} / xprev {tuple(xprev.shape)} do not match z {tuple(z.shape)}")
-    for o, name in ((xnew, "xnew"), (znew, "znew")):
-        if o is not None and (not o.is_cuda or o.dtype != z.dtype or not o.is_contiguous() or o.numel() != z.numel()):
-            raise CineHipError(f"kt_prox: {name} must be a contiguous float32 GPU tensor of z's size")
-    xnew = torch.empty_like(z) if xnew is None else xnew
-    znew = torch.empty_like(z) if znew is None else znew
-    rec = ws = None
-    nbytes = 0
-    if record:
-        rec = torch.empty(KT_REC, device=z.device, dtype=torch.float32)
-        nbytes = lib().cine_kt_prox_ws_bytes(b, t, h, w)
-        ws = _general_ws(nbytes, z.device)
+    xnew, znew = _prox_outputs("kt_prox", z, "z", xnew=xnew, znew=znew)
+    rec, ws, nbytes = _prox_record(record, z.device, KT_REC, lib().cine_kt_prox_ws_bytes, b, t, h, w)
     check(lib().cine_kt_prox(z.data_ptr(), g.data_ptr(), xprev.data_ptr(), step.data_ptr(), thresh.data_ptr(), float(beta), int(bool(penalise_dc)),
                              xnew.data_ptr(), znew.data_ptr(), _p(rec), b, t, h, w, _p(ws), nbytes, _stream()), "cine_kt_prox")
     return (xnew, znew, rec) if record else (xnew, znew)
@@ -755,20 +787,8 @@ def kt_fista(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: tor
     (1, 0, -1), then ``kt_prox``, per iteration; the momentum of ``classical.fista_momentum``).  zf (b, t, [1,] h, w, 2); sens (b, 1, c, h, w, 2);
     ``mask``: either layout of ``as_mask_u8``; ``step``, ``thresh``: one device float each.  Returns x in zf's shape, with ``record``
     (x, rec) with rec (iters, ``KT_REC``)."""
-    _pair(zf); _pair(sens)
-    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
-    step = _kt_scalar(step, "step"); thresh = _kt_scalar(thresh, "thresh")
-    if sens.dim() != 6:
-        raise ValueError(f"kt_fista: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
-    b, _, c, h, w, _ = sens.shape
-    t = zf.shape[1]
-    layout = mask_layout(mask, sens, t)
-    if zf.numel() != b * t * h * w * 2 or layout is None:
-        raise ValueError(f"kt_fista: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
-    iters = int(iters)
-    if iters < 1:
-        raise ValueError(f"kt_fista: iters = {iters}")
-    mask_w = 1 if layout == "row" else w
+    zf, sens, mask, (b, t, c, h, w), mask_w, iters = _solve_operands("kt_fista", zf, sens, mask, iters)
+    step = _scalar(step, "step"); thresh = _scalar(thresh, "thresh")
     x = torch.empty_like(zf)
     rec = torch.empty((iters, KT_REC), device=zf.device, dtype=torch.float32) if record else None
     nbytes = lib().cine_kt_fista_ws_bytes(b, t, c, h, w, mask_w, iters)
@@ -788,24 +808,16 @@ def ls_prox_pixels() -> int:
     return int(lib().cine_ls_prox_pixels())
 
 
-def _ls_image(x: torch.Tensor, name: str, what: str):
-    _pair(x)
-    x = _dev(x, name)
-    if x.dim() not in (5, 6) or (x.dim() == 6 and x.shape[2] != 1):
-        raise ValueError(f"{what}: {name} {tuple(x.shape)} is not (b, t, [1,] h, w, 2)")
-    return x, (x.shape[0], x.shape[1], x.shape[-3], x.shape[-2])
-
-
 def casorati_gram(a: torch.Tensor, g: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None) -> torch.Tensor:
     """cine_casorati_gram: the (b, t, t) complex128 Gram matrix of the (h w) x t Casorati matrix of v = a - step g (``g`` None: of ``a``),
     gram[i][j] = sum_pixels conj(v_i) v_j -- exact float32 products added in float64 in a fixed order; exactly Hermitian.  a, g:
     (b, t, [1,] h, w, 2); ``step``: one device float.  Returns (b, t, t, 2) float64."""
-    a, (b, t, h, w) = _ls_image(a, "a", "casorati_gram")
+    a, (b, t, h, w) = _frames_image(a, "a", "casorati_gram")
     if g is not None:
         g = _dev(g, "g")
         if g.numel() != a.numel() or step is None:
             raise ValueError(f"casorati_gram: g {tuple(g.shape)} does not match a {tuple(a.shape)}, or comes without a step")
-        step = _kt_scalar(step, "step")
+        step = _scalar(step, "step")
     gram = torch.empty((b, t, t, 2), device=a.device, dtype=torch.float64)
     nbytes = lib().cine_casorati_gram_ws_bytes(b, t, h, w)
     ws = _general_ws(nbytes, a.device)
@@ -821,8 +833,8 @@ def svt_weight(gram: torch.Tensor, thresh: torch.Tensor, step: Optional[torch.Te
     gram = _dev(gram, "gram", torch.float64)
     if gram.dim() != 4 or gram.shape[1] != gram.shape[2] or gram.shape[3] != 2:
         raise ValueError(f"svt_weight: gram {tuple(gram.shape)} is not (b, t, t, 2)")
-    thresh = _kt_scalar(thresh, "thresh")
-    step = None if step is None else _kt_scalar(step, "step")
+    thresh = _scalar(thresh, "thresh")
+    step = None if step is None else _scalar(step, "step")
     b, t = gram.shape[0], gram.shape[1]
     weight = torch.empty((b, t, t, 2), device=gram.device, dtype=torch.float32)
     info = torch.empty((b, LS_INFO), device=gram.device, dtype=torch.float64)
@@ -836,23 +848,14 @@ def ls_prox(l: torch.Tensor, s: torch.Tensor, g: torch.Tensor, weight: torch.Ten
     step thresh_s), xsum = lnew + snew.  l, s, g: (b, t, [1,] h, w, 2); ``weight``: ``svt_weight``'s W; ``step``, ``thresh_s``: one device
     float each.  ``lnew`` / ``snew``: where to write (``lnew`` may be ``l`` and ``snew`` may be ``s``: in place); new tensors by default.
     Returns (lnew, snew, xsum), with ``record`` also rec, the ``LS_REC`` device floats of the record (column 3 is 0 here)."""
-    l, (b, t, h, w) = _ls_image(l, "l", "ls_prox")
+    l, (b, t, h, w) = _frames_image(l, "l", "ls_prox")
     s = _dev(s, "s"); g = _dev(g, "g"); weight = _dev(weight, "weight")
-    step = _kt_scalar(step, "step"); thresh_s = _kt_scalar(thresh_s, "thresh_s")
+    step = _scalar(step, "step"); thresh_s = _scalar(thresh_s, "thresh_s")
     if s.numel() != l.numel() or g.numel() != l.numel() or weight.numel() != b * t * t * 2:
         raise ValueError(f"ls_prox: s {tuple(s.shape)} / g {tuple(g.shape)} / weight {tuple(weight.shape)} do not match l {tuple(l.shape)}")
-    for o, name in ((lnew, "lnew"), (snew, "snew")):
-        if o is not None and (not o.is_cuda or o.dtype != l.dtype or not o.is_contiguous() or o.numel() != l.numel()):
-            raise CineHipError(f"ls_prox: {name} must be a contiguous float32 GPU tensor of l's size")
-    lnew = torch.empty_like(l) if lnew is None else lnew
-    snew = torch.empty_like(l) if snew is None else snew
+    lnew, snew = _prox_outputs("ls_prox", l, "l", lnew=lnew, snew=snew)
     xsum = torch.empty_like(l)
-    rec = ws = None
-    nbytes = 0
-    if record:
-        rec = torch.empty(LS_REC, device=l.device, dtype=torch.float32)
-        nbytes = lib().cine_ls_prox_ws_bytes(b, t, h, w)
-        ws = _general_ws(nbytes, l.device)
+    rec, ws, nbytes = _prox_record(record, l.device, LS_REC, lib().cine_ls_prox_ws_bytes, b, t, h, w)
     check(lib().cine_ls_prox(l.data_ptr(), s.data_ptr(), g.data_ptr(), weight.data_ptr(), step.data_ptr(), thresh_s.data_ptr(), lnew.data_ptr(),
                              snew.data_ptr(), xsum.data_ptr(), _p(rec), b, t, h, w, _p(ws), nbytes, _stream()), "cine_ls_prox")
     return (lnew, snew, xsum, rec) if record else (lnew, snew, xsum)
@@ -865,20 +868,8 @@ def ls_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: tor
     either layout of ``as_mask_u8``; ``step``, ``thresh_l``, ``thresh_s``: one device float each.  Returns x = L + S in zf's shape; with
     ``components`` (x, L, S); with ``record`` also rec (iters, ``LS_REC``) float32 and resid (iters,) float64, the worst Jacobi residual of
     each iteration."""
-    _pair(zf); _pair(sens)
-    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
-    step = _kt_scalar(step, "step"); thresh_l = _kt_scalar(thresh_l, "thresh_l"); thresh_s = _kt_scalar(thresh_s, "thresh_s")
-    if sens.dim() != 6:
-        raise ValueError(f"ls_solve: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
-    b, _, c, h, w, _ = sens.shape
-    t = zf.shape[1]
-    layout = mask_layout(mask, sens, t)
-    if zf.numel() != b * t * h * w * 2 or layout is None:
-        raise ValueError(f"ls_solve: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
-    iters = int(iters)
-    if iters < 1:
-        raise ValueError(f"ls_solve: iters = {iters}")
-    mask_w = 1 if layout == "row" else w
+    zf, sens, mask, (b, t, c, h, w), mask_w, iters = _solve_operands("ls_solve", zf, sens, mask, iters)
+    step = _scalar(step, "step"); thresh_l = _scalar(thresh_l, "thresh_l"); thresh_s = _scalar(thresh_s, "thresh_s")
     x = torch.empty_like(zf)
     lo = torch.empty_like(zf) if components else None
     so = torch.empty_like(zf) if components else None
@@ -925,29 +916,24 @@ def llr_prox(x: torch.Tensor, g: Optional[torch.Tensor], step: Optional[torch.Te
     (b, t, [1,] h, w, 2); ``step``, ``thresh``: one device float each.  ``xnew``: where to write (may be ``x``: in place); a new tensor by
     default.  ``image`` False: no image is written at all and (rec, info) is returned -- how ``classical.block_sigma_max`` is formed.
     Returns xnew, with ``record`` (xnew, rec, info): rec the ``LLR_REC`` device floats, info the ``LLR_INFO`` device doubles."""
-    x, (b, t, h, w) = _ls_image(x, "x", "llr_prox")
+    x, (b, t, h, w) = _frames_image(x, "x", "llr_prox")
     block = _llr_block(block, "llr_prox")
     sh, sw = (int(v) for v in shift)
     if not (0 <= sh < block and 0 <= sw < block):
         raise ValueError(f"llr_prox: shift {(sh, sw)} is outside [0, {block})")
-    thresh = _kt_scalar(thresh, "thresh")
-    step = None if step is None else _kt_scalar(step, "step")
+    thresh = _scalar(thresh, "thresh")
+    step = None if step is None else _scalar(step, "step")
     if g is not None:
         g = _dev(g, "g")
         if g.numel() != x.numel() or step is None:
             raise ValueError(f"llr_prox: g {tuple(g.shape)} does not match x {tuple(x.shape)}, or comes without a step")
-    if xnew is not None and (not image or not xnew.is_cuda or xnew.dtype != x.dtype or not xnew.is_contiguous() or xnew.numel() != x.numel()):
-        raise CineHipError("llr_prox: xnew must be a contiguous float32 GPU tensor of x's size (and image must be on)")
-    if image and xnew is None:
-        xnew = torch.empty_like(x)
+    if xnew is not None and not image:
+        raise CineHipError("llr_prox: xnew is given, but image is off")
+    if image:
+        xnew, = _prox_outputs("llr_prox", x, "x", xnew=xnew)
     record = record or not image
-    rec = info = ws = None
-    nbytes = 0
-    if record:
-        rec = torch.empty(LLR_REC, device=x.device, dtype=torch.float32)
-        info = torch.empty(LLR_INFO, device=x.device, dtype=torch.float64)
-        nbytes = lib().cine_llr_prox_ws_bytes(b, t, h, w, block, sh, sw)
-        ws = _general_ws(nbytes, x.device)
+    rec, ws, nbytes = _prox_record(record, x.device, LLR_REC, lib().cine_llr_prox_ws_bytes, b, t, h, w, block, sh, sw)
+    info = torch.empty(LLR_INFO, device=x.device, dtype=torch.float64) if record else None
     check(lib().cine_llr_prox(x.data_ptr(), _p(g), _p(step), thresh.data_ptr(), block, sh, sw, _p(xnew), _p(rec), _p(info), b, t, h, w,
                               _p(ws), nbytes, _stream()), "cine_llr_prox")
     if not image:
@@ -963,22 +949,10 @@ def llr_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, step: to
     or an (iters, 2) integer HOST array with entries in [0, block) -- it is read during the call, so a captured graph replays the shifts it
     was captured with.  Returns x in zf's shape, with ``record`` (x, rec, info) with rec (iters, ``LLR_REC``) float32 and info
     (iters, ``LLR_INFO``) float64."""
-    _pair(zf); _pair(sens)
-    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
-    step = _kt_scalar(step, "step"); thresh = _kt_scalar(thresh, "thresh")
-    if sens.dim() != 6:
-        raise ValueError(f"llr_solve: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
-    b, _, c, h, w, _ = sens.shape
-    t = zf.shape[1]
-    layout = mask_layout(mask, sens, t)
-    if zf.numel() != b * t * h * w * 2 or layout is None:
-        raise ValueError(f"llr_solve: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
-    iters = int(iters)
-    if iters < 1:
-        raise ValueError(f"llr_solve: iters = {iters}")
+    zf, sens, mask, (b, t, c, h, w), mask_w, iters = _solve_operands("llr_solve", zf, sens, mask, iters)
+    step = _scalar(step, "step"); thresh = _scalar(thresh, "thresh")
     block = _llr_block(block, "llr_solve")
     host = None if shifts is None else llr_shift_array(shifts, iters, block, "llr_solve")
-    mask_w = 1 if layout == "row" else w
     x = torch.empty_like(zf)
     rec = torch.empty((iters, LLR_REC), device=zf.device, dtype=torch.float32) if record else None
     info = torch.empty((iters, LLR_INFO), device=zf.device, dtype=torch.float64) if record else None
@@ -1025,26 +999,19 @@ def tv_pd_step(x: torch.Tensor, g: torch.Tensor, p: torch.Tensor, tau: torch.Ten
     2 spatial, 3 both; the planes of a term that is off are neither read nor written (a ``pnew`` made here holds zeros there).
     ``xnew`` / ``pnew``: where to write; never an operand -- workgroups read across each other's seams.
     Returns (xnew, pnew), with ``record`` (xnew, pnew, rec) with rec the ``TV_REC`` device floats of the record."""
-    x, (b, t, h, w) = _ls_image(x, "x", "tv_pd_step")
+    x, (b, t, h, w) = _frames_image(x, "x", "tv_pd_step")
     terms = _tv_terms(terms, "tv_pd_step")
     g = _dev(g, "g"); p = _tv_dual(p, "p", "tv_pd_step", x)
-    tau = _kt_scalar(tau, "tau"); sigma = _kt_scalar(sigma, "sigma")
-    lam_t = _kt_scalar(lam_t, "lam_t") if terms & TV_TEMPORAL else None
-    lam_s = _kt_scalar(lam_s, "lam_s") if terms & TV_SPATIAL else None
+    tau = _scalar(tau, "tau"); sigma = _scalar(sigma, "sigma")
+    lam_t = _scalar(lam_t, "lam_t") if terms & TV_TEMPORAL else None
+    lam_s = _scalar(lam_s, "lam_s") if terms & TV_SPATIAL else None
     if g.numel() != x.numel():
         raise ValueError(f"tv_pd_step: g {tuple(g.shape)} does not match x {tuple(x.shape)}")
-    for o, name, n in ((xnew, "xnew", x.numel()), (pnew, "pnew", p.numel())):
-        if o is not None and (not o.is_cuda or o.dtype != x.dtype or not o.is_contiguous() or o.numel() != n):
-            raise CineHipError(f"tv_pd_step: {name} must be a contiguous float32 GPU tensor of the size of its operand")
-    xnew = torch.empty_like(x) if xnew is None else xnew
-    if pnew is None:
-        pnew = torch.empty_like(p) if terms == 3 else torch.zeros_like(p)
-    rec = ws = None
-    nbytes = 0
-    if record:
-        rec = torch.empty(TV_REC, device=x.device, dtype=torch.float32)
-        nbytes = lib().cine_tv_pd_ws_bytes(b, t, h, w)
-        ws = _general_ws(nbytes, x.device)
+    xnew, = _prox_outputs("tv_pd_step", x, "x", xnew=xnew)
+    if pnew is None and terms != 3:
+        pnew = torch.zeros_like(p)
+    pnew, = _prox_outputs("tv_pd_step", p, "p", pnew=pnew)
+    rec, ws, nbytes = _prox_record(record, x.device, TV_REC, lib().cine_tv_pd_ws_bytes, b, t, h, w)
     check(lib().cine_tv_pd_step(x.data_ptr(), g.data_ptr(), p.data_ptr(), tau.data_ptr(), sigma.data_ptr(), _p(lam_t), _p(lam_s), terms,
                                 int(bool(periodic)), xnew.data_ptr(), pnew.data_ptr(), _p(rec), b, t, h, w, _p(ws), nbytes, _stream()),
           "cine_tv_pd_step")
@@ -1059,23 +1026,11 @@ def tv_solve(zf: torch.Tensor, sens: torch.Tensor, mask: torch.Tensor, tau: torc
     ``as_mask_u8``; ``tau``, ``sigma``, ``lam_t``, ``lam_s``: one device float each (the ``lam`` of a term that is off may be None).
     Returns x in zf's shape; with ``dual`` also the final p, (3,) + zf's shape, zeros in the planes of a term that is off; with ``record``
     also rec (iters, ``TV_REC``).  The order of the results: x, [p,] [rec]."""
-    _pair(zf); _pair(sens)
-    zf = _dev(zf, "zero-filled image"); sens = _dev(sens, "sens_maps"); mask = _dev(mask, "mask", torch.uint8)
+    zf, sens, mask, (b, t, c, h, w), mask_w, iters = _solve_operands("tv_solve", zf, sens, mask, iters)
     terms = _tv_terms(terms, "tv_solve")
-    tau = _kt_scalar(tau, "tau"); sigma = _kt_scalar(sigma, "sigma")
-    lam_t = _kt_scalar(lam_t, "lam_t") if terms & TV_TEMPORAL else None
-    lam_s = _kt_scalar(lam_s, "lam_s") if terms & TV_SPATIAL else None
-    if sens.dim() != 6:
-        raise ValueError(f"tv_solve: sens_maps {tuple(sens.shape)} is not (b, 1, c, h, w, 2)")
-    b, _, c, h, w, _ = sens.shape
-    t = zf.shape[1]
-    layout = mask_layout(mask, sens, t)
-    if zf.numel() != b * t * h * w * 2 or layout is None:
-        raise ValueError(f"tv_solve: image {tuple(zf.shape)} / mask {tuple(mask.shape)} do not match sens_maps {tuple(sens.shape)}")
-    iters = int(iters)
-    if iters < 1:
-        raise ValueError(f"tv_solve: iters = {iters}")
-    mask_w = 1 if layout == "row" else w
+    tau = _scalar(tau, "tau"); sigma = _scalar(sigma, "sigma")
+    lam_t = _scalar(lam_t, "lam_t") if terms & TV_TEMPORAL else None
+    lam_s = _scalar(lam_s, "lam_s") if terms & TV_SPATIAL else None
     x = torch.empty_like(zf)
     p_out = torch.empty((3,) + tuple(zf.shape), device=zf.device, dtype=zf.dtype) if dual else None
     rec = torch.empty((iters, TV_REC), device=zf.device, dtype=torch.float32) if record else None

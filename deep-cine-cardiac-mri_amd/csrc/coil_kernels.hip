@@ -30,6 +30,7 @@
 #include "common.h"
 #include "conv_src.h"
 #include "ls_jacobi.h"
+#include "solve.h"                   // large_lds_opt_in
 
 namespace cine {
 
@@ -554,7 +555,7 @@ int coil_matrix_run(const char* what, bool whitened, const double* gram, const d
     if (lds >= 64 * 1024) {
         static std::once_flag once[2][64];
         static hipError_t status[2][64];
-        if (int e = ls_large_lds(reinterpret_cast<const void*>(kern), "coil_matrix_kernel", once[whitened], status[whitened])) return e;
+        if (int e = large_lds_opt_in(reinterpret_cast<const void*>(kern), "coil_matrix_kernel", once[whitened], status[whitened])) return e;
     }
     CoilMatrixArgs a{};
     a.gram = reinterpret_cast<const double2*>(gram); a.whitener = reinterpret_cast<const double2*>(whitener);

@@ -17,14 +17,12 @@
 //                      its pixels is written and tiles do not share pixels, so xnew may be x.
 //                      LDS: 32 t^2 (G and V) + 6 KiB (rotations, reductions) + 8 t (S + 1) (tile); see llr_plan.
 //   llr_record_kernel  one 64-byte record per workgroup behind a header that holds their number -> rec and info, in float64 in a fixed order.
-#include <cstdint>
-#include <mutex>
-#include <string>
-#include "common.h"
+#include "solve.h"
 #include "ls_jacobi.h"
 
 namespace cine {
 
+static_assert(kLsThreads == kSolveThreads, "block_sums is written for the workgroup of the Jacobi kernels");
 constexpr int kLlrMinBlock = 2, kLlrMaxBlock = 16;
 constexpr int kLlrGramItems = (kLsMaxT * (kLsMaxT + 1) / 2 + kLsThreads - 1) / kLsThreads;     // Gram entries per thread at t = 64
 constexpr int kLlrWItems = kLsMaxT * kLsMaxT / kLsThreads;                                     // entries of W per thread at t = 64
@@ -47,7 +45,7 @@ __device__ __forceinline__ void llr_stage(const LlrArgs& a, cf* tile, int ld, lo
         const int r = p / bw, c = p - r * bw;
         const long q = base + (long)f * HW + (long)r * a.W + c;
         cf v = a.x[q];
-        if (a.g) v = ls_v(v, a.g[q], step);
+        if (a.g) v = solve_v(v, a.g[q], step);
         tile[f * ld + s] = v;
     }
 }
@@ -212,15 +210,13 @@ __global__ __launch_bounds__(kLsThreads) void llr_prox_kernel(LlrArgs a) {
         }
     }
     if (a.part) {                                             // one record per workgroup; llr_record_kernel adds them in a fixed order
-        float* rf = reinterpret_cast<float*>(red);            // [2][kLsThreads / 64]
-        const float v0 = ls_wave_sum(s_dx), v1 = ls_wave_sum(s_x2);
-        if ((tid & 63) == 0) { rf[tid >> 6] = v0; rf[4 + (tid >> 6)] = v1; }
-        __syncthreads();
+        float s[2] = {s_dx, s_x2};
+        block_sums(s, reinterpret_cast<float*>(red), tid);
         if (tid == 0) {
             const long wg = (long)blockIdx.y * gridDim.x + blockIdx.x;
             double* o = a.part + (1 + wg) * kLlrRecord;
-            o[0] = (double)((rf[0] + rf[1]) + (rf[2] + rf[3]));
-            o[1] = (double)((rf[4] + rf[5]) + (rf[6] + rf[7]));
+            o[0] = (double)s[0];
+            o[1] = (double)s[1];
             o[2] = nuc; o[3] = smax;
             o[4] = diag > 0.0 ? off / diag : off;
             o[5] = (double)sweeps;
@@ -297,7 +293,7 @@ static long llr_blocks_along(int n, int block, int shift) { return ((long)n + sh
 static int llr_prepare(int t, int block) {
     static std::once_flag once[64];
     static hipError_t status[64];
-    return llr_plan(t, block).large ? ls_large_lds(reinterpret_cast<const void*>(llr_prox_kernel), "llr_prox_kernel", once, status) : CINE_OK;
+    return llr_plan(t, block).large ? large_lds_opt_in(reinterpret_cast<const void*>(llr_prox_kernel), "llr_prox_kernel", once, status) : CINE_OK;
 }
 
 // the limits both entry points share; shifts are checked by the caller
@@ -371,7 +367,7 @@ extern "C" int cine_llr_prox(const float* x, const float* g, const float* step_d
     }
     CINE_REQUIRE(!info || (reinterpret_cast<uintptr_t>(info) & 7u) == 0, CINE_EINVAL, "%s: info must be 8-byte aligned", what);
     if (records) {
-        CINE_REQUIRE(ls_aligned16(ws), CINE_EINVAL, "%s: ws must be 16-byte aligned", what);
+        CINE_REQUIRE(solve_aligned16(ws), CINE_EINVAL, "%s: ws must be 16-byte aligned", what);
         const size_t need = cine_llr_prox_ws_bytes(b, t, h, w, block, shift_h, shift_w);
         CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
     }
@@ -383,15 +379,19 @@ extern "C" int cine_llr_prox(const float* x, const float* g, const float* step_d
 }
 
 namespace {
-// workspace of the solve, each part on a 256-byte boundary: [operator scratch | g | iters rows of records, each for the worst case over all shifts]
-struct LlrSolveLayout { size_t op, img, row, total; };
+// workspace of the solve: [operator scratch | g | iters rows of records, each for the worst case over all shifts]
+struct LlrSolveWs { size_t op_bytes, total; long stride; void* op; float* g; double* part; };      // stride: doubles per row of records
 
-LlrSolveLayout llr_solve_layout(int b, int t, int c, int h, int w, int mask_w, int block, int iters) {
-    LlrSolveLayout y{};
-    y.op = ls_align(mask_w == 1 ? cine_image_dc_ws_bytes(b, t, c, h, w) : cine_image_dc_general_ws_bytes(b, t, c, h, w));
-    y.img = ls_align((size_t)b * t * h * w * sizeof(cf));
-    y.row = llr_part_bytes(llr_blocks_along(h, block, block - 1) * llr_blocks_along(w, block, block - 1), b);
-    y.total = y.op + y.img + (size_t)iters * y.row;
+LlrSolveWs llr_solve_ws(void* ws, int b, int t, int c, int h, int w, int mask_w, int block, int iters) {
+    LlrSolveWs y{};
+    WsCursor at{static_cast<unsigned char*>(ws)};
+    const size_t row = llr_part_bytes(llr_blocks_along(h, block, block - 1) * llr_blocks_along(w, block, block - 1), b);
+    y.stride = (long)(row / sizeof(double));
+    y.op_bytes = dc_ws_bytes(mask_w, b, t, c, h, w);
+    y.op = y.op_bytes ? at.take<void>(y.op_bytes) : nullptr;
+    y.g = at.take<float>((size_t)b * t * h * w * sizeof(cf));
+    y.part = at.take<double>((size_t)iters * row);
+    y.total = at.end;
     return y;
 }
 }  // namespace
@@ -399,7 +399,7 @@ LlrSolveLayout llr_solve_layout(int b, int t, int c, int h, int w, int mask_w, i
 extern "C" size_t cine_llr_solve_ws_bytes(int b, int t, int c, int h, int w, int mask_w, int block, int iters) {
     if (b <= 0 || b > 65535 || t < 2 || t > kLsMaxT || c <= 0 || h <= 0 || w <= 0 || iters <= 0 || block < kLlrMinBlock || block > kLlrMaxBlock)
         return 0;
-    return llr_solve_layout(b, t, c, h, w, mask_w, block, iters).total;
+    return llr_solve_ws(nullptr, b, t, c, h, w, mask_w, block, iters).total;
 }
 
 extern "C" int cine_llr_solve(float* x, const float* zf, const float* sens, const float* sens_tiled, const uint8_t* mask, int mask_w,
@@ -416,46 +416,27 @@ extern "C" int cine_llr_solve(float* x, const float* zf, const float* sens, cons
                          what, shifts[2 * k], shifts[2 * k + 1], k, block);
     }
     {
-        const void* ins[7] = {zf, sens, sens_tiled, mask, step_dev, thresh_dev, ws};
-        const void* outs[3] = {x, rec, info};
-        bool ok = true;
-        for (int i = 0; i < 3; ++i) {
-            if (!outs[i]) continue;
-            for (int j = 0; j < 7; ++j) ok = ok && outs[i] != ins[j];
-            for (int j = 0; j < i; ++j) ok = ok && outs[i] != outs[j];
-        }
-        for (int j = 0; j < 6; ++j) ok = ok && ws != ins[j];
-        CINE_REQUIRE(ok, CINE_EINVAL, "%s: x, rec, info and ws must not alias an operand or each other", what);
+        const void* const outs[] = {x, rec, info};
+        const void* const ins[] = {zf, sens, sens_tiled, mask, step_dev, thresh_dev};
+        CINE_REQUIRE(solve_no_alias(outs, ins, ws), CINE_EINVAL, "%s: x, rec, info and ws must not alias an operand or each other", what);
     }
-    CINE_REQUIRE(ls_aligned16(ws), CINE_EINVAL, "%s: ws must be 16-byte aligned", what);
+    CINE_REQUIRE(solve_aligned16(ws), CINE_EINVAL, "%s: ws must be 16-byte aligned", what);
     CINE_REQUIRE(!info || (reinterpret_cast<uintptr_t>(info) & 7u) == 0, CINE_EINVAL, "%s: info must be 8-byte aligned", what);
     const size_t need = cine_llr_solve_ws_bytes(b, t, c, h, w, mask_w, block, iters);
     CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
-    const bool row = mask_w == 1;
-    const size_t op_bytes = row ? cine_image_dc_ws_bytes(b, t, c, h, w) : cine_image_dc_general_ws_bytes(b, t, c, h, w);
-    const LlrSolveLayout y = llr_solve_layout(b, t, c, h, w, mask_w, block, iters);
-    unsigned char* at = reinterpret_cast<unsigned char*>(ws);
-    void* op_ws = op_bytes ? at : nullptr;                     at += y.op;
-    float* g = reinterpret_cast<float*>(at);                   at += y.img;
-    double* part = reinterpret_cast<double*>(at);
-    const long stride = (long)(y.row / sizeof(double));
+    const LlrSolveWs y = llr_solve_ws(ws, b, t, c, h, w, mask_w, block, iters);
     const bool records = rec || info;
     hipStream_t st = as_stream(stream);
     for (int k = 0; k < iters; ++k) {
         const float* xk = k == 0 ? zf : x;          // x_0 = zf without a copy; from then on the prox works in place
-        const int e = row ? cine_image_dc_t(xk, sens, sens_tiled, zf, mask, nullptr, 1.f, 0.f, -1.f, g, b, t, c, h, w, 0, op_ws, op_bytes, stream)
-                          : cine_image_dc_general(xk, sens, zf, mask, nullptr, 1.f, 0.f, -1.f, g, b, t, c, h, w, 0, op_ws, op_bytes, stream);
-        if (e) {                                    // at k == 0 nothing has been launched yet: the operator's own refusal of a size
-            const std::string why = cine_last_error();
-            set_error("%s: %s", what, why.c_str());
-            return e;
-        }
+        if (int e = solve_gradient(what, xk, zf, sens, sens_tiled, mask, mask_w, y.g, b, t, c, h, w, y.op, y.op_bytes, stream)) return e;
         if (k == 0) {                               // the opt-in only after the operator has accepted the sizes
-            if (int e2 = llr_prepare(t, block)) return e2;
+            if (int e = llr_prepare(t, block)) return e;
         }
         const int sh = shifts ? shifts[2 * k] : 0, sw = shifts ? shifts[2 * k + 1] : 0;
-        if (int e2 = llr_prox_launch(xk, g, step_dev, thresh_dev, block, sh, sw, x, records ? part + (size_t)k * stride : nullptr, b, t, h, w, st))
-            return e2;
+        if (int e = llr_prox_launch(xk, y.g, step_dev, thresh_dev, block, sh, sw, x, records ? y.part + (size_t)k * y.stride : nullptr,
+                                    b, t, h, w, st))
+            return e;
     }
-    return records ? llr_record_launch(part, stride, rec, info, iters, st) : CINE_OK;
+    return records ? llr_record_launch(y.part, y.stride, rec, info, iters, st) : CINE_OK;
 }

@@ -1,11 +1,8 @@
 // ls_jacobi.h -- what the two singular-value-thresholding files share (ls_kernels.hip: one Casorati matrix per batch element;
-// llr_kernels.hip: one per spatial block): the limits, v = a - step g, the upper-triangle indexing of a Gram matrix, and the cyclic
-// Jacobi eigensolver for a complex Hermitian matrix in LDS.
+// llr_kernels.hip: one per spatial block) and the coil-compression matrix (coil_kernels.hip): the limits, the upper-triangle indexing of
+// a Gram matrix, and the cyclic Jacobi eigensolver for a complex Hermitian matrix in LDS.
 #pragma once
-#include <cstdint>
-#include <mutex>
 #include "common.h"
-#include "fft_core.h"
 
 namespace cine {
 
@@ -15,15 +12,6 @@ constexpr int kLsMaxSweeps = 40;
 constexpr double kLsJacobiTol = 1e-14;
 constexpr int kLsRotDoubles = (kLsMaxT / 2) * 8;            // ls_jacobi's rot: c, s, e^{i phi}, the new diagonal pair, on / off per pair
 constexpr int kLsRedDoubles = 2 * kLsThreads;               // ls_jacobi's red
-
-// v = a - step g in float32: ONE expression for the Gram matrix and the prox, so that both see the same v
-__device__ __forceinline__ cf ls_v(cf a, cf g, float step) { return mk(fmaf(-step, g.x, a.x), fmaf(-step, g.y, a.y)); }
-
-__device__ __forceinline__ float ls_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __host__ __device__ __forceinline__ int ls_row_start(int i, int t) { return i * t - i * (i - 1) / 2; }
 
@@ -139,19 +127,5 @@ __device__ __forceinline__ int ls_jacobi(double2* A, double2* V, double* rot, do
     }
     return sweeps;
 }
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device: raise it once per (kernel, device) and keep the result
-static int ls_large_lds(const void* kern, const char* what, std::once_flag* once, hipError_t* status) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    CINE_REQUIRE(dev >= 0 && dev < 64, CINE_EUNSUPPORTED, "%s: device index %d", what, dev);
-    std::call_once(once[dev], [&] { status[dev] = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-    CINE_REQUIRE(status[dev] == hipSuccess, CINE_EHIP, "%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", what, hipGetErrorString(status[dev]));
-    return CINE_OK;
-}
-
-static bool ls_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-static size_t ls_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace cine

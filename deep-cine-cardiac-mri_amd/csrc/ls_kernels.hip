@@ -18,16 +18,12 @@
 //                        ls_jacobi.h, which llr_kernels.hip runs per spatial block.
 //   ls_prox_kernel       one workgroup = kLsPix consecutive pixels, all frames: W in LDS, L' = v_L W, then the W region is reused for the
 //                        twiddles and the tile for the temporal prox of kt_prox_kernel; 64 KiB of LDS at t = 64, no scratch.
-#include <cstdint>
-#include <mutex>
-#include <string>
-#include "common.h"
-#include "fft_core.h"
+#include "solve.h"
 #include "ls_jacobi.h"
 
 namespace cine {
 
-constexpr int kLsPix = 64;                      // prox: pixels per workgroup (one wavefront = one frame / bin of the tile)
+constexpr int kLsPix = 64;                     // prox: pixels per workgroup (one wavefront = one frame / bin of the tile)
 constexpr int kLsItems = kLsMaxT * kLsPix / kLsThreads;
 constexpr int kLsGramTile = 2048;               // gram: complex128 entries of one staged tile (32 KiB)
 constexpr int kLsGramRecords = 256;             // gram: records (workgroups) over the whole batch, unless b itself is larger
@@ -68,7 +64,7 @@ __global__ __launch_bounds__(kLsThreads) void ls_gram_partial_kernel(LsGramArgs 
             if (s < ns) {
                 const long q = ((long)b * T + f) * a.HW + p0 + s;
                 cf v = a.a[q];
-                if (a.g) v = ls_v(v, a.g[q], step);
+                if (a.g) v = solve_v(v, a.g[q], step);
                 tile[f * ld + s] = make_double2((double)v.x, (double)v.y);
             }
         }
@@ -155,11 +151,7 @@ static LsGramPlan ls_gram_plan(int b, int t, int h, int w) {
 }
 
 static int ls_sizes(const char* what, int b, int t, int h, int w) {
-    CINE_REQUIRE(b > 0 && t > 0 && h > 0 && w > 0, CINE_EINVAL, "%s: bad sizes", what);
-    CINE_REQUIRE(t >= 2 && t <= kLsMaxT, CINE_EUNSUPPORTED, "%s: %d frames, 2 .. %d are supported", what, t, kLsMaxT);
-    CINE_REQUIRE(b <= 65535, CINE_EUNSUPPORTED, "%s: b > 65535", what);
-    CINE_REQUIRE(ceil_div((long)h * w, (long)kLsPix) <= 2147483647L, CINE_EUNSUPPORTED, "%s: h*w too large", what);
-    return CINE_OK;
+    return solve_sizes(what, b, t, h, w, kLsMaxT, ceil_div((long)h * w, (long)kLsPix));
 }
 
 static int ls_gram_launch(const float* a, const float* g, const float* step_dev, double* gram, int b, int t, int h, int w, void* ws,
@@ -246,7 +238,7 @@ static size_t ls_svt_lds(int t) { return (size_t)2 * t * t * sizeof(double2) + (
 static int ls_svt_prepare(int t) {
     static std::once_flag once[64];
     static hipError_t status[64];
-    return ls_svt_lds(t) >= 64 * 1024 ? ls_large_lds(reinterpret_cast<const void*>(ls_svt_kernel), "ls_svt_kernel", once, status) : CINE_OK;
+    return ls_svt_lds(t) >= 64 * 1024 ? large_lds_opt_in(reinterpret_cast<const void*>(ls_svt_kernel), "ls_svt_kernel", once, status) : CINE_OK;
 }
 
 static int ls_svt_launch(const double* gram, const float* thresh_dev, const float* step_dev, float* weight, double* info, int b, int t,
@@ -287,7 +279,7 @@ __global__ __launch_bounds__(kLsThreads) void ls_prox_kernel(LsProxArgs a) {
         cf v = mk(0.f, 0.f);
         if (p < np) {
             const long q = ((long)b * T + t) * HW + p0 + p;
-            v = ls_v(a.l[q], a.g[q], step);
+            v = solve_v(a.l[q], a.g[q], step);
         }
         buf[e] = v;
     }
@@ -310,6 +302,11 @@ __global__ __launch_bounds__(kLsThreads) void ls_prox_kernel(LsProxArgs a) {
         }
     }
     __syncthreads();
+    // A DELIBERATE COPY: from here on this is temporal_twiddles, temporal_dft_fwd + soft_threshold, temporal_dft_inv and block_record of
+    // solve.h written out -- a change there has to be made here as well.  With the helpers the outputs keep their bits, but the
+    // compiler schedules this 16-fold unrolled kernel differently (9558 instead of 9721 instructions, 119 instead of 118 VGPRs) and
+    // tools/ls_rate.py measured 50 iterations at 12.137 / 12.102 ms against 12.054 / 12.078 ms (row mask) and 15.029 / 14.989 ms against
+    // 14.959 / 14.932 ms (plane mask), parent - new - parent - new on one card: 0.4 % slower, outside the parent's own spread.
     cf* tw = wl;                                    // [T]: exp(-2 pi i j / T) / sqrt(T)
     float* red = reinterpret_cast<float*>(wl + T);  // [3][kLsThreads / 64]
     {
@@ -325,7 +322,7 @@ __global__ __launch_bounds__(kLsThreads) void ls_prox_kernel(LsProxArgs a) {
         cf v = mk(0.f, 0.f);
         if (p < np) {
             const long q = ((long)b * T + t) * HW + p0 + p;
-            v = ls_v(a.s ? a.s[q] : mk(0.f, 0.f), a.g[q], step);           // s == NULL (the solve's first iteration): S = 0
+            v = solve_v(a.s ? a.s[q] : mk(0.f, 0.f), a.g[q], step);           // s == NULL (the solve's first iteration): S = 0
         }
         buf[e] = v;
     }
@@ -389,8 +386,8 @@ __global__ __launch_bounds__(kLsThreads) void ls_prox_kernel(LsProxArgs a) {
         s_dx += dx * dx + dy * dy;
         s_x2 += xx * xx + xy * xy;
     }
-    if (a.part) {                                   // one record per workgroup; ls_record_kernel adds them in a fixed order
-        const float v0 = ls_wave_sum(s_dx), v1 = ls_wave_sum(s_x2), v2 = ls_wave_sum(s_l1);
+    if (a.part) {                                   // one record per workgroup; solve_record_kernel adds them in a fixed order
+        const float v0 = wave_sum(s_dx), v1 = wave_sum(s_x2), v2 = wave_sum(s_l1);
         if ((tid & 63) == 0) { red[tid >> 6] = v0; red[4 + (tid >> 6)] = v1; red[8 + (tid >> 6)] = v2; }
         __syncthreads();
         if (tid == 0) {
@@ -400,39 +397,6 @@ __global__ __launch_bounds__(kLsThreads) void ls_prox_kernel(LsProxArgs a) {
             float* o = a.part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 4;
             o[0] = r[0]; o[1] = r[1]; o[2] = r[2]; o[3] = 0.f;
         }
-    }
-}
-
-// rows of nblk records each -> rec (rows, 4): the records of a row added in float64 in a fixed order (one workgroup per row).  With info
-// (rows, nb, 4): column 3 = the nuclear norms of the row added over the batch, and resid (rows) = the worst Jacobi residual of the row.
-__global__ __launch_bounds__(256) void ls_record_kernel(const float* part, long nblk, float* rec, const double* info, int nb, double* resid) {
-    __shared__ double red[3][256];
-    const int tid = threadIdx.x;
-    const float* p = part + (long)blockIdx.x * nblk * 4;
-    double s[3] = {0.0, 0.0, 0.0};
-    for (long e = tid; e < nblk; e += 256) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) s[q] += (double)p[e * 4 + q];
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) red[q][tid] = s[q];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-#pragma unroll
-            for (int q = 0; q < 3; ++q) red[q][tid] += red[q][tid + st];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        double nuc = 0.0, worst = 0.0;
-        if (info) {
-            const double* f = info + (long)blockIdx.x * nb * 4;
-            for (int i = 0; i < nb; ++i) { nuc += f[i * 4 + 1]; worst = ls_nanmax(worst, f[i * 4 + 2]); }
-            if (resid) resid[blockIdx.x] = worst;
-        }
-        float* o = rec + (long)blockIdx.x * 4;
-        o[0] = (float)red[0][0]; o[1] = (float)red[1][0]; o[2] = (float)red[2][0]; o[3] = (float)nuc;
     }
 }
 
@@ -446,7 +410,7 @@ static size_t ls_prox_lds(int t) {
 static int ls_prox_prepare(int t) {
     static std::once_flag once[64];
     static hipError_t status[64];
-    return ls_prox_lds(t) >= 64 * 1024 ? ls_large_lds(reinterpret_cast<const void*>(ls_prox_kernel), "ls_prox_kernel", once, status) : CINE_OK;
+    return ls_prox_lds(t) >= 64 * 1024 ? large_lds_opt_in(reinterpret_cast<const void*>(ls_prox_kernel), "ls_prox_kernel", once, status) : CINE_OK;
 }
 
 static int ls_prox_launch(const float* l, const float* s, const float* g, const float* weight, const float* step_dev, const float* thresh_dev,
@@ -461,10 +425,26 @@ static int ls_prox_launch(const float* l, const float* s, const float* g, const 
     return check_launch("ls_prox_kernel");
 }
 
-static int ls_record_launch(const float* part, long nblk, float* rec, int rows, const double* info, int nb, double* resid, hipStream_t st) {
-    ProfScope prof(F_MISC, st);
-    hipLaunchKernelGGL(ls_record_kernel, dim3(rows), dim3(256), 0, st, part, nblk, rec, info, nb, resid);
-    return check_launch("ls_record_kernel");
+// workspace of the solve:
+// [operator scratch | g | L | S | gram | gram records | weight | iters rows of info | iters rows of per-workgroup records]
+struct LsSolveWs { size_t op_bytes, total; void* op; float* g; float* L; float* S; double* gram; void* gram_ws; float* weight; double* info; float* part; };
+
+static LsSolveWs ls_solve_ws(void* ws, int b, int t, int c, int h, int w, int mask_w, int iters) {
+    LsSolveWs y{};
+    WsCursor at{static_cast<unsigned char*>(ws)};
+    const size_t img = (size_t)b * t * h * w * sizeof(cf);
+    y.op_bytes = dc_ws_bytes(mask_w, b, t, c, h, w);
+    y.op = y.op_bytes ? at.take<void>(y.op_bytes) : nullptr;
+    y.g = at.take<float>(img);
+    y.L = at.take<float>(img);
+    y.S = at.take<float>(img);
+    y.gram = at.take<double>((size_t)b * t * t * sizeof(double2));
+    y.gram_ws = at.take<void>(cine_casorati_gram_ws_bytes(b, t, h, w));
+    y.weight = at.take<float>((size_t)b * t * t * sizeof(cf));
+    y.info = at.take<double>((size_t)iters * b * 4 * sizeof(double));
+    y.part = at.take<float>((size_t)iters * cine_ls_prox_ws_bytes(b, t, h, w));
+    y.total = at.end;
+    return y;
 }
 
 }  // namespace cine
@@ -484,11 +464,12 @@ extern "C" int cine_casorati_gram(const float* a, const float* g, const float* s
     CINE_REQUIRE(a && gram && ws && (!g || step_dev), CINE_EINVAL, "%s: null pointer", what);
     if (int e = ls_sizes(what, b, t, h, w)) return e;
     {
-        const void* o = gram;
-        CINE_REQUIRE(o != a && o != g && o != step_dev && o != ws && ws != (const void*)a && ws != (const void*)g && ws != (const void*)step_dev &&
-                     (const void*)a != (const void*)step_dev, CINE_EINVAL, "%s: gram and ws must not alias an operand or each other", what);
+        const void* const outs[] = {gram};
+        const void* const ins[] = {a, g, step_dev};
+        CINE_REQUIRE(solve_no_alias(outs, ins, ws) && (const void*)a != (const void*)step_dev, CINE_EINVAL,
+                     "%s: gram and ws must not alias an operand or each other", what);
     }
-    CINE_REQUIRE(ls_aligned16(gram) && ls_aligned16(ws), CINE_EINVAL, "%s: gram and ws must be 16-byte aligned", what);
+    CINE_REQUIRE(solve_aligned16(gram) && solve_aligned16(ws), CINE_EINVAL, "%s: gram and ws must be 16-byte aligned", what);
     const size_t need = cine_casorati_gram_ws_bytes(b, t, h, w);
     CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
     return ls_gram_launch(a, g, step_dev, gram, b, t, h, w, ws, as_stream(stream));
@@ -500,11 +481,11 @@ extern "C" int cine_svt_weight(const double* gram, const float* thresh_dev, cons
     CINE_REQUIRE(gram && thresh_dev && weight && info, CINE_EINVAL, "%s: null pointer", what);
     if (int e = ls_sizes(what, b, t, 1, 1)) return e;
     {
-        const void* o = weight; const void* f = info;
-        CINE_REQUIRE(o != gram && o != thresh_dev && o != step_dev && o != f && f != gram && f != thresh_dev && f != step_dev, CINE_EINVAL,
-                     "%s: weight and info must not alias an operand or each other", what);
+        const void* const outs[] = {weight, info};
+        const void* const ins[] = {gram, thresh_dev, step_dev};
+        CINE_REQUIRE(solve_no_alias(outs, ins, nullptr), CINE_EINVAL, "%s: weight and info must not alias an operand or each other", what);
     }
-    CINE_REQUIRE(ls_aligned16(gram) && (reinterpret_cast<uintptr_t>(info) & 7u) == 0, CINE_EINVAL,
+    CINE_REQUIRE(solve_aligned16(gram) && (reinterpret_cast<uintptr_t>(info) & 7u) == 0, CINE_EINVAL,
                  "%s: gram must be 16-byte aligned and info 8-byte aligned", what);
     if (int e = ls_svt_prepare(t)) return e;
     return ls_svt_launch(gram, thresh_dev, step_dev, weight, info, b, t, as_stream(stream));
@@ -533,11 +514,9 @@ extern "C" int cine_ls_prox(const float* l, const float* s, const float* g, cons
         CINE_REQUIRE(ok, CINE_EINVAL, "%s: only lnew == l and snew == s may alias", what);
     }
     if (rec) {
-        const void* r = rec;
-        const void* all[9] = {l, s, g, weight, step_dev, thresh_s_dev, lnew, snew, xsum};
-        bool ok = r != ws;
-        for (int i = 0; i < 9; ++i) ok = ok && r != all[i] && ws != all[i];
-        CINE_REQUIRE(ok, CINE_EINVAL, "%s: rec and ws must not alias an operand or each other", what);
+        const void* const outs[] = {rec};
+        const void* const ins[] = {l, s, g, weight, step_dev, thresh_s_dev, lnew, snew, xsum};
+        CINE_REQUIRE(solve_no_alias(outs, ins, ws), CINE_EINVAL, "%s: rec and ws must not alias an operand or each other", what);
         const size_t need = cine_ls_prox_ws_bytes(b, t, h, w);
         CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
     }
@@ -545,31 +524,12 @@ extern "C" int cine_ls_prox(const float* l, const float* s, const float* g, cons
     hipStream_t st = as_stream(stream);
     float* part = rec ? reinterpret_cast<float*>(ws) : nullptr;
     if (int e = ls_prox_launch(l, s, g, weight, step_dev, thresh_s_dev, lnew, snew, xsum, part, b, t, h, w, st)) return e;
-    return rec ? ls_record_launch(part, ls_blocks(b, h, w), rec, 1, nullptr, 0, nullptr, st) : CINE_OK;
+    return rec ? solve_record_launch(part, ls_blocks(b, h, w), rec, 1, st) : CINE_OK;
 }
-
-namespace {
-// workspace of the solve, each part on a 256-byte boundary:
-// [operator scratch | g | L | S | gram | gram records | weight | iters rows of info | iters rows of per-workgroup records]
-struct LsSolveLayout { size_t op, img, gram, gram_ws, weight, info, part, total; };
-
-LsSolveLayout ls_solve_layout(int b, int t, int c, int h, int w, int mask_w, int iters) {
-    LsSolveLayout y{};
-    y.op = ls_align(mask_w == 1 ? cine_image_dc_ws_bytes(b, t, c, h, w) : cine_image_dc_general_ws_bytes(b, t, c, h, w));
-    y.img = ls_align((size_t)b * t * h * w * sizeof(cf));
-    y.gram = ls_align((size_t)b * t * t * sizeof(double2));
-    y.gram_ws = ls_align(cine_casorati_gram_ws_bytes(b, t, h, w));
-    y.weight = ls_align((size_t)b * t * t * sizeof(cf));
-    y.info = ls_align((size_t)iters * b * 4 * sizeof(double));
-    y.part = (size_t)iters * cine_ls_prox_ws_bytes(b, t, h, w);
-    y.total = y.op + 3 * y.img + y.gram + y.gram_ws + y.weight + y.info + y.part;
-    return y;
-}
-}  // namespace
 
 extern "C" size_t cine_ls_solve_ws_bytes(int b, int t, int c, int h, int w, int mask_w, int iters) {
     if (b <= 0 || t < 2 || t > kLsMaxT || c <= 0 || h <= 0 || w <= 0 || iters <= 0 || b > 65535) return 0;
-    return ls_solve_layout(b, t, c, h, w, mask_w, iters).total;
+    return ls_solve_ws(nullptr, b, t, c, h, w, mask_w, iters).total;
 }
 
 extern "C" int cine_ls_solve(float* x, float* l_out, float* s_out, const float* zf, const float* sens, const float* sens_tiled,
@@ -582,53 +542,30 @@ extern "C" int cine_ls_solve(float* x, float* l_out, float* s_out, const float* 
     if (int e = ls_sizes(what, b, t, h, w)) return e;
     CINE_REQUIRE(mask_w == 1 || mask_w == w, CINE_EINVAL, "%s: mask_w %d is neither 1 (row mask) nor w", what, mask_w);
     {
-        const void* ins[8] = {zf, sens, sens_tiled, mask, step_dev, thresh_l_dev, thresh_s_dev, ws};
-        const void* outs[5] = {x, l_out, s_out, rec, resid};
-        bool ok = true;
-        for (int i = 0; i < 5; ++i) {
-            if (!outs[i]) continue;
-            for (int j = 0; j < 8; ++j) ok = ok && outs[i] != ins[j];
-            for (int j = 0; j < i; ++j) ok = ok && outs[i] != outs[j];
-        }
-        for (int j = 0; j < 7; ++j) ok = ok && ws != ins[j];
-        CINE_REQUIRE(ok, CINE_EINVAL, "%s: x, l, s, rec, resid and ws must not alias an operand or each other", what);
+        const void* const outs[] = {x, l_out, s_out, rec, resid};
+        const void* const ins[] = {zf, sens, sens_tiled, mask, step_dev, thresh_l_dev, thresh_s_dev};
+        CINE_REQUIRE(solve_no_alias(outs, ins, ws), CINE_EINVAL, "%s: x, l, s, rec, resid and ws must not alias an operand or each other", what);
     }
-    CINE_REQUIRE(ls_aligned16(ws), CINE_EINVAL, "%s: ws must be 16-byte aligned", what);
+    CINE_REQUIRE(solve_aligned16(ws), CINE_EINVAL, "%s: ws must be 16-byte aligned", what);
     CINE_REQUIRE(!resid || (reinterpret_cast<uintptr_t>(resid) & 7u) == 0, CINE_EINVAL, "%s: resid must be 8-byte aligned", what);
     const size_t need = cine_ls_solve_ws_bytes(b, t, c, h, w, mask_w, iters);
     CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
+    const LsSolveWs y = ls_solve_ws(ws, b, t, c, h, w, mask_w, iters);
     if (int e = ls_svt_prepare(t)) return e;
     if (int e = ls_prox_prepare(t)) return e;
-    const bool row = mask_w == 1;
-    const size_t op_bytes = row ? cine_image_dc_ws_bytes(b, t, c, h, w) : cine_image_dc_general_ws_bytes(b, t, c, h, w);
-    const LsSolveLayout y = ls_solve_layout(b, t, c, h, w, mask_w, iters);
-    unsigned char* at = reinterpret_cast<unsigned char*>(ws);
-    void* op_ws = op_bytes ? at : nullptr;                     at += y.op;
-    float* g = reinterpret_cast<float*>(at);                   at += y.img;
-    float* L = l_out ? l_out : reinterpret_cast<float*>(at);   at += y.img;
-    float* S = s_out ? s_out : reinterpret_cast<float*>(at);   at += y.img;
-    double* gram = reinterpret_cast<double*>(at);              at += y.gram;
-    void* gram_ws = at;                                        at += y.gram_ws;
-    float* weight = reinterpret_cast<float*>(at);              at += y.weight;
-    double* info = reinterpret_cast<double*>(at);              at += y.info;
-    float* part = reinterpret_cast<float*>(at);
+    float* L = l_out ? l_out : y.L;
+    float* S = s_out ? s_out : y.S;
     const long nblk = ls_blocks(b, h, w);
     hipStream_t st = as_stream(stream);
     for (int k = 0; k < iters; ++k) {
         const float* xk = k == 0 ? zf : x;          // L_0 + S_0 = zf without a copy
         const float* lk = k == 0 ? zf : L;          // and S_0 = 0 without a buffer of zeros: the prox kernel takes s == NULL
-        const int e = row ? cine_image_dc_t(xk, sens, sens_tiled, zf, mask, nullptr, 1.f, 0.f, -1.f, g, b, t, c, h, w, 0, op_ws, op_bytes, stream)
-                          : cine_image_dc_general(xk, sens, zf, mask, nullptr, 1.f, 0.f, -1.f, g, b, t, c, h, w, 0, op_ws, op_bytes, stream);
-        if (e) {                                    // at k == 0 nothing has been launched yet: the operator's own refusal of a size
-            const std::string why = cine_last_error();
-            set_error("%s: %s", what, why.c_str());
+        if (int e = solve_gradient(what, xk, zf, sens, sens_tiled, mask, mask_w, y.g, b, t, c, h, w, y.op, y.op_bytes, stream)) return e;
+        if (int e = ls_gram_launch(lk, y.g, step_dev, y.gram, b, t, h, w, y.gram_ws, st)) return e;
+        if (int e = ls_svt_launch(y.gram, thresh_l_dev, step_dev, y.weight, y.info + (size_t)k * b * 4, b, t, st)) return e;
+        if (int e = ls_prox_launch(lk, k == 0 ? nullptr : S, y.g, y.weight, step_dev, thresh_s_dev, L, S, x,
+                                   rec ? y.part + (size_t)k * nblk * 4 : nullptr, b, t, h, w, st))
             return e;
-        }
-        double* info_k = info + (size_t)k * b * 4;
-        if (int e2 = ls_gram_launch(lk, g, step_dev, gram, b, t, h, w, gram_ws, st)) return e2;
-        if (int e2 = ls_svt_launch(gram, thresh_l_dev, step_dev, weight, info_k, b, t, st)) return e2;
-        if (int e2 = ls_prox_launch(lk, k == 0 ? nullptr : S, g, weight, step_dev, thresh_s_dev, L, S, x, rec ? part + (size_t)k * nblk * 4 : nullptr, b, t, h, w, st))
-            return e2;
     }
-    return rec ? ls_record_launch(part, nblk, rec, iters, info, b, resid, st) : CINE_OK;
+    return rec ? solve_record_launch(y.part, nblk, rec, iters, st, y.info, b, resid) : CINE_OK;
 }

@@ -12,15 +12,14 @@
 // further on the low side straight from memory.  The frames are walked with a rolling window of two LDS slots, {xnew, 2 xnew - x} per point
 // (2 x 297 x 16 B = 9.3 KiB): the slot of frame f + 1 is filled, then the duals of frame f are formed from both.  Halo values are
 // recomputed, never exchanged: every workgroup reads x, g, p and writes xnew, pnew, so no output may alias an input.
-#include <string>
-#include "common.h"
-#include "fft_core.h"
+#include "solve.h"
 
 namespace cine {
 
 constexpr int kTvTh = 8;             // tile rows
 constexpr int kTvTw = 32;            // tile columns: 256 B of one image row per tile row
 constexpr int kTvThreads = kTvTh * kTvTw;
+static_assert(kTvThreads == kSolveThreads, "block_record is written for this workgroup");
 constexpr int kTvFrames = 2;         // frames per workgroup (plus one evaluated for D_t of the last); the fastest of 1 .. 16 at 15 x 200 x 200
 constexpr int kTvMaxT = 64;
 constexpr int kTvRow = kTvTw + 1;    // LDS row: the tile's columns and the halo column
@@ -38,12 +37,6 @@ struct TvArgs {
 };
 
 struct TvOwn { cf pt, ph, pw; };     // the duals at an evaluated point, kept for the projection of that point
-
-__device__ __forceinline__ float tv_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // xnew and 2 xnew - x at (f, i, j) of batch element b, which lies inside the image
 __device__ __forceinline__ float4 tv_eval(const TvArgs& a, int b, int f, int i, int j, float tau, TvOwn& own, cf& xold) {
@@ -84,7 +77,7 @@ __device__ __forceinline__ float4 tv_eval(const TvArgs& a, int b, int f, int i, 
 
 __global__ __launch_bounds__(kTvThreads) void tv_pd_kernel(TvArgs a) {
     __shared__ float4 slot[2][kTvSlot];
-    __shared__ float red[4][kTvThreads / 64];
+    __shared__ float red[4 * kTvThreads / 64];
     const int tid = threadIdx.x;
     const int T = a.T, H = a.H, W = a.W;
     const int b = blockIdx.y;
@@ -175,39 +168,10 @@ __global__ __launch_bounds__(kTvThreads) void tv_pd_kernel(TvArgs a) {
         own_cur = own_nxt;
         __syncthreads();                            // slot cur is the next iteration's nxt
     }
-    if (a.part) {                                   // one record per workgroup; tv_record_kernel adds them in a fixed order
-        const float v0 = tv_wave_sum(s_dx), v1 = tv_wave_sum(s_x2), v2 = tv_wave_sum(s_dt), v3 = tv_wave_sum(s_ds);
-        if ((tid & 63) == 0) { red[0][tid >> 6] = v0; red[1][tid >> 6] = v1; red[2][tid >> 6] = v2; red[3][tid >> 6] = v3; }
-        __syncthreads();
-        if (tid == 0) {
-            float* o = a.part + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 4;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) o[q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-        }
+    if (a.part) {
+        float s[4] = {s_dx, s_x2, s_dt, s_ds};
+        block_record(s, red, a.part, tid);
     }
-}
-
-// rows of nblk records each -> rec (rows, 4): the records of a row added in float64 in a fixed order (one workgroup per row)
-__global__ __launch_bounds__(256) void tv_record_kernel(const float* part, long nblk, float* rec) {
-    __shared__ double red[4][256];
-    const int tid = threadIdx.x;
-    const float* p = part + (long)blockIdx.x * nblk * 4;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (long e = tid; e < nblk; e += 256) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] += (double)p[e * 4 + q];
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) red[q][tid] = s[q];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) red[q][tid] += red[q][tid + st];
-        }
-        __syncthreads();
-    }
-    if (tid < 4) rec[(long)blockIdx.x * 4 + tid] = (float)red[tid][0];
 }
 
 __global__ __launch_bounds__(256) void tv_zero_kernel(float* p, long n) {
@@ -219,11 +183,7 @@ static long tv_blocks(int b, int t, int h, int w) { return tv_tiles(h, w) * ceil
 
 // sizes of one step launch: everything cine_tv_pd_step and cine_tv_solve refuse about (b, t, h, w)
 static int tv_sizes(const char* what, int b, int t, int h, int w) {
-    CINE_REQUIRE(b > 0 && t > 0 && h > 0 && w > 0, CINE_EINVAL, "%s: bad sizes", what);
-    CINE_REQUIRE(t >= 2 && t <= kTvMaxT, CINE_EUNSUPPORTED, "%s: %d frames, 2 .. %d are supported", what, t, kTvMaxT);
-    CINE_REQUIRE(b <= 65535, CINE_EUNSUPPORTED, "%s: b > 65535", what);                    // b rides on grid.y
-    CINE_REQUIRE(tv_tiles(h, w) * ceil_div(t, kTvFrames) <= 2147483647L, CINE_EUNSUPPORTED, "%s: h*w too large", what);
-    return CINE_OK;
+    return solve_sizes(what, b, t, h, w, kTvMaxT, tv_tiles(h, w) * ceil_div(t, kTvFrames));
 }
 
 // p / pnew: the three planes given one by one (the solve keeps only the planes of the terms that are on)
@@ -243,13 +203,26 @@ static int tv_launch(const float* x, const float* g, const float* const p[3], co
     return check_launch("tv_pd_kernel");
 }
 
-static int tv_record_launch(const float* part, long nblk, float* rec, int rows, hipStream_t st) {
-    ProfScope prof(F_MISC, st);
-    hipLaunchKernelGGL(tv_record_kernel, dim3(rows), dim3(256), 0, st, part, nblk, rec);
-    return check_launch("tv_record_kernel");
+// workspace of the solve: [operator scratch | g | x' | two dual buffers of three planes each | iters rows of per-workgroup records].
+// The terms are not among the arguments of cine_tv_solve_ws_bytes, so the duals are sized for all three planes; a solve with one term
+// packs the planes that are on at the front of p[0] and behind them p[1].
+struct TvSolveWs { size_t op_bytes, total, plane_floats; void* op; float* g; float* xtmp; float* p; float* part; };
+
+static TvSolveWs tv_solve_ws(void* ws, int b, int t, int c, int h, int w, int mask_w, int iters) {
+    TvSolveWs y{};
+    WsCursor at{static_cast<unsigned char*>(ws)};
+    const size_t img = solve_align((size_t)b * t * h * w * sizeof(cf));
+    y.plane_floats = img / sizeof(float);
+    y.op_bytes = dc_ws_bytes(mask_w, b, t, c, h, w);
+    y.op = y.op_bytes ? at.take<void>(y.op_bytes) : nullptr;
+    y.g = at.take<float>(img);
+    y.xtmp = at.take<float>(img);
+    y.p = at.take<float>(6 * img);
+    y.part = at.take<float>((size_t)iters * cine_tv_pd_ws_bytes(b, t, h, w));
+    y.total = at.end;
+    return y;
 }
 
-static size_t tv_align(size_t n) { return (n + 255) & ~(size_t)255; }
 static int tv_planes(int terms) { return ((terms & 1) ? 1 : 0) + ((terms & 2) ? 2 : 0); }
 
 }  // namespace cine
@@ -277,19 +250,12 @@ extern "C" int cine_tv_pd_step(const float* x, const float* g, const float* p, c
     if (int e = tv_sizes(what, b, t, h, w)) return e;
     // workgroups read x, g and p across each other's seams: an output is no operand
     {
-        const void* ins[] = {x, g, p, tau_dev, sigma_dev, lam_t_dev, lam_s_dev};
-        for (const void* in : ins)
-            CINE_REQUIRE(in != (const void*)xnew && in != (const void*)pnew, CINE_EINVAL, "%s: xnew and pnew must not alias an operand", what);
-        CINE_REQUIRE(xnew != pnew, CINE_EINVAL, "%s: xnew and pnew must not alias each other", what);
-        if (rec) {
-            const void* r = rec;
-            CINE_REQUIRE(r != ws && r != (const void*)xnew && r != (const void*)pnew && ws != (const void*)xnew && ws != (const void*)pnew, CINE_EINVAL,
-                         "%s: rec and ws must not alias an output or each other", what);
-            for (const void* in : ins)
-                CINE_REQUIRE(in != r && in != (const void*)ws, CINE_EINVAL, "%s: rec and ws must not alias an operand", what);
-            const size_t need = cine_tv_pd_ws_bytes(b, t, h, w);
-            CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
-        }
+        const void* const outs[] = {xnew, pnew, rec};
+        const void* const ins[] = {x, g, p, tau_dev, sigma_dev, lam_t_dev, lam_s_dev};
+        CINE_REQUIRE(solve_no_alias(outs, ins, rec ? ws : nullptr), CINE_EINVAL,
+                     "%s: xnew, pnew, rec and ws must not alias an operand or each other", what);
+        const size_t need = rec ? cine_tv_pd_ws_bytes(b, t, h, w) : 0;
+        CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
     }
     hipStream_t st = as_stream(stream);
     const size_t plane = (size_t)b * t * h * w * 2;
@@ -297,16 +263,12 @@ extern "C" int cine_tv_pd_step(const float* x, const float* g, const float* p, c
     float* pout[3] = {pnew, pnew + plane, pnew + 2 * plane};
     float* part = rec ? reinterpret_cast<float*>(ws) : nullptr;
     if (int e = tv_launch(x, g, pin, tau_dev, sigma_dev, lam_t_dev, lam_s_dev, terms, periodic, xnew, pout, part, b, t, h, w, st)) return e;
-    return rec ? tv_record_launch(part, tv_blocks(b, t, h, w), rec, 1, st) : CINE_OK;
+    return rec ? solve_record_launch(part, tv_blocks(b, t, h, w), rec, 1, st) : CINE_OK;
 }
 
-// workspace of the solve: [operator scratch | g | x' | p (the planes that are on) | p' | iters rows of per-workgroup records], each part
-// on a 256-byte boundary.  cine_tv_solve_ws_bytes sizes p for all three planes: the terms are not among its arguments.
 extern "C" size_t cine_tv_solve_ws_bytes(int b, int t, int c, int h, int w, int mask_w, int iters) {
     if (b <= 0 || t <= 0 || c <= 0 || h <= 0 || w <= 0 || iters <= 0) return 0;
-    const size_t op = mask_w == 1 ? cine_image_dc_ws_bytes(b, t, c, h, w) : cine_image_dc_general_ws_bytes(b, t, c, h, w);
-    const size_t img = tv_align((size_t)b * t * h * w * sizeof(cf));
-    return tv_align(op) + 8 * img + (size_t)iters * cine_tv_pd_ws_bytes(b, t, h, w);
+    return tv_solve_ws(nullptr, b, t, c, h, w, mask_w, iters).total;
 }
 
 extern "C" int cine_tv_solve(float* x, const float* zf, const float* sens, const float* sens_tiled, const uint8_t* mask, int mask_w,
@@ -321,63 +283,39 @@ extern "C" int cine_tv_solve(float* x, const float* zf, const float* sens, const
     if (int e = tv_sizes(what, b, t, h, w)) return e;
     CINE_REQUIRE(mask_w == 1 || mask_w == w, CINE_EINVAL, "%s: mask_w %d is neither 1 (row mask) nor w", what, mask_w);
     {
-        const void* ins[] = {zf, sens, sens_tiled, mask, tau_dev, sigma_dev, lam_t_dev, lam_s_dev};
-        const void* o = x; const void* r = rec; const void* d = p_out;
-        for (const void* in : ins) {
-            if (!in) continue;
-            CINE_REQUIRE(in != o, CINE_EINVAL, "%s: x must not alias another operand", what);
-            CINE_REQUIRE(in != r && in != d, CINE_EINVAL, "%s: rec and p_out must not alias another operand", what);
-            CINE_REQUIRE(in != (const void*)ws, CINE_EINVAL, "%s: ws must not alias an operand", what);
-        }
-        CINE_REQUIRE(o != r && o != d && o != ws && (!r || (r != d && r != ws)) && (!d || d != ws), CINE_EINVAL,
-                     "%s: x, rec, p_out and ws must not alias each other", what);
+        const void* const outs[] = {x, rec, p_out};
+        const void* const ins[] = {zf, sens, sens_tiled, mask, tau_dev, sigma_dev, lam_t_dev, lam_s_dev};
+        CINE_REQUIRE(solve_no_alias(outs, ins, ws), CINE_EINVAL, "%s: x, rec, p_out and ws must not alias an operand or each other", what);
     }
     const size_t need = cine_tv_solve_ws_bytes(b, t, c, h, w, mask_w, iters);
     CINE_REQUIRE(ws_bytes >= need, CINE_EWORKSPACE, "%s: workspace %zu < %zu", what, ws_bytes, need);
-    const bool row = mask_w == 1;
-    const size_t op_bytes = row ? cine_image_dc_ws_bytes(b, t, c, h, w) : cine_image_dc_general_ws_bytes(b, t, c, h, w);
-    const size_t img_bytes = tv_align((size_t)b * t * h * w * sizeof(cf));
-    const size_t img_floats = img_bytes / sizeof(float);
-    const int np = tv_planes(terms);
-    unsigned char* base = reinterpret_cast<unsigned char*>(ws);
-    void* op_ws = op_bytes ? base : nullptr;
-    float* g = reinterpret_cast<float*>(base + tv_align(op_bytes));
-    float* xtmp = g + img_floats;
-    float* pbuf[2] = {xtmp + img_floats, xtmp + img_floats + (size_t)np * img_floats};
-    float* part = reinterpret_cast<float*>(base + tv_align(op_bytes) + 8 * img_bytes);
+    const TvSolveWs y = tv_solve_ws(ws, b, t, c, h, w, mask_w, iters);
+    float* pbuf[2] = {y.p, y.p + (size_t)tv_planes(terms) * y.plane_floats};
     const long nblk = tv_blocks(b, t, h, w);
     const size_t plane = (size_t)b * t * h * w * 2;
     hipStream_t st = as_stream(stream);
-    // the planes of buffer q, in the order (t, h, w); a plane that is off is a null pointer
-    auto planes = [&](float* buf, size_t stride, float* out[3]) {
-        float* next = buf;
+    // the planes of a buffer, in the order (t, h, w); a plane that is off is a null pointer
+    auto planes = [&](float* buf, float* out[3]) {
         for (int q = 0; q < 3; ++q) {
-            const bool on = q == 0 ? (terms & 1) != 0 : (terms & 2) != 0;
-            out[q] = on ? next : nullptr;
-            if (on) next += stride;
+            const bool on = (terms & (q == 0 ? 1 : 2)) != 0;
+            out[q] = on ? buf : nullptr;
+            if (on) buf += y.plane_floats;
         }
     };
     for (int k = 0; k < iters; ++k) {
         // the iterates alternate between x and x' so that the last one lands in x; x_0 = zf without a copy
-        float* xout = (iters - 1 - k) % 2 == 0 ? x : xtmp;
-        const float* xin = k == 0 ? zf : (xout == x ? xtmp : x);
-        const int e = row ? cine_image_dc_t(xin, sens, sens_tiled, zf, mask, nullptr, 1.f, 0.f, -1.f, g, b, t, c, h, w, 0, op_ws, op_bytes, stream)
-                          : cine_image_dc_general(xin, sens, zf, mask, nullptr, 1.f, 0.f, -1.f, g, b, t, c, h, w, 0, op_ws, op_bytes, stream);
-        if (e) {                                    // at k == 0 nothing has been launched yet: the operator's own refusal of a size
-            const std::string why = cine_last_error();
-            set_error("%s: %s", what, why.c_str());
-            return e;
-        }
+        float* xout = (iters - 1 - k) % 2 == 0 ? x : y.xtmp;
+        const float* xin = k == 0 ? zf : (xout == x ? y.xtmp : x);
+        if (int e = solve_gradient(what, xin, zf, sens, sens_tiled, mask, mask_w, y.g, b, t, c, h, w, y.op, y.op_bytes, stream)) return e;
         float* pin[3]; float* pout[3];
-        planes(pbuf[k & 1], img_floats, pin);
+        planes(pbuf[k & 1], pin);
+        planes(pbuf[(k & 1) ^ 1], pout);
         if (k == iters - 1 && p_out) {              // the last duals go straight to the caller, at their places among the three planes
             for (int q = 0; q < 3; ++q) pout[q] = p_out + (size_t)q * plane;
-        } else {
-            planes(pbuf[(k & 1) ^ 1], img_floats, pout);
         }
-        if (int e2 = tv_launch(xin, g, pin, tau_dev, sigma_dev, lam_t_dev, lam_s_dev, terms, periodic, xout, pout,
-                               rec ? part + (size_t)k * nblk * 4 : nullptr, b, t, h, w, st, k == 0))      // p_0 = 0 is told, not read
-            return e2;
+        if (int e = tv_launch(xin, y.g, pin, tau_dev, sigma_dev, lam_t_dev, lam_s_dev, terms, periodic, xout, pout,
+                              rec ? y.part + (size_t)k * nblk * 4 : nullptr, b, t, h, w, st, k == 0))       // p_0 = 0 is told, not read
+            return e;
     }
     if (p_out && terms != 3) {                      // the planes of the term that is off: zeros
         float* off = (terms & 1) ? p_out + plane : p_out;
@@ -386,5 +324,5 @@ extern "C" int cine_tv_solve(float* x, const float* zf, const float* sens, const
         hipLaunchKernelGGL(tv_zero_kernel, dim3((unsigned)min(ceil_div(n, 256L), 65536L)), dim3(256), 0, st, off, n);
         if (int e = check_launch("tv_zero_kernel")) return e;
     }
-    return rec ? tv_record_launch(part, nblk, rec, iters, st) : CINE_OK;
+    return rec ? solve_record_launch(y.part, nblk, rec, iters, st) : CINE_OK;
 }
