@@ -1426,7 +1426,8 @@ extern "C" int cine_crnn_step2(const float* x_f, const float* addend_f, float* y
 
 // Both time sweeps of a BCRNN layer (recurrent_varnet.py:236-254, batch 1) in ONE call: h_t = [ReLU](conv3x3(h_prev; W_h2h) + P_t) forward in time
 // (frames 0 .. T-1) and backward in time (T-1 .. 0), both chains advanced by one pair launch per step (T launches, T + 1 for odd T: the
-// middle frame is reached by both in the same step), out = hidden_f + hidden_b -- the first chain to reach a frame stores, the second adds.
+// middle frame is reached by both in the same step) -- or, on shapes outside the pair configuration of crnn_step2_impl (more than 16 padded
+// rows, or 2 * ceil(frags / 52) >= 200), by two launches per step, 2 T in all --, out = hidden_f + hidden_b -- the first chain to reach a frame stores, the second adds.
 // P, out (T, c, h, w); `zero` (c, h, w) zeros = hid_init (:236), read only; keep != 0: hf / hb (T, c, h, w) receive EVERY hidden state (what
 // cine_bcrnn_sweep_bwd reads), keep == 0: hf / hb are two-frame ping-pong buffers (2, c, h, w).
 extern "C" int cine_bcrnn_sweep(const float* P, const float* wpacked_hh, const float* zero, float* hf, float* hb, float* out,
@@ -1462,7 +1463,7 @@ extern "C" int cine_bcrnn_sweep(const float* P, const float* wpacked_hh, const f
 //   gb[t] = [hb[t] > 0] (conv(gb[t - 1]; Wd) + gout[t]),  t = 0 .. T-1      (the chain that ran backward in time)
 // with Wd = the input-gradient packing of W_h2h (cine_pack_conv3x3_dgrad) -- the forward conv kernel, gout riding in as the addend and the ReLU
 // mask as the epilogue's gate (relu == 0: identity activation, no gate) -- and gP = gf + gb = d loss / d P through the second output.  The two
-// chains are independent: one pair launch per step, as in the forward sweep.  gf, gb, gP (T, c, h, w); `zero` as above.
+// chains are independent: one pair launch per step (two launches outside the pair configuration), as in the forward sweep.  gf, gb, gP (T, c, h, w); `zero` as above.
 extern "C" int cine_bcrnn_sweep_bwd(const float* gout, const float* wpacked_hh_dgrad, const float* zero, const float* hf, const float* hb,
                                     float* gf, float* gb, float* gP, int T, int c, int h, int w, int relu, void* stream) {
     CINE_REQUIRE(gout && wpacked_hh_dgrad && zero && hf && hb && gf && gb && gP, CINE_EINVAL, "cine_bcrnn_sweep_bwd: null pointer");

@@ -339,7 +339,9 @@ int cine_crnn_step2(const float* x_f, const float* addend_f, float* y_f, float* 
  * tests/test_hip_grad.py, made by the reference with F.relu patched out). */
 /* BOTH time sweeps of a BCRNN layer (BCRNNlayer.forward, recurrent_varnet.py:236-254, batch 1) in one call -- the reference's two Python loops
  * over the frames: h_t = [ReLU](conv3x3(h_prev; W_h2h) + P_t) forward in time and backward in time, hid_init = `zero` ((c, h, w) zeros, read
- * only), one cine_crnn_step2 pair launch per step (T launches; T + 1 for odd T, where both chains reach the middle frame in the same step),
+ * only), one cine_crnn_step2 pair launch per step (T launches; T + 1 for odd T, where both chains reach the middle frame in the same step and
+ * run one after the other) -- on shapes outside the pair configuration (more than 16 padded rows, ceil(c / 16) * 16 > 16, or a plane of
+ * 2 * ceil(fragments / 52) >= 200, e.g. 400 x 208) TWO launches per step, 2 T in all, with the same results --,
  * out = hidden_f + hidden_b (the first chain to reach a frame stores, the second adds: no zero fill, no extra pass).  P (T, c, h, w) = the
  * input terms i2h(x_t) + ih2ih(hid_iter_t) + the three biases for ALL frames (:172-176, one batched launch by the caller), out (T, c, h, w).
  * keep != 0: hf / hb (T, c, h, w) receive every hidden state of the chain (training); keep == 0: hf / hb are (2, c, h, w) ping-pong buffers. */
@@ -348,7 +350,7 @@ int cine_bcrnn_sweep(const float* P, const float* wpacked_hh, const float* zero,
 /* Back-propagation through time of cine_bcrnn_sweep (keep != 0) -- what torch.autograd unrolls over the reference's two loops: from gout =
  * d loss / d out,  gf[t] = [hf[t] > 0] (conv(gf[t + 1]; Wd) + gout[t]) for t = T-1 .. 0 and gb[t] = [hb[t] > 0] (conv(gb[t - 1]; Wd) + gout[t]) for
  * t = 0 .. T-1, Wd = cine_pack_conv3x3_dgrad of W_h2h (the forward conv kernel; gout rides in as the addend, the ReLU mask is the epilogue's
- * gate; relu == 0: no mask), and gP = gf + gb = d loss / d P.  One pair launch per step; gf, gb, gP (T, c, h, w).  The weight gradients are the
+ * gate; relu == 0: no mask -- hf / hb are then not read but must still be non-NULL: NULL is refused with CINE_EINVAL either way), and gP = gf + gb = d loss / d P.  Launches per step as in cine_bcrnn_sweep; gf, gb, gP (T, c, h, w).  The weight gradients are the
  * caller's: dW_h2h from (hf[t - 1], gf[t]) and (hb[t + 1], gb[t]) with cine_conv3x3_wgrad, everything upstream of P from gP. */
 int cine_bcrnn_sweep_bwd(const float* gout, const float* wpacked_hh_dgrad, const float* zero, const float* hf, const float* hb,
                          float* gf, float* gb, float* gP, int T, int c, int h, int w, int relu, void* stream);
