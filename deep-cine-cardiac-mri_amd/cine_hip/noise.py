@@ -7,6 +7,9 @@ deviation of the N results is the noise map -- for any reconstruction, the non-l
                    and launch shape, one pass over the sampled points only; also the noise augmentation of a training loop
   ReplicaStats     Welford's running mean and variance over the replicas in float64 (cine_replica_accum / cine_replica_finish)
   pseudo_replica   the whole method, as a loop on the current stream or through a ``SlicePipeline`` (``submit(..., noise=)``)
+  add_noise_raw    cine_noise_add_raw: the same values on RAW data (t, x, y, coil), where receiver noise enters -- in front of whitening,
+                   coil compression, crop and filter, which colour it as they colour a scan's own
+  pseudo_replica_raw  the method for a raw scan: noise, ``frontend.prepare_masked_slice``, model -- or ``submit_raw(..., noise=)``
   g_factor         std_accel / (std_full sqrt(R)) from two noise maps
 
 The definition of the noise source is in include/cine_hip.h.  No CPU fallback.
@@ -19,9 +22,10 @@ import torch
 from . import ops
 from ._lib import CineHipError, check, lib
 
-__all__ = ["NOISE_MAX_COILS", "NoiseMaps", "NoiseSpec", "noise_cholesky", "add_noise", "ReplicaStats", "pseudo_replica", "g_factor"]
+__all__ = ["NOISE_MAX_COILS", "NoiseMaps", "NoiseSpec", "noise_cholesky", "add_noise", "add_noise_raw", "ReplicaStats", "pseudo_replica",
+           "pseudo_replica_raw", "g_factor"]
 
-NOISE_MAX_COILS = 64            # cine_noise_add: L and the lane's normals share the LDS (include/cine_hip.h)
+NOISE_MAX_COILS = 64            # cine_noise_add, cine_noise_add_raw: L and the lane's normals share the LDS (include/cine_hip.h)
 
 NoiseMaps = collections.namedtuple("NoiseMaps", "mean std snr g replicas")
 NoiseSpec = collections.namedtuple("NoiseSpec", "chol scale seed replica", defaults=(None, 1.0, 0, 0))
@@ -146,6 +150,75 @@ def add_noise(masked_kspace: torch.Tensor, mask: Optional[torch.Tensor], chol: O
     return out
 
 
+def _raw_noise_mask(mask, t: int, nx: int, ny: int, device, what: str = "add_noise_raw"):
+    """The mask of the raw samples as cine_noise_add_raw reads it: (contiguous uint8 (t, nx) or (t, nx, ny) or None, mask_ny)."""
+    if mask is None:
+        return None, 1
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
+        raise CineHipError(f"{what}: noise_mask must be a GPU tensor or None (the HIP path has no CPU fallback)")
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise CineHipError(f"{what}: noise_mask must be uint8 or bool, got {mask.dtype}")
+    if mask.device != device:
+        raise CineHipError(f"{what}: noise_mask is on {mask.device}, the raw data on {device}")
+    shape = tuple(mask.shape)
+    if not (mask.dim() in (2, 3) and shape[0] in (1, t) and shape[1:] in ((nx,), (nx, ny))):
+        raise ValueError(f"{what}: noise_mask {shape}; expected ({t} | 1, {nx}) or ({t} | 1, {nx}, {ny}) for raw data (t, x, y) = "
+                         f"({t}, {nx}, {ny})")
+    m = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    m = m.expand((t,) + shape[1:]).contiguous()
+    return m, (ny if mask.dim() == 3 else 1)
+
+
+def add_noise_raw(raw: torch.Tensor, chol: Optional[torch.Tensor] = None, *, noise_mask: Optional[torch.Tensor] = None,
+                  scale: float = 1.0, seed: int = 0, replica: int = 0, replica_dev: Optional[torch.Tensor] = None, point0: int = 0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``raw + eta`` at the acquired samples of RAW k-space, in front of the front-end (cine_noise_add_raw, one launch): receiver noise
+    where it enters, so that whitening, coil compression, crop, filter and calibration act on it as they act on a scan's own.
+
+    ``raw``: (t, x, y, coil) complex64 or (t, x, y, coil, 2) float32 on the GPU, contiguous -- what ``frontend.prepare_masked_slice``
+    and ``SlicePipeline.submit_raw`` take; the result has the input's form.  ``noise_mask``: which samples were acquired, uint8 or bool
+    on the GPU, (T | 1, x) for whole lines or (T | 1, x, y); a leading 1 is expanded; None: every sample (fully sampled raw that is
+    masked retrospectively).  ``chol``, ``scale``, ``seed``, ``replica``, ``replica_dev``: as in ``add_noise``; the point index is
+    ``point0`` + the flat index over (t, x, y), and the value of a (point, coil) is the one ``add_noise`` gives the permuted data
+    (t, coil, h = x, w = y), bit for bit.  ``out``: the result's place; ``out=raw`` works in place and touches the acquired samples
+    only.  At most 64 coils.  Not differentiable: an input that requires grad is refused."""
+    _no_grad_inputs("add_noise_raw", raw=raw, chol=chol)
+    if not isinstance(raw, torch.Tensor):
+        raise TypeError("add_noise_raw: expected a tensor")
+    if raw.is_complex() and raw.dtype != torch.complex64:
+        raise CineHipError(f"add_noise_raw: raw is {raw.dtype}; expected complex64 or float32 pairs")
+    cplx = raw.is_complex()
+    if cplx and not raw.is_contiguous():
+        raise CineHipError("add_noise_raw: raw must be contiguous")
+    x = torch.view_as_real(raw) if cplx else raw
+    if x.dim() != 5 or x.shape[-1] != 2:
+        raise ValueError(f"add_noise_raw: raw {tuple(raw.shape)}; expected (t, x, y, coil) complex64 or (t, x, y, coil, 2) float32")
+    k = ops._dev(x, "raw")
+    t, nx, ny, c = (int(v) for v in k.shape[:4])
+    if c > NOISE_MAX_COILS:
+        raise CineHipError(f"add_noise_raw: {c} coils, at most {NOISE_MAX_COILS}")
+    m, mask_ny = _raw_noise_mask(noise_mask, t, nx, ny, k.device)
+    low = _chol_pairs(chol, c, k.device)
+    if out is None:
+        res = torch.empty_like(k)
+    elif out is raw:
+        if k is not x:
+            raise CineHipError("add_noise_raw: in place needs contiguous raw data")
+        res = k
+    else:
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == raw.dtype and out.is_contiguous() and out.shape == raw.shape):
+            raise CineHipError("add_noise_raw: out must be a contiguous GPU tensor of the raw data's shape and dtype")
+        res = torch.view_as_real(out) if cplx else out
+    if replica_dev is not None and not (isinstance(replica_dev, torch.Tensor) and replica_dev.is_cuda and replica_dev.dtype == torch.int64
+                                        and replica_dev.numel() == 1):
+        raise CineHipError("add_noise_raw: replica_dev must be a one-element int64 GPU tensor")
+    check(lib().cine_noise_add_raw(k.data_ptr(), res.data_ptr(), ops._p(m), mask_ny, ops._p(low), float(scale), _as_long(seed), int(replica),
+                                   ops._p(replica_dev), int(point0), t, nx, ny, c, ops._stream()), "cine_noise_add_raw")
+    if out is not None:
+        return out
+    return torch.view_as_complex(res) if cplx else res
+
+
 def _as_long(seed: int) -> int:
     """Any Python integer as the C long of the same low 64 bits."""
     s = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -248,6 +321,84 @@ def pseudo_replica(model, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_
         raise CineHipError(f"pseudo_replica: the pipeline has {pipeline.pending()} slices pending; take them first")
     for r in range(replicas):
         pipeline.submit(masked_kspace, mask, sens_maps, noise=NoiseSpec(chol, scale, seed, r))
+        for _, o in pipeline.results():
+            take(o)
+    for _, o in pipeline.drain():
+        take(o)
+    return stats.finish()
+
+
+def pseudo_replica_raw(model, raw: torch.Tensor, mask: torch.Tensor, sens_maps: Optional[torch.Tensor] = None, *,
+                       chol: Optional[torch.Tensor] = None, scale: float = 1.0, replicas: int = 64, seed: int = 0,
+                       noise_mask: Optional[torch.Tensor] = None, pipeline=None, output: Optional[str] = None, **front_end) -> NoiseMaps:
+    """The noise maps of a RAW scan's slice through the front-end and ``model``: replica r is
+    ``model(frontend.prepare_masked_slice(add_noise_raw(raw[:n], chol, noise_mask=noise_mask, scale=scale, seed=seed, replica=r), mask,
+    **front_end), mask[, sens_maps])``, r = 0 .. replicas - 1, accumulated in that order; n = min(n_slices, t) kept frames.  The noise
+    enters where a receiver's does, so whitening, coil compression (with ``virtual_coils=`` every replica's matrix is computed from its
+    own noisy data), crop, filter and mask colour it as they colour the scan's own.  With ``chol`` from the scan's noise pre-scan
+    (``noise_cholesky(noise=...)``) ``scale=1`` means "the scan's noise once more"; the front-end's ``scaling=`` is applied behind it.
+
+    ``front_end``: the keywords of ``frontend.prepare_masked_slice`` / ``SlicePipeline.submit_raw`` (``crop_shape``, ``n_slices`` or
+    ``n_frames``, ``filter_size``, ``scaling``, ``coil_matrix``, ``apply_mask``, ``virtual_coils``, ``cc_region``, ``whitener``).
+    ``noise_mask``: see ``add_noise_raw``, on the kept frames; None for fully sampled raw masked retrospectively.  ``raw`` is moved to
+    the device once (a host array handed to ``submit_raw`` would be copied again for every replica).  Without ``pipeline`` a loop on
+    the current stream with ``output`` handed to the model; with ``pipeline`` the replicas go through ``submit_raw(..., noise=)`` under
+    the rules of ``pseudo_replica`` (no ``output``, nothing pending, device results), and ``sens_maps`` may be "espirit": every replica
+    then calibrates from its own noisy data.  The two ways give bit-identical maps."""
+    from . import frontend
+    replicas = int(replicas)
+    if replicas < 2:
+        raise ValueError(f"pseudo_replica_raw: replicas = {replicas}, at least 2")
+    if output not in (None, "magnitude", "complex"):
+        raise ValueError(f"pseudo_replica_raw: output {output!r}")
+    fe = dict(front_end)
+    if "n_frames" in fe and "n_slices" in fe:
+        raise ValueError("pseudo_replica_raw: n_frames and n_slices name the same setting; pass one")
+    n_keep = int(fe.pop("n_frames", fe.pop("n_slices", 15)))
+    unknown = set(fe) - {"crop_shape", "filter_size", "scaling", "coil_matrix", "apply_mask", "virtual_coils", "cc_region", "whitener"}
+    if unknown:
+        raise TypeError(f"pseudo_replica_raw: unknown front-end keywords {sorted(unknown)}")
+    if not torch.cuda.is_available():
+        raise CineHipError("pseudo_replica_raw: no GPU (the HIP path has no CPU fallback)")
+    dev = pipeline.device if pipeline is not None else torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(raw, torch.Tensor):
+        raw = torch.from_numpy(raw)
+    if raw.dim() < 4 or raw.shape[0] < 1 or n_keep < 1:
+        raise ValueError("Invalid shapes.")
+    kept = frontend._raw_pairs(raw[:min(n_keep, raw.shape[0])].to(dev), "pseudo_replica_raw")     # once: the replicas start from device memory
+    stats = None
+
+    def take(o):
+        nonlocal stats
+        if not isinstance(o, torch.Tensor):
+            raise CineHipError(f"pseudo_replica_raw: the reconstruction returned {type(o).__name__}, not a tensor")
+        if stats is None:
+            stats = ReplicaStats(o.shape, o.device, pairs=output == "complex")
+        stats.add(o)
+
+    if pipeline is None:
+        if isinstance(sens_maps, str):
+            raise CineHipError('pseudo_replica_raw: sens_maps="espirit" is calibrated in flight: pass pipeline=')
+        kw = {} if output is None else {"output": output}
+        noisy = torch.empty_like(kept)
+        with torch.no_grad():
+            for r in range(replicas):
+                add_noise_raw(kept, chol, noise_mask=noise_mask, scale=scale, seed=seed, replica=r, out=noisy)
+                mk = frontend.prepare_masked_slice(noisy, mask, n_slices=n_keep, **fe)
+                take(model(mk, mask, **kw) if sens_maps is None else model(mk, mask, sens_maps, **kw))
+        return stats.finish()
+    if pipeline.model is not model:
+        raise CineHipError("pseudo_replica_raw: the pipeline was built on another model")
+    if output is not None:
+        raise CineHipError("pseudo_replica_raw: a pipeline calls forward(masked_kspace, mask[, sens_maps]) only; leave output= out, or "
+                           "run without pipeline=")
+    if pipeline.zero_filled or pipeline.out != "device":
+        raise CineHipError("pseudo_replica_raw: the pipeline must hand out device tensors without the zero-filled image")
+    if pipeline.pending():
+        raise CineHipError(f"pseudo_replica_raw: the pipeline has {pipeline.pending()} slices pending; take them first")
+    for r in range(replicas):
+        pipeline.submit_raw(kept, mask, sens_maps, tag=("replica", r), n_frames=n_keep, noise=NoiseSpec(chol, scale, seed, r),
+                            noise_mask=noise_mask, **fe)
         for _, o in pipeline.results():
             take(o)
     for _, o in pipeline.drain():

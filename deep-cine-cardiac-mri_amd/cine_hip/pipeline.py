@@ -100,8 +100,11 @@ calibrates on the whitened virtual coils.
 ``submit(..., noise=noise.NoiseSpec(chol, scale, seed, replica))``: one pseudo replica (``cine_hip.noise``).  The slot's stream runs
 cine_noise_add in place on the slot's copy of the k-space, between the wait for the copy and the replay, so the result is bit for bit
 ``model(noise.add_noise(masked_kspace, mask, chol, scale=scale, seed=seed, replica=replica), mask[, sens_maps])``.  The spec is not part of
-the set key and no graph holds it: replicas and plain slices share one set, and ``noise=None`` is the path as it was.  ``submit_raw`` has no
-such keyword: noise in front of the crop and the filter would be coloured by them.
+the set key and no graph holds it: replicas and plain slices share one set, and ``noise=None`` is the path as it was.
+``submit_raw(..., noise=NoiseSpec, noise_mask=None)``: the replica of a raw scan.  cine_noise_add_raw runs in place on the slot's copy of
+the raw data, behind the wait for the copy and in front of the coil compression and the graph, so the noise passes through whitening, compression
+(``virtual_coils=``: the matrix of the noisy slice), crop, filter, mask and calibration as a scan's own does.  ``noise_mask`` (the acquired
+samples; for prospectively undersampled raw) is an input like the others, with a per-slot buffer that is made on first use.
 
 ``graphs=False`` is the explicit eager mode: same slots, streams, buffers, copies and events, with the launch sequence
 enqueued on the slot's stream for every slice.  A failure raises ``CineHipError``; nothing falls back to eager launches.
@@ -110,6 +113,7 @@ Not thread-safe: one pipeline is driven from one thread.  One pipeline per GPU (
 """
 import collections
 import inspect
+import math
 from typing import Optional
 
 import numpy as np
@@ -305,14 +309,14 @@ def _same_device(pipe, named):
             raise CineHipError(f"{name} is on {x.device}, the pipeline's device is {pipe.device}")
 
 
-def _check_noise(pipe, spec, masked_kspace):
-    """``submit(..., noise=)`` validated: a noise.NoiseSpec with its factor as float32 pairs on the pipeline's device, or None."""
+def _check_noise(pipe, spec, c: int):
+    """``submit(..., noise=)`` / ``submit_raw(..., noise=)`` validated for data of c coils: a noise.NoiseSpec with its factor as float32
+    pairs on the pipeline's device, or None."""
     if spec is None:
         return None
     from . import noise as N
     if not isinstance(spec, N.NoiseSpec):
         raise CineHipError(f"noise: expected a cine_hip.noise.NoiseSpec(chol, scale, seed, replica), got {type(spec).__name__}")
-    c = masked_kspace.shape[2] if isinstance(masked_kspace, torch.Tensor) and masked_kspace.dim() >= 5 else 0
     if c > N.NOISE_MAX_COILS:
         raise CineHipError(f"noise: {c} coils, at most {N.NOISE_MAX_COILS}")
     if isinstance(spec.replica, bool) or not isinstance(spec.replica, int) or not 0 <= spec.replica < 1 << 32:
@@ -326,7 +330,8 @@ class _Source:
     input_names = ("mk", "mask", "sens")
 
     def __init__(self, pipe, masked_kspace, mask, sens_maps, ecalib_r=15, sign_iters=60, noise=None):
-        self.noise = _check_noise(pipe, noise, masked_kspace)                # not part of the key: the graphs do not hold it
+        c = masked_kspace.shape[2] if isinstance(masked_kspace, torch.Tensor) and masked_kspace.dim() >= 5 else 0
+        self.noise = _check_noise(pipe, noise, c)                            # not part of the key: the graphs do not hold it
         mk, self.mk_kind = _pairs(masked_kspace, "masked_kspace")
         if mk.dim() != 6:
             raise CineHipError(f"masked_kspace: shape {tuple(mk.shape)}; expected (b, t, c, h, w, 2) or complex (b, t, c, h, w)")
@@ -404,10 +409,9 @@ class _RawSource:
     """One raw slice's validated inputs (``submit_raw``): the kept frames of the raw data in their original place, mask, sens, the coil
     matrix, the front-end's settings, the set key."""
     input_names = ("raw", "mask", "sens", "cmat", "wh")
-    noise = None                                    # submit(noise=) is for prepared k-space only
 
     def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask, ecalib_r=15,
-                 sign_iters=60, virtual_coils=None, cc_region=24, whitener=None):
+                 sign_iters=60, virtual_coils=None, cc_region=24, whitener=None, noise=None, noise_mask=None):
         if not isinstance(raw, (np.ndarray, torch.Tensor)):
             raise CineHipError(f"raw: expected a torch tensor or a numpy array, got {type(raw).__name__}")
         if raw.ndim < 4 or raw.shape[0] < 1 or int(n_frames) < 1:
@@ -418,6 +422,11 @@ class _RawSource:
         self.raw = x
         n, nx, ny, c, _ = x.shape
         self.n, self.c = n, c
+        # a pseudo replica: noise on the slot's copy of the raw data, in front of everything; neither is part of the key
+        self.noise = _check_noise(pipe, noise, c)
+        self.nmask, self.nmask_kind = _check_noise_mask(noise_mask, self.noise, n, nx, ny)
+        self.nmask_shape = None if self.nmask is None else (n,) + tuple(self.nmask.shape[1:])
+        self.nmask_nbytes = n * nx * ny                                      # the slot's buffer serves either layout
         self.crop = (int(crop_shape[0]), int(crop_shape[1]))
         if not (0 < self.crop[0] <= nx and 0 < self.crop[1] <= ny):
             raise ValueError("Invalid shapes.")                              # transforms.py:206-207
@@ -472,7 +481,7 @@ class _RawSource:
         if isinstance(self.sens, str):                                       # calibrated in flight, on the V virtual coils with a coil matrix
             self.sens, self.espirit = None, espirit_key(ecalib_r, sign_iters)
         _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat),
-                            ("whitener", self.wh)))
+                            ("whitener", self.wh), ("noise_mask", self.nmask)))
         self.raw_nbytes = x.numel() * 4
         self.gram_nbytes = 0                                                 # asked of the library when a buffer is needed (_submit, alloc)
         self.key = raw_set_key((n, nx, ny, c), n, self.crop, self.filter, self.scaling, self.apply_mask, self.mask_shape,
@@ -520,8 +529,13 @@ class _RawSource:
         c = self.c
         return b["wh"][:c * c].view(c, c)
 
+    def nmask_view(self, b):
+        return b["nmask"][:math.prod(self.nmask_shape)].view(self.nmask_shape)
+
     def items(self, b):
         it = [("raw", self.raw_view(b), self.raw, self.raw_kind), ("mask", b["mask"], self.mask, self.mask_kind)]
+        if self.nmask is not None:
+            it.append(("nmask", self.nmask_view(b), self.nmask, self.nmask_kind))
         if self.sens is not None:
             it.append(("sens", b["sens"], self.sens, self.sens_kind))
         if self.cmat is not None:
@@ -529,6 +543,30 @@ class _RawSource:
         if self.wh is not None:
             it.append(("wh", torch.view_as_real(self.wh_view(b)), self.wh, self.wh_kind))
         return it
+
+
+def _check_noise_mask(noise_mask, spec, n: int, nx: int, ny: int):
+    """``submit_raw(..., noise_mask=)`` against the kept frames: (the mask as given or a host uint8 one, its kind), or (None, None).
+    uint8 or bool, (n | 1, nx) for acquired lines or (n | 1, nx, ny); a leading 1 is expanded by the copy."""
+    if noise_mask is None:
+        return None, None
+    if spec is None:
+        raise CineHipError("noise_mask: says where noise= is added; without noise= there is nothing to mask")
+    m = torch.from_numpy(noise_mask) if isinstance(noise_mask, np.ndarray) else noise_mask
+    if not isinstance(m, torch.Tensor):
+        raise CineHipError(f"noise_mask: expected a torch tensor or a numpy array, got {type(noise_mask).__name__}")
+    if m.dtype not in (torch.uint8, torch.bool):
+        raise CineHipError(f"noise_mask: dtype {m.dtype}; expected uint8 or bool")
+    shape = tuple(m.shape)
+    if not (m.dim() in (2, 3) and shape[0] in (1, n) and shape[1:] in ((nx,), (nx, ny))):
+        raise CineHipError(f"noise_mask: shape {shape}; expected ({n} | 1, {nx}) or ({n} | 1, {nx}, {ny}) for the {n} kept frames of raw "
+                           f"data (t, x, y) = ({n}, {nx}, {ny})")
+    m = m.view(torch.uint8) if m.dtype == torch.bool else m
+    if m.is_cuda:
+        return m, "device"
+    m = m.expand((n,) + shape[1:])
+    canonical = m.is_contiguous() and m.is_pinned()
+    return (m, "pinned") if canonical else (m.contiguous(), "pageable")
 
 
 def _whitener_pairs(whitener, c: int):
@@ -630,8 +668,8 @@ class SlicePipeline:
         ``noise=noise.NoiseSpec(chol, scale, seed, replica)``: one pseudo replica -- the slot's stream runs cine_noise_add in place on
         the slot's copy of the k-space, between the copy and the replay, so the slice is reconstructed from
         ``noise.add_noise(masked_kspace, mask, chol, scale=scale, seed=seed, replica=replica)``, bit for bit.  The spec is not part of
-        the set key; ``noise=None`` takes the path it always took.  It describes noise on the PREPARED k-space: ``submit_raw`` has
-        no such keyword (the crop and the filter of the front-end would colour noise injected in front of them)."""
+        the set key; ``noise=None`` takes the path it always took.  It describes noise on the PREPARED k-space; noise where a
+        receiver's enters, in front of the crop and the filter that colour it, is ``submit_raw(..., noise=)``."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit after close()")
         return self._submit(_Source(self, masked_kspace, mask, sens_maps, ecalib_r, sign_iters, noise), tag)
@@ -639,7 +677,7 @@ class SlicePipeline:
     def submit_raw(self, raw, mask, sens_maps=None, tag=None, *, crop_shape=(200, 200), n_frames: int = 15,
                    filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, apply_mask: bool = True,
                    ecalib_r: int = 15, sign_iters: int = 60, virtual_coils: Optional[int] = None, cc_region: int = 24,
-                   whitener=None) -> SliceHandle:
+                   whitener=None, noise=None, noise_mask=None) -> SliceHandle:
         """Enqueue one slice from its RAW k-space (t, x, y, coil) -- complex64 or float32 pairs, in any of the four places ``submit`` takes
         its input from.  Only ``raw[:min(n_frames, t)]`` is copied to the device.  ``frontend.prepare_masked_slice`` and the model run on
         the slot's stream inside the slot's graph; see the module docstring.  ``mask``: the mask on the crop grid, a row mask or one that varies along w under the
@@ -651,11 +689,20 @@ class SlicePipeline:
         the slice is ``pipe.last_coil_info[tag].kept`` once ``results`` / ``drain`` have handed it out; ``tag`` must then be hashable.
         ``whitener=W`` (coil, coil) complex128 from ``frontend.noise_whitener`` on the scan's noise samples, from numpy, pinned or device
         memory: noise pre-whitening.  With ``virtual_coils=V`` it is folded into every slice's matrix on the slot's stream
-        (cine_coil_matrix_whitened); alone it is ``coil_matrix=W.to(torch.complex64)``; with ``coil_matrix`` it raises."""
+        (cine_coil_matrix_whitened); alone it is ``coil_matrix=W.to(torch.complex64)``; with ``coil_matrix`` it raises.
+        ``noise=noise.NoiseSpec(chol, scale, seed, replica)``: one pseudo replica with the noise where a receiver's enters -- the slot's
+        stream runs cine_noise_add_raw in place on the slot's copy of the raw data, behind the wait for the copy and in front of
+        everything else, so with ``virtual_coils=`` the Gram matrix and the (whitened) matrix are computed from the noisy slice, as a
+        scanner would compute them.  The result is ``model(frontend.prepare_masked_slice(noise.add_noise_raw(raw[:n], chol,
+        noise_mask=noise_mask, scale=scale, seed=seed, replica=replica), mask, <the same front-end arguments>), mask[, sens_maps])``,
+        bit for bit; the caller's array is never written.  ``noise_mask``: the acquired samples, uint8 or bool (n | 1, x) or
+        (n | 1, x, y) on the n kept frames, from any of the places an input may lie in -- None for fully sampled raw that is masked
+        retrospectively (``apply_mask=True``), needed for prospectively undersampled raw (``apply_mask=False``), whose unacquired lines
+        hold zeros and carry no noise.  Neither is part of the set key; ``noise=None`` takes the path it always took."""
         if self._closed:
             raise CineHipError("SlicePipeline: submit_raw after close()")
         src = _RawSource(self, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask,
-                         ecalib_r, sign_iters, virtual_coils, cc_region, whitener)
+                         ecalib_r, sign_iters, virtual_coils, cc_region, whitener, noise, noise_mask)
         if src.vc is not None:
             try:
                 hash(tag)
@@ -917,7 +964,13 @@ class SlicePipeline:
         st = self._set
         cs = self.copy_stream
         keep = []
-        items = src.items(st.bufs[key])
+        b = st.bufs[key]
+        if getattr(src, "nmask", None) is not None and b.get("nmask") is None:
+            # the mask of a raw replica: no graph holds it, so the buffer is made when a slot first needs one; like the set's other
+            # buffers it comes from the pool of the caller's stream
+            b["nmask"] = torch.empty(src.nmask_nbytes, device=self.device, dtype=torch.uint8)
+            cs.wait_stream(torch.cuda.current_stream(self.device))
+        items = src.items(b)
         stage = None
         if any(kind == "pageable" for _, _, _, kind in items):
             r, stage = self._staging(items)
@@ -933,7 +986,7 @@ class SlicePipeline:
                 if kind == "pageable":
                     dst.copy_(stage[name], non_blocking=True)
                 elif kind == "device":
-                    dst.copy_(x.expand(dst.shape) if name == "mask" else x, non_blocking=True)
+                    dst.copy_(x.expand(dst.shape) if name in ("mask", "nmask") else x, non_blocking=True)
                     x.record_stream(cs)
                     keep.append(x)
                 else:
@@ -952,8 +1005,14 @@ class SlicePipeline:
         s = self.streams[key[0]]
         with torch.cuda.stream(s):
             s.wait_event(st.ready[key])
+            if src.noise is not None and src.raw is not None:                # a raw replica: in place on the slot's raw data, in front of all
+                from . import noise as N
+                b, ns = st.bufs[key], src.noise
+                rv = src.raw_view(b)
+                N.add_noise_raw(rv, ns.chol, noise_mask=None if src.nmask is None else src.nmask_view(b), scale=ns.scale, seed=ns.seed,
+                                replica=ns.replica, out=rv)
             self._pre(st.bufs[key], src)
-            if src.noise is not None:               # a pseudo replica: in place on the slot's k-space, in front of the replay
+            if src.noise is not None and src.raw is None:                    # a pseudo replica: in place on the slot's k-space, in front of the replay
                 from . import noise as N
                 b, ns = st.bufs[key], src.noise
                 N.add_noise(b["mk"], b["mask"], ns.chol, scale=ns.scale, seed=ns.seed, replica=ns.replica, out=b["mk"])

@@ -2,6 +2,7 @@
 // counterpart (the reference has no noise model):
 //   cine_noise_add       : out = kspace + eta at the sampled points, eta complex normal with covariance scale^2 L L^H, drawn from
 //                          Philox4x32-10 keyed by (seed, replica, k-space point, coil) -- philox.h, the definition in include/cine_hip.h
+//   cine_noise_add_raw   : the same values on raw data (t, nx, ny, c), coil fastest, in front of the front-end
 //   cine_replica_accum   : Welford's running mean / sum of squared deviations over the replicas, float64
 //   cine_replica_finish  : mean, standard deviation, SNR and g-factor maps from the two
 // One pass over the sampled points.  A workgroup owns 64 consecutive points of one row (lanes along w, 8-byte accesses, a wave reads
@@ -102,6 +103,122 @@ __global__ __launch_bounds__(kNoiseThreads) void noise_add_kernel(NoiseArgs a) {
     }
 }
 
+// The same noise on the raw layout (t, nx, ny, c) with the coil index fastest.  Lanes along the points with a coil stride of one
+// element would store 8 bytes at a stride of 8 c, so the values go through LDS: a workgroup owns 64 consecutive flat points, whose
+// 64 c values are ONE contiguous span.  Phases one and two are those of noise_add_kernel (wave g draws the pairs g, g + 4, ... into
+// z[coil][point], then lane = point forms eta_i, i = g, g + 4, ..., in registers); L and z are dead after the chain, so behind a
+// barrier the etas are written over them as eta[point][coil] with the row padded to an odd number of 8-byte words (lanes along the
+// points: conflict-free), and behind another the four waves walk the span, consecutive lanes on consecutive elements.  The span's
+// values are loaded into registers in that order before anything else, so their latency lies under the arithmetic.  A run may
+// straddle lines and frames: the mask is looked up per point, and the ballot of the 64 flags is the same in every wave.
+struct NoiseRawArgs {
+    const float2* raw; float2* out; const uint8_t* mask; const float2* chol; const long* replica_dev;
+    float scale, inv_c; long seed, replica; uint64_t point0; long npoints;
+    int mask_ny, c, ny;
+};
+
+// kSlots: the coils a lane holds between the two barriers and the span elements it holds from the start, 8 up to 32 coils and 16 up to
+// 64 (where the LDS, not the registers, bounds the residency).
+template <int kSlots>
+__global__ __launch_bounds__(kNoiseThreads) void noise_add_raw_kernel(NoiseRawArgs a) {
+    extern __shared__ float2 noise_lds[];                    // with chol: L (c x c), then z[c][64]; then eta[64][c | 1] over both
+    const int tid = threadIdx.x, pt = tid & (kNoisePoints - 1), g = tid / kNoisePoints, c = a.c, cs = c | 1;
+    const long base = (long)blockIdx.x * kNoisePoints;       // the first flat point (frame * nx + x) * ny + y of the run
+    const long q = base + pt;
+    const long left = a.npoints - base;
+    const int count = (int)(left < kNoisePoints ? left : kNoisePoints) * c;       // elements of the span
+    const long span = base * c;
+    const bool inplace = a.out == a.raw;
+    bool on = q < a.npoints;
+    if (on && a.mask) on = a.mask[a.mask_ny == 1 ? (long)((uint64_t)q / (uint32_t)a.ny) : q] != 0;
+    const unsigned long long flags = __ballot(on);           // lane = point in every wave: uniform over the workgroup
+    if (!flags) {                                            // nothing sampled in the run
+        if (!inplace)
+            for (int e = tid; e < count; e += kNoiseThreads) a.out[span + e] = a.raw[span + e];
+        return;
+    }
+    // the lane's elements of the span, loaded ahead of the arithmetic they are added to (in place: the sampled ones only)
+    // e / c for e < 64 * 64, c <= 64: (e + 0.5) / c is at least 1 / 128 away from an integer, the two roundings move it by < 1e-5
+    const float inv_c = a.inv_c;
+    float2 kv[kSlots];
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) {
+        const int e = tid + s * kNoiseThreads;
+        kv[s] = make_float2(0.f, 0.f);
+        if (e < count && (!inplace || ((flags >> (int)(((float)e + 0.5f) * inv_c)) & 1))) kv[s] = a.raw[span + e];
+    }
+    const long replica = a.replica_dev ? *a.replica_dev : a.replica;
+    const uint64_t p = a.point0 + (uint64_t)q;
+    const float scale = a.scale;
+    float2* eta = noise_lds;
+    if (!a.chol) {                                           // white: eta_i = scale z_i
+        if (on)
+            for (int j = g; 2 * j < c; j += kNoiseGroups) {
+                const Philox4 v = philox_point(a.seed, replica, p, j);
+                const PhiloxNormal z0 = philox_normal(v.x[0], v.x[1]);
+                const float er0 = scale * z0.re, ei0 = scale * z0.im;
+                eta[pt * cs + 2 * j] = make_float2(er0, ei0);
+                if (2 * j + 1 < c) {
+                    const PhiloxNormal z1 = philox_normal(v.x[2], v.x[3]);
+                    const float er1 = scale * z1.re, ei1 = scale * z1.im;
+                    eta[pt * cs + 2 * j + 1] = make_float2(er1, ei1);
+                }
+            }
+    } else {
+        const float2* L = noise_lds;
+        float2* z = noise_lds + c * c;
+        for (int i = tid; i < c * c; i += kNoiseThreads) noise_lds[i] = a.chol[i];
+        if (on)
+            for (int j = g; 2 * j < c; j += kNoiseGroups) {
+                const Philox4 v = philox_point(a.seed, replica, p, j);
+                const PhiloxNormal z0 = philox_normal(v.x[0], v.x[1]);
+                z[(2 * j) * kNoisePoints + pt] = make_float2(z0.re, z0.im);
+                if (2 * j + 1 < c) {
+                    const PhiloxNormal z1 = philox_normal(v.x[2], v.x[3]);
+                    z[(2 * j + 1) * kNoisePoints + pt] = make_float2(z1.re, z1.im);
+                }
+            }
+        __syncthreads();                                     // L and the normals of every coil of the 64 points
+        float2 mine[kSlots];
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            const int i = g + s * kNoiseGroups;
+            float re = 0.f, im = 0.f;
+            if (on && i < c)
+                for (int kk = 0; kk <= i; ++kk) {
+                    const float2 l = L[i * c + kk], zz = z[kk * kNoisePoints + pt];
+                    PhiloxNormal zn;
+                    zn.re = zz.x; zn.im = zz.y;
+                    philox_cfma(re, im, l.x, l.y, zn);
+                }
+            const float er = scale * re, ei = scale * im;
+            mine[s] = make_float2(er, ei);
+        }
+        __syncthreads();                                     // L and z are read: eta goes over them
+        if (on) {
+#pragma unroll
+            for (int s = 0; s < kSlots; ++s) {
+                const int i = g + s * kNoiseGroups;
+                if (i < c) eta[pt * cs + i] = mine[s];
+            }
+        }
+    }
+    __syncthreads();                                         // eta[point][coil] of the sampled points
+#pragma unroll
+    for (int s = 0; s < kSlots; ++s) {
+        const int e = tid + s * kNoiseThreads;
+        if (e < count) {
+            const int ep = (int)(((float)e + 0.5f) * inv_c), coil = e - ep * c;
+            if ((flags >> ep) & 1) {
+                const float2 et = eta[ep * cs + coil];
+                a.out[span + e] = make_float2(kv[s].x + et.x, kv[s].y + et.y);
+            } else if (!inplace) {
+                a.out[span + e] = kv[s];
+            }
+        }
+    }
+}
+
 __global__ void replica_accum_kernel(const float* x, double* mean, double* m2, long n, int k) {
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long)gridDim.x * blockDim.x) {
         const double v = (double)x[e];
@@ -187,6 +304,42 @@ extern "C" int cine_noise_add(const float* kspace, float* out, const uint8_t* ma
     const long rows = bt * h;
     noise_launch(a, rows, st);
     return check_launch("noise_add_kernel");
+}
+
+extern "C" int cine_noise_add_raw(const float* raw, float* out, const uint8_t* mask, int mask_ny, const float* chol, float scale,
+                                  long seed, long replica, const long* replica_dev, long point0, long t, int nx, int ny, int c, void* stream) {
+    const char* what = "cine_noise_add_raw";
+    constexpr long kMaxPoints = (long)INT_MAX * kNoisePoints;                // one workgroup per 64 points, the grid's x limit
+    CINE_REQUIRE(raw && out, CINE_EINVAL, "%s: null pointer", what);
+    CINE_REQUIRE(t > 0 && nx > 0 && ny > 0 && c > 0, CINE_EINVAL, "%s: Invalid shapes t %ld nx %d ny %d c %d", what, t, nx, ny, c);
+    CINE_REQUIRE(c <= kNoiseMaxCoils, CINE_EUNSUPPORTED, "%s: %d coils, at most %d", what, c, kNoiseMaxCoils);
+    CINE_REQUIRE(t <= kMaxPoints / ((long)nx * ny), CINE_EUNSUPPORTED, "%s: t * nx * ny = %ld * %d * %d points, at most %ld", what, t, nx, ny,
+                 kMaxPoints);
+    CINE_REQUIRE(mask_ny == 1 || mask_ny == ny, CINE_EINVAL, "%s: mask_ny %d is neither 1 nor ny = %d", what, mask_ny, ny);
+    CINE_REQUIRE(replica >= 0 && replica <= 0xffffffffL, CINE_EINVAL, "%s: replica %ld outside [0, 2^32)", what, replica);
+    CINE_REQUIRE(point0 >= 0, CINE_EINVAL, "%s: point0 %ld is negative", what, point0);
+    CINE_REQUIRE(((uintptr_t)raw | (uintptr_t)out | (uintptr_t)chol) % 8 == 0, CINE_EINVAL, "%s: raw, out and chol must be 8-byte aligned", what);
+    CINE_REQUIRE(!replica_dev || (uintptr_t)replica_dev % 8 == 0, CINE_EINVAL, "%s: replica_dev must be 8-byte aligned", what);
+    const long npoints = t * nx * ny;
+    const size_t bytes = (size_t)npoints * c * 2 * sizeof(float);
+    const uintptr_t r0 = (uintptr_t)raw, o0 = (uintptr_t)out;
+    CINE_REQUIRE(r0 == o0 || r0 + bytes <= o0 || o0 + bytes <= r0, CINE_EINVAL, "%s: out overlaps raw without being raw", what);
+    NoiseRawArgs a;
+    a.raw = reinterpret_cast<const float2*>(raw); a.out = reinterpret_cast<float2*>(out); a.mask = mask;
+    a.chol = reinterpret_cast<const float2*>(chol); a.replica_dev = replica_dev;
+    a.scale = scale; a.inv_c = 1.0f / (float)c; a.seed = seed; a.replica = replica; a.point0 = (uint64_t)point0; a.npoints = npoints;
+    a.mask_ny = mask ? mask_ny : 1; a.c = c; a.ny = ny;
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(F_MISC, st);
+    // eta[64][c | 1] lies over L and z[c][64]: 64 KB at 64 coils, what a launch gets without opting in
+    const size_t eta = (size_t)kNoisePoints * (c | 1), chain = chol ? (size_t)c * c + (size_t)c * kNoisePoints : 0;
+    const dim3 grid((unsigned)ceil_div(npoints, (long)kNoisePoints));
+    const size_t lds = (eta > chain ? eta : chain) * sizeof(float2);
+    if (c <= 8 * kNoiseGroups)
+        hipLaunchKernelGGL(noise_add_raw_kernel<8>, grid, dim3(kNoiseThreads), lds, st, a);
+    else
+        hipLaunchKernelGGL(noise_add_raw_kernel<16>, grid, dim3(kNoiseThreads), lds, st, a);
+    return check_launch("noise_add_raw_kernel");
 }
 
 extern "C" int cine_replica_accum(const float* x, double* mean, double* m2, long n, int k, void* stream) {

@@ -1177,6 +1177,19 @@ int cine_llr_solve(float* x, const float* zf, const float* sens, const float* se
  * the same bits on every call. */
 int cine_noise_add(const float* kspace, float* out, const uint8_t* mask, int mask_w, const float* chol, float scale,
                    long seed, long replica, const long* replica_dev, long point0, long bt, int c, int h, int w, void* stream);
+/* The same noise on RAW data, in front of the front-end: raw, out (t, nx, ny, c, 2) with the coil index fastest, the layout
+ * cine_raw_ingest and cine_coil_compress read.  The k-space point of a sample is p = point0 + (frame * nx + x) * ny + y, and the value
+ * added to coil i of it is the eta_i defined above for (seed, replica, p, i): permute any input to (t, c, h = nx, w = ny), call
+ * cine_noise_add with the same (seed, replica, point0, chol, scale, mask), permute back, and the bits are these.  mask: uint8 (t, nx)
+ * for mask_ny == 1 (the acquired lines) or (t, nx, ny) for mask_ny == ny; NULL: every sample (mask_ny is still checked: pass 1).
+ * out == raw works in place and neither reads nor writes a sample that is not sampled; out of place those are copied bit for bit; any
+ * other overlap is CINE_EINVAL.  chol, replica, replica_dev, point0: as for cine_noise_add.  A workgroup owns 64 consecutive points,
+ * whose 64 * c values are one contiguous span of raw, and walks it with consecutive lanes on consecutive 8-byte elements.
+ * CINE_EINVAL: null raw / out, non-positive sizes, mask_ny outside {1, ny}, replica outside [0, 2^32), a negative point0, a pointer
+ * off its 8-byte alignment.  CINE_EUNSUPPORTED: more than 64 coils, more than 64 * (2^31 - 1) points.  Every argument is checked
+ * before the launch; no allocation, no host read, no atomics: capturable, and the same bits on every call. */
+int cine_noise_add_raw(const float* raw, float* out, const uint8_t* mask, int mask_ny, const float* chol, float scale,
+                       long seed, long replica, const long* replica_dev, long point0, long t, int nx, int ny, int c, void* stream);
 /* Welford's update of (mean, m2) with the k-th sample x, k >= 1, element-wise over n floats, in float64:
  *   d = x - mean;  mean += d / k;  m2 += d * (x - mean)
  * k == 1 initialises both buffers (they are not read and need not be zeroed).  Null pointers, n <= 0, k < 1, mean == m2: CINE_EINVAL. */

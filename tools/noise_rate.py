@@ -13,7 +13,12 @@ outside the centre rows, so the mask varies along w; "none" = every point.  hipE
   * the composed torch path of one replica: torch.randn + einsum with L + mask multiply + add;
   * replicas per second for 64 replicas of the cfg-2 model (XF-VarNet, 6 cascades) through a 10-slot SlicePipeline with ``noise=``,
     the same 64 submissions without it, and the sequential loop (``pseudo_replica`` without a pipeline).
---out writes the document, stamped with the commit and a sha256 over csrc/."""
+--out writes the document, stamped with the commit and a sha256 over csrc/.
+
+    python tools/noise_rate.py --raw [--out profiles/noise_raw_rate.json] [--commit SHA]
+
+Noise on RAW data, in front of the front-end (``raw_main``): cine_noise_add_raw against cine_noise_add at equal element counts, and the
+replicas of a raw scan through ``submit_raw(..., noise=)``."""
 import argparse
 import json
 import os
@@ -77,11 +82,137 @@ def masks(dev):
     return {"row": row.to(dev), "plane": plane.contiguous().to(dev), "none": None}
 
 
+RAW_SHAPES = ((15, 416, 208, 30), (15, 384, 144, 15))       # (t, x, y, coil): the two raw matrix sizes of tools/pipeline_rate.py --raw
+RAW_SCAN, RAW_CROP = (15, 384, 144, 15), (200, 144)         # the scan the replicas of the pipeline start from
+
+
+def raw_main(args):
+    """--raw: noise in front of the front-end.  cine_noise_add_raw alone, in place, coloured and white, every sample acquired, at the two
+    raw sizes; in the same run cine_noise_add with every point sampled at the same element count ((t, c, h = x, w = y), what the raw
+    kernel's values are defined by), the two timed in turn, and the composed torch path (randn + einsum + add) on the raw layout; then replicas per second of
+    the cfg-2 model through a 10-slot pipeline from device-resident raw data, with and without ``noise=``."""
+    import numpy as np
+    import reconstruction.models as M
+    from cine_hip import noise as N, ops, synth
+    from cine_hip.pipeline import SlicePipeline
+    from pipeline_rate import _stamp
+    dev = torch.device("cuda:0")
+    commit, csrc = _stamp(args.commit)
+    doc = {"what": "cine_noise_add_raw on (t, x, y, coil) raw data beside cine_noise_add on (t, coil, x, y) at equal element counts",
+           "device": torch.cuda.get_device_name(dev), "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "steps": STEPS,
+           "commit": commit, "csrc_sha256": csrc, "margin": 1.25, "kernels": []}
+
+    def event_ms(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(); fn(); b.record()
+        b.synchronize()
+        return a.elapsed_time(b)
+
+    def timed_pair(fa, fb, moved):
+        """The two calls timed in turn, so that a drift of the clocks or of the machine's load falls on both: STEPS single calls each
+        between an event pair of their own, then 5 bursts each of BURST calls back to back between one pair."""
+        for _ in range(3):
+            fa(); fb()
+        torch.cuda.synchronize()
+        ms = ([], [])
+        for _ in range(STEPS):
+            ms[0].append(event_ms(fa)); ms[1].append(event_ms(fb))
+        bursts = ([], [])
+        for _ in range(5):
+            for k, fn in enumerate((fa, fb)):
+                bursts[k].append(event_ms(lambda: [fn() for _ in range(BURST)]) / BURST)
+        out = []
+        for k in (0, 1):
+            r = {"median_ms": median(ms[k]), "ms": ms[k], "bytes_moved": moved, "burst_ms_per_call": median(bursts[k])}
+            r["burst_tb_per_s"] = moved / (r["burst_ms_per_call"] * 1e-3) / 1e12
+            out.append(r)
+        return out
+
+    with torch.no_grad():
+        one = torch.ones(1, device=dev)
+        doc["event_pair_floor"] = {"median_ms": median(measure(lambda: ops.scale_(one, 1.0))), "burst_ms_per_call": burst(lambda: ops.scale_(one, 1.0))}
+        for t, nx, ny, c in RAW_SHAPES:
+            rs = np.random.RandomState(c)
+            a = (rs.standard_normal((c, 2 * c)) + 1j * rs.standard_normal((c, 2 * c))) / np.sqrt(4 * c)
+            low = N.noise_cholesky(torch.from_numpy(a @ a.conj().T + 0.25 * np.eye(c)))
+            raw = torch.empty((t, nx, ny, c, 2), dtype=torch.float32, device=dev).normal_()
+            planar = torch.empty((t, c, nx, ny, 2), dtype=torch.float32, device=dev).normal_()
+            moved = 2 * raw.numel() * 4
+            row = {"raw_shape": [t, nx, ny, c], "elements": raw.numel() // 2, "bytes": raw.numel() * 4}
+            for key, chol in (("coloured", low), ("white", None)):
+                row[f"noise_add_raw_{key}"], row[f"noise_add_{key}"] = timed_pair(
+                    lambda: N.add_noise_raw(raw, chol, scale=0.01, seed=1, replica=2, out=raw),
+                    lambda: N.add_noise(planar, None, chol, scale=0.01, seed=1, replica=2, out=planar), moved)
+                for stat in ("median_ms", "burst_ms_per_call"):
+                    row[f"raw_over_planar_{key}_{stat}"] = row[f"noise_add_raw_{key}"][stat] / row[f"noise_add_{key}"][stat]
+            row["within_margin"] = bool(max(row["raw_over_planar_coloured_median_ms"], row["raw_over_planar_white_median_ms"]) <= doc["margin"])
+            lc = torch.view_as_complex(N._chol_pairs(low, c, dev)).tril()
+            rc = torch.view_as_complex(raw)
+
+            def composed():
+                z = torch.view_as_complex(torch.randn(t, nx, ny, c, 2, device=dev)) * (0.5 ** 0.5)
+                return rc + torch.einsum("ij,txyj->txyi", lc, z) * 0.01
+            ms = measure(composed)
+            row["composed_torch"] = {"median_ms": median(ms), "ms": ms}
+            row["composed_over_noise_add_raw"] = row["composed_torch"]["median_ms"] / row["noise_add_raw_coloured"]["median_ms"]
+            doc["kernels"].append(row)
+            print(json.dumps({"kernel": row}), flush=True)
+            del raw, planar, rc
+        # replicas of one raw scan through the pipeline: the same submissions with and without noise=
+        t, nx, ny, c = RAW_SCAN
+        rs = np.random.RandomState(1)
+        raw = torch.from_numpy((1e-6 * rs.standard_normal(RAW_SCAN + (2,))).astype(np.float32)).to(dev)
+        a = (rs.standard_normal((c, 2 * c)) + 1j * rs.standard_normal((c, 2 * c))) / np.sqrt(4 * c)
+        low = N.noise_cholesky(torch.from_numpy(a @ a.conj().T + 0.25 * np.eye(c)))
+        mask = torch.zeros(1, t, 1, RAW_CROP[0], 1, 1, dtype=torch.uint8)
+        for f in range(t):
+            mask[0, f, 0, f % 4::4] = 1
+        mask[:, :, :, RAW_CROP[0] // 2 - 8:RAW_CROP[0] // 2 + 8] = 1
+        mask = mask.to(dev)
+        model = M.VarNet(6, 8, 3, 16, 3, "XF").eval()
+        synth.fill_parameters_(model, 1, keep=("lambda",))
+        model = model.to(dev)
+        kw = dict(crop_shape=RAW_CROP, n_frames=t)
+        runs = {"in_flight_noise": [], "in_flight_plain": []}
+        with SlicePipeline(model, slots=SLOTS) as pipe:
+            pipe.submit_raw(raw, mask, tag="build", **kw)
+            list(pipe.drain())
+            for _ in range(3):
+                for key in runs:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for r in range(REPLICAS):
+                        pipe.submit_raw(raw, mask, tag=r, noise=N.NoiseSpec(low, 1e-8, 1, r) if key == "in_flight_noise" else None, **kw)
+                        for _ in pipe.results():
+                            pass
+                    list(pipe.drain())
+                    torch.cuda.synchronize()
+                    runs[key].append(REPLICAS / (time.perf_counter() - t0))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            maps = N.pseudo_replica_raw(model, raw, mask, chol=low, scale=1e-8, replicas=REPLICAS, seed=1, pipeline=pipe, **kw)
+            torch.cuda.synchronize()
+            runs["pseudo_replica_raw_in_flight"] = [REPLICAS / (time.perf_counter() - t0)]
+            assert pipe.set_builds == 1
+        doc["replicas"] = {"model": "XF-VarNet cfg 2 (6 cascades)", "raw_shape": list(RAW_SCAN), "crop": list(RAW_CROP), "slots": SLOTS,
+                           "replicas": REPLICAS, "raw_from": "device", "replicas_per_s": {k: median(v) for k, v in runs.items()}, "runs": runs,
+                           "noise_over_plain": median(runs["in_flight_noise"]) / median(runs["in_flight_plain"]),
+                           "median_snr": float(maps.snr.median())}
+        print(json.dumps({"replicas": doc["replicas"]}), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None, help="the commit to stamp the result with (default: git rev-parse HEAD)")
+    ap.add_argument("--raw", action="store_true", help="noise on raw data, in front of the front-end (profiles/noise_raw_rate.json)")
     args = ap.parse_args()
+    if args.raw:
+        return raw_main(args)
     import numpy as np
     import reconstruction.models as M
     from cine_hip import noise as N, ops, synth
