@@ -106,6 +106,14 @@ the raw data, behind the wait for the copy and in front of the coil compression 
 (``virtual_coils=``: the matrix of the noisy slice), crop, filter, mask and calibration as a scan's own does.  ``noise_mask`` (the acquired
 samples; for prospectively undersampled raw) is an input like the others, with a per-slot buffer that is made on first use.
 
+``submit_readouts(lines, plan, mask, ...)``: the slice from its ACQUISITION LIST (``cine_hip.gating``): the readouts (n_lines, y, coil) that
+were acquired and a ``GatingPlan``, the sparse matrix that sorts them into cardiac phases.  Only the readouts and the plan's three CSR arrays
+are copied, on the copy stream, into buffers of the (slot, parity); the slot's stream runs cine_gate_readouts into the slot's raw buffer
+behind the wait for the copy, in front of cine_noise_add_raw and the coil compression, and everything downstream is ``submit_raw``'s path:
+the result is bit for bit ``submit_raw(gating.gate_readouts(lines, plan), mask, apply_mask=False, n_frames=plan.n_frames, ...)``.  The set
+key is that call's key, so both may alternate on one set; the readout count and the entry count are not part of it -- the gating
+buffers are made when a set first serves readouts and replaced by larger ones, after a drain, like the raw buffers.
+
 ``graphs=False`` is the explicit eager mode: same slots, streams, buffers, copies and events, with the launch sequence
 enqueued on the slot's stream for every slice.  A failure raises ``CineHipError``; nothing falls back to eager launches.
 
@@ -411,7 +419,13 @@ class _RawSource:
     input_names = ("raw", "mask", "sens", "cmat", "wh")
 
     def __init__(self, pipe, raw, mask, sens_maps, crop_shape, n_frames, filter_size, scaling, coil_matrix, apply_mask, ecalib_r=15,
-                 sign_iters=60, virtual_coils=None, cc_region=24, whitener=None, noise=None, noise_mask=None):
+                 sign_iters=60, virtual_coils=None, cc_region=24, whitener=None, noise=None, noise_mask=None, gate=None):
+        self.gate = None                                # submit_readouts: (lines as pairs, their kind, the plan, its host tensors)
+        if gate is not None:
+            raw = _check_readouts(self, *gate)          # the gated array's shape on the meta device: the slot's stream writes the data
+            n_frames = raw.shape[0]
+            if noise is not None and noise_mask is None:
+                noise_mask = gate[1].acquired           # the lines the gating filled
         if not isinstance(raw, (np.ndarray, torch.Tensor)):
             raise CineHipError(f"raw: expected a torch tensor or a numpy array, got {type(raw).__name__}")
         if raw.ndim < 4 or raw.shape[0] < 1 or int(n_frames) < 1:
@@ -483,6 +497,8 @@ class _RawSource:
         _same_device(pipe, (("raw", self.raw), ("mask", self.mask), ("sens_maps", self.sens), ("coil_matrix", self.cmat),
                             ("whitener", self.wh), ("noise_mask", self.nmask)))
         self.raw_nbytes = x.numel() * 4
+        if self.gate is not None:
+            _same_device(pipe, (("lines", self.gate[0]),))
         self.gram_nbytes = 0                                                 # asked of the library when a buffer is needed (_submit, alloc)
         self.key = raw_set_key((n, nx, ny, c), n, self.crop, self.filter, self.scaling, self.apply_mask, self.mask_shape,
                                None if self.sens is None else self.sens.shape, None if self.cmat is None else self.cmat.shape, self.espirit,
@@ -532,8 +548,21 @@ class _RawSource:
     def nmask_view(self, b):
         return b["nmask"][:math.prod(self.nmask_shape)].view(self.nmask_shape)
 
+    def gate_views(self, b):
+        """(lines, row_ptr, index, weight) of this slice in the gating buffers of set b."""
+        lines, _, plan, host = self.gate
+        return (b["lines"][:max(lines.numel(), 2) * 4].view(torch.float32), b["rptr"][:host[0].numel()], b["gidx"][:host[1].numel()],
+                b["gw"][:host[2].numel()])
+
     def items(self, b):
-        it = [("raw", self.raw_view(b), self.raw, self.raw_kind), ("mask", b["mask"], self.mask, self.mask_kind)]
+        if self.gate is None:
+            it = [("raw", self.raw_view(b), self.raw, self.raw_kind)]
+        else:                                            # the readouts and the plan in place of the binned array
+            lines, kind, _, host = self.gate
+            lv, rp, gi, gw = self.gate_views(b)
+            it = [("lines", lv[:lines.numel()].view(lines.shape), lines, kind)] if lines.numel() else []
+            it += [("rptr", rp, host[0], "pinned"), ("gidx", gi, host[1], "pinned"), ("gw", gw, host[2], "pinned")]
+        it.append(("mask", b["mask"], self.mask, self.mask_kind))
         if self.nmask is not None:
             it.append(("nmask", self.nmask_view(b), self.nmask, self.nmask_kind))
         if self.sens is not None:
@@ -543,6 +572,30 @@ class _RawSource:
         if self.wh is not None:
             it.append(("wh", torch.view_as_real(self.wh_view(b)), self.wh, self.wh_kind))
         return it
+
+
+def _check_readouts(src, lines, plan):
+    """``submit_readouts``'s readouts against its plan.  Files (lines as float32 pairs, their kind, the plan, its host tensors) under
+    ``src.gate`` and returns a tensor without storage of the gated array's shape (n_frames, nx, ny, coil, 2)."""
+    from . import gating
+    if not isinstance(plan, gating.GatingPlan):
+        raise CineHipError(f"plan: expected a cine_hip.gating.GatingPlan (gating.plan_gating), got {type(plan).__name__}")
+    x, kind = _pairs(lines, "lines")
+    if x.dim() != 4 or x.shape[1] < 1 or x.shape[2] < 1:
+        raise CineHipError(f"lines: shape {tuple(x.shape)}; expected (n_lines, y, coil) complex64 or (n_lines, y, coil, 2) float32")
+    if x.shape[0] != plan.n_lines:
+        raise CineHipError(f"lines: {x.shape[0]} readouts, the plan was made for {plan.n_lines}")
+    if kind == "device" and not x.is_contiguous():
+        x = x.contiguous()
+    src.gate = (x, kind, plan, plan.host_tensors())
+    src.input_names = ("lines", "rptr", "gidx", "gw") + _RawSource.input_names[1:]       # what a new set copies to its other buffer sets
+    return torch.empty((plan.n_frames, plan.nx, x.shape[1], x.shape[2], 2), dtype=torch.float32, device="meta")
+
+
+def _gate_capacity(src):
+    """(bytes of readouts, CSR entries, row pointers) the gating buffers must hold for this slice; the last is fixed by the set key."""
+    lines, _, _, host = src.gate
+    return max(lines.numel(), 2) * 4, host[1].numel(), host[0].numel()
 
 
 def _check_noise_mask(noise_mask, spec, n: int, nx: int, ny: int):
@@ -608,10 +661,11 @@ class _Set:
 
     def __init__(self, key):
         self.key = key
-        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front", "wh" in a raw set; "gram", "gws", "lam", "cinfo" with virtual_coils=)
+        self.bufs = {}          # (slot, parity) -> {"mk", "mask", "sens"} (+ "raw", "cmat", "cc", "front", "wh" in a raw set; "gram", "gws", "lam", "cinfo" with virtual_coils=; "lines", "rptr", "gidx", "gw" once it serves readouts)
         self.raw = None         # the front-end's settings when the graphs start from raw data (the _RawSource that built the set)
         self.raw_bytes = 0      # capacity of each raw byte buffer
         self.gram_bytes = 0     # capacity of each Gram workspace (virtual_coils=)
+        self.gate_cap = (0, 0)  # capacity of the gating buffers (submit_readouts): bytes of readouts, CSR entries; 0: none yet
         self.espirit = None     # espirit_key(...) when the graphs calibrate the maps themselves (sens_maps="espirit")
         self.graphs = {}        # (slot, parity) -> (graph, static outputs)
         self.ready = {}         # (slot, parity) -> event recorded on the copy stream behind the copy into the set
@@ -710,6 +764,29 @@ class SlicePipeline:
                 raise CineHipError(f"virtual_coils: tag {tag!r} is not hashable (last_coil_info is keyed by it)") from None
         return self._submit(src, tag)
 
+    def submit_readouts(self, lines, plan, mask, sens_maps=None, tag=None, *, crop_shape=(200, 200),
+                        filter_size=(0.7, 0.0, 0.3, 0.3), scaling: float = 1e6, coil_matrix=None, ecalib_r: int = 15, sign_iters: int = 60,
+                        virtual_coils: Optional[int] = None, cc_region: int = 24, whitener=None, noise=None, noise_mask=None) -> SliceHandle:
+        """Enqueue one slice from its ACQUISITION LIST: ``lines`` (n_lines, y, coil) complex64 or float32 pairs, the readouts in the order
+        ``plan`` (``gating.plan_gating``) was made for, in any of the four places ``submit_raw`` takes its input from.  Only the readouts
+        and the plan's CSR arrays are copied to the device; the slot's stream gates them (cine_gate_readouts) into the slot's raw buffer
+        behind the wait for the copy and in front of everything ``submit_raw`` runs there.  The result is, bit for bit,
+        ``submit_raw(gating.gate_readouts(lines, plan), mask, sens_maps, apply_mask=False, n_frames=plan.n_frames, <the same keywords>)``
+        -- gated data are prospectively undersampled, so ``mask`` (the plan's pattern on the crop grid, for the model's data consistency)
+        is not applied by the front-end.  The keywords are ``submit_raw``'s.  With ``noise=``, ``noise_mask`` defaults to
+        ``plan.acquired``: the lines the gating filled carry noise, the empty ones stay zero.  The set key is that ``submit_raw``
+        call's; ``n_lines`` and the plan's entry count are not part of it, and ``set_builds`` does not move when they change."""
+        if self._closed:
+            raise CineHipError("SlicePipeline: submit_readouts after close()")
+        src = _RawSource(self, None, mask, sens_maps, crop_shape, 0, filter_size, scaling, coil_matrix, False, ecalib_r, sign_iters,
+                         virtual_coils, cc_region, whitener, noise, noise_mask, gate=(lines, plan))
+        if src.vc is not None:
+            try:
+                hash(tag)
+            except TypeError:
+                raise CineHipError(f"virtual_coils: tag {tag!r} is not hashable (last_coil_info is keyed by it)") from None
+        return self._submit(src, tag)
+
     @property
     def set_builds(self) -> int:
         """How many graph sets this pipeline has built so far (one per change of the set key)."""
@@ -725,6 +802,10 @@ class SlicePipeline:
             elif src.raw is not None and (src.raw_nbytes > self._set.raw_bytes or src.gram_bytes() > self._set.gram_bytes):
                 # a scan with more coils than any before it (coil_matrix or virtual_coils given)
                 self._grow_raw(max(src.raw_nbytes, self._set.raw_bytes), max(src.gram_bytes(), self._set.gram_bytes))
+            if src.raw is not None and src.gate is not None:
+                need, have = _gate_capacity(src), self._set.gate_cap
+                if need[0] > have[0] or need[1] > have[1]:                  # the set's first readouts, or more of them than before
+                    self._grow_gate(max(need[0], have[0]), max(need[1], have[1]), need[2])
             k0 = self._sched.must_retire()
             if k0 is not None:
                 self._recs[k0][0]._event.synchronize()
@@ -825,10 +906,21 @@ class SlicePipeline:
                 raise CineHipError(f"SlicePipeline: {type(self.model).__name__}.forward returned {type(o).__name__}, not a tensor")
             return (o, ops.zero_filled_rss(b["mk"])) if self.zero_filled else (o,)
 
-    def _pre(self, b, src) -> None:
-        """What runs eagerly on the slot's stream in front of the graph: with a coil matrix, the compression of this scan's raw data
-        (any coil count) into the static (T, x, y, V) buffer the graph starts from; with virtual_coils= the Gram matrix and the
-        matrix of this slice in front of it (with whitener= the whitened matrix, from the copied whitener)."""
+    def _pre(self, b, src, noise: bool = False) -> None:
+        """What runs eagerly on the slot's stream in front of the graph: for readouts (submit_readouts) the gating into the slot's raw
+        buffer; with ``noise`` the replica's noise on the raw data (_launch; setting up a set runs without); with a coil matrix, the
+        compression of this scan's raw data (any coil count) into the static (T, x, y, V) buffer the graph starts from; with
+        virtual_coils= the Gram matrix and the matrix of this slice in front of it (with whitener= the whitened matrix, from the
+        copied whitener)."""
+        if src.raw is not None and src.gate is not None:
+            from . import gating
+            gating.gate_into(*src.gate_views(b), src.gate[2].n_lines, src.raw_view(b))
+        if noise and src.noise is not None and src.raw is not None:          # a raw replica: in place on the slot's raw data, in front of the rest
+            from . import noise as N
+            ns = src.noise
+            rv = src.raw_view(b)
+            N.add_noise_raw(rv, ns.chol, noise_mask=None if src.nmask is None else src.nmask_view(b), scale=ns.scale, seed=ns.seed,
+                            replica=ns.replica, out=rv)
         if src.raw is not None and src.v is not None:
             with torch.no_grad():
                 if src.vc is not None:                       # this slice's own matrix, where coil_matrix= has the copied one
@@ -884,6 +976,26 @@ class SlicePipeline:
         st.raw_bytes, st.gram_bytes = nbytes, gram_bytes
         self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))        # as in _build: new memory of the caller's stream
 
+    def _grow_gate(self, line_bytes: int, entries: int, rows1: int) -> None:
+        """Gating buffers for every (slot, parity): readouts, row_ptr (rows1 = n_frames * nx + 1), index, weight.  No graph holds them
+        (the gate runs in front of the replay), so like _grow_raw this drains and allocates, and nothing is captured again."""
+        self._retire_all()
+        st = self._set
+        for b in st.bufs.values():
+            b["lines"] = b["rptr"] = b["gidx"] = b["gw"] = None
+        self._raw_memory(line_bytes + 4 * rows1 + 8 * entries)
+        try:
+            for b in st.bufs.values():
+                b["lines"] = torch.empty(line_bytes, device=self.device, dtype=torch.uint8)
+                b["rptr"] = torch.empty(rows1, device=self.device, dtype=torch.int32)
+                b["gidx"] = torch.empty(entries, device=self.device, dtype=torch.int32)
+                b["gw"] = torch.empty(entries, device=self.device, dtype=torch.float32)
+        except Exception as e:
+            self._set = None
+            raise CineHipError(f"SlicePipeline: allocating gating buffers of {line_bytes} bytes failed: {type(e).__name__}: {e}") from e
+        st.gate_cap = (line_bytes, entries)
+        self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))        # as in _build: new memory of the caller's stream
+
     def _build(self, src) -> _Set:
         """Buffers for every (slot, parity), filled with this slice's inputs; with graphs, one eager forward per slot stream
         (per-stream caches are filled outside capture) and one capture per buffer set."""
@@ -902,6 +1014,8 @@ class SlicePipeline:
                     st.ready[(i, p)] = torch.cuda.Event()
                     st.done[(i, p)] = torch.cuda.Event()
             self._set = st
+            if src.raw is not None and src.gate is not None:
+                self._grow_gate(*_gate_capacity(src))
             # the new buffers come from the pool of the caller's stream: whatever that stream still has to run on the memory they
             # took over (an eager forward just before the first submit) goes first
             self.copy_stream.wait_stream(torch.cuda.current_stream(dev))
@@ -1005,13 +1119,7 @@ class SlicePipeline:
         s = self.streams[key[0]]
         with torch.cuda.stream(s):
             s.wait_event(st.ready[key])
-            if src.noise is not None and src.raw is not None:                # a raw replica: in place on the slot's raw data, in front of all
-                from . import noise as N
-                b, ns = st.bufs[key], src.noise
-                rv = src.raw_view(b)
-                N.add_noise_raw(rv, ns.chol, noise_mask=None if src.nmask is None else src.nmask_view(b), scale=ns.scale, seed=ns.seed,
-                                replica=ns.replica, out=rv)
-            self._pre(st.bufs[key], src)
+            self._pre(st.bufs[key], src, noise=True)
             if src.noise is not None and src.raw is None:                    # a pseudo replica: in place on the slot's k-space, in front of the replay
                 from . import noise as N
                 b, ns = st.bufs[key], src.noise

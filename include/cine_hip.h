@@ -1190,6 +1190,24 @@ int cine_noise_add(const float* kspace, float* out, const uint8_t* mask, int mas
  * before the launch; no allocation, no host read, no atomics: capturable, and the same bits on every call. */
 int cine_noise_add_raw(const float* raw, float* out, const uint8_t* mask, int mask_ny, const float* chol, float scale,
                        long seed, long replica, const long* replica_dev, long point0, long t, int nx, int ny, int c, void* stream);
+/* Retrospective gating: the acquired readouts of a scan, sorted and averaged / interpolated into the raw (t, x, y, coil) array.
+ * lines (n_lines, row_elems, 2): the readouts in acquisition order, row_elems = ny * coil complex samples each, coil fastest.
+ * out (rows, row_elems, 2), rows = n_frames * nx: the layout cine_raw_ingest, cine_coil_gram, cine_coil_compress and
+ * cine_noise_add_raw read.  row_ptr (rows + 1 ints), index, weight: a CSR matrix in device memory, and
+ *   out[r] = sum_j weight[j] * lines[index[j]],  j = row_ptr[r] .. row_ptr[r + 1] - 1, in that order:
+ * the first term is one fp32 product, every further term one fmaf per real component, so a row with the single weight 1.0 is its
+ * line bit for bit (finite data).  A row without entries is written as zeros: EVERY element of out is written by the call, no memset
+ * is needed and what out held does not matter.  A workgroup owns a chunk of one output row, reads the row's CSR entries once
+ * (uniform loads), streams the contributing spans with consecutive lanes on consecutive 16-byte accesses (8-byte ones when
+ * row_elems is odd or lines / out sit off a 16-byte boundary), accumulates in registers and stores once.
+ * The CSR arrays are DEVICE data and the call trusts them: row_ptr non-decreasing from row_ptr[0] >= 0, 0 <= index[j] < n_lines.
+ * cine_hip.gating.GatingPlan validates them on the host when it is built; n_lines serves the overlap check only.
+ * CINE_EINVAL: a null pointer, rows <= 0, row_elems <= 0, n_lines < 0, sizes whose byte count overflows, out overlapping lines,
+ * lines / out off their 8-byte alignment, row_ptr / index / weight off their 4-byte alignment.  CINE_EUNSUPPORTED: more than
+ * 2^31 - 1 workgroups (rows * ceil(accesses of a row / 512)), the grid limit.  Every argument is checked before the launch; no
+ * allocation, no host read, no atomics: capturable, and the same bits on every call. */
+int cine_gate_readouts(const float* lines, float* out, const int* row_ptr, const int* index, const float* weight,
+                       long n_lines, long rows, long row_elems, void* stream);
 /* Welford's update of (mean, m2) with the k-th sample x, k >= 1, element-wise over n floats, in float64:
  *   d = x - mean;  mean += d / k;  m2 += d * (x - mean)
  * k == 1 initialises both buffers (they are not read and need not be zeroed).  Null pointers, n <= 0, k < 1, mean == m2: CINE_EINVAL. */
