@@ -46,7 +46,7 @@ def __getattr__(name):
     if name in _CLASSICAL:
         from . import classical
         return getattr(classical, name)
-    if name in ("noise", "gating"):               # cine_hip.noise: pseudo-replica noise maps; cine_hip.gating: retrospective gating
-        import importlib                          # imported on first use as well
+    if name in ("noise", "gating", "augment"):    # cine_hip.noise: pseudo-replica noise maps; cine_hip.gating: retrospective gating;
+        import importlib                          # cine_hip.augment: training augmentation -- imported on first use as well
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

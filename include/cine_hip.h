@@ -1208,6 +1208,30 @@ int cine_noise_add_raw(const float* raw, float* out, const uint8_t* mask, int ma
  * allocation, no host read, no atomics: capturable, and the same bits on every call. */
 int cine_gate_readouts(const float* lines, float* out, const int* row_ptr, const int* index, const float* weight,
                        long n_lines, long rows, long row_elems, void* stream);
+/* Training augmentation (cine_hip.augment; no reference counterpart): in resampled under one inverse affine map, with a cyclic shift /
+ * reversal of the frames.  in, out (frames, inner, h, w, 2) float32 complex pairs, out of place only; inner is the coil axis (or 1).
+ * Output frame f reads source frame g = (f + t_shift) mod frames, or with t_reverse != 0 g = (t_shift - f) mod frames (the mathematical
+ * mod).  Every plane shares the map: for the output pixel (yo, xo), centred on the image centre cy = (h - 1) / 2, cx = (w - 1) / 2,
+ *   ys = a_yy (yo - cy) + a_yx (xo - cx) + b_y + cy,   xs = a_xy (yo - cy) + a_xx (xo - cx) + b_x + cx
+ * in float64 (as fma(a_yy, yo - cy, fma(a_yx, xo - cx, b_y + cy)): exact for flips, quarter turns and integer shifts), i0 = floor(.),
+ * and the fraction rounded to float32 once.  Float32 weights: mode 0 bilinear, (1 - f, f) on the taps i0, i0 + 1; mode 1 bicubic, the
+ * cubic-convolution kernel with A = -0.75 on the taps i0 - 1 .. i0 + 2, in the Horner forms ((A + 2) x - (A + 3)) x^2 + 1 on [0, 1] and
+ * ((A x - 5 A) x + 8 A) x - 4 A on [1, 2], which are exactly 1 and 0 at integer fractions.  border 0: a tap outside the plane counts as
+ * 0 and is not read; border 1: every tap index is reflected half-sample symmetrically with period 2 n (.., 1, 0 | 0, 1, .., n - 1 |
+ * n - 1, n - 2, ..), as often as it takes.  This is torch.nn.functional.grid_sample(align_corners=False, padding_mode "zeros" /
+ * "reflection") behind affine_grid([[a_xx, a_xy h / w, 2 b_x / w], [a_yx w / h, a_yy, 2 b_y / h]]).
+ * The sum: per tap row, ascending, s_r = the fmaf chain from 0 of wx[k] v[r][k] over the tap columns, ascending; the pixel is the fmaf
+ * chain from 0 of wy[r] s_r; real and imaginary parts apart.  The same bits on every call and from every launch shape; with integral
+ * coordinates the pixel is its tap bit for bit (finite data).  A lane computes coordinates, taps and weights once and walks the inner
+ * planes with them.
+ * CINE_EINVAL: a null pointer, a size below 1, mode / border outside {0, 1}, a matrix entry or offset that is not finite, |a| > 1024,
+ * |b| > 2^20 (within these limits every coordinate fits an int with room), t_shift outside [0, frames), in / out off their 8-byte
+ * alignment, sizes whose byte count overflows, in and out overlapping.  CINE_EUNSUPPORTED: h or w above 4096, more than 2^31 - 1
+ * workgroups (frames * ceil(inner / 4) * ceil(h / 8) * ceil(w / 32); bicubic: inner / 2).  Every argument is checked on the host before the launch; no allocation, no host
+ * read, no atomics: capturable. */
+int cine_affine_warp(const float* in, float* out, int frames, int inner, int h, int w,
+                     double a_yy, double a_yx, double b_y, double a_xy, double a_xx, double b_x,
+                     int mode, int border, int t_shift, int t_reverse, void* stream);
 /* Welford's update of (mean, m2) with the k-th sample x, k >= 1, element-wise over n floats, in float64:
  *   d = x - mean;  mean += d / k;  m2 += d * (x - mean)
  * k == 1 initialises both buffers (they are not read and need not be zeroed).  Null pointers, n <= 0, k < 1, mean == m2: CINE_EINVAL. */
