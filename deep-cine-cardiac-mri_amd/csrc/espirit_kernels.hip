@@ -333,8 +333,9 @@ ProjWs proj_ws(void* ws, int n) {
 using namespace cine;
 
 extern "C" size_t cine_espirit_gram_ws_bytes(int c, int ny, int nx, int r, int kk) {
-    if (c < 1 || c > esp::kMaxCoils || ny < 1 || nx < 1 || r < 1 || kk < 1) return 0;
+    if (c < 1 || c > esp::kMaxCoils || ny < 1 || nx < 1 || r < 1 || kk < 1 || (long)kk * kk * c > esp::kMaxN) return 0;
     const int ry = r < ny ? r : ny, rx = r < nx ? r : nx;
+    if (ry < kk || rx < kk) return 0;
     return (size_t)ry * rx * c * sizeof(double2);
 }
 

@@ -575,7 +575,7 @@ size_t cine_raw_window_ws_bytes(int t_out, int nx, int ny, int c, int cx, int cy
  * axes) for raw sizes the line engines take, kept frames only: raw (t_in, nx, ny, c, 2) -> out (t_out, c, nx, ny, 2),
  * out[t, k, x, y] = scale * raw[t, x, y, k] for t < t_out <= t_in, each component ONE fp32 product.  cine_fft2c on t_out * c images and
  * cine_crop_select follow.  One pass, 16-byte accesses on both sides for any c and ny.  Sizes >= 1, t_out <= t_in, distinct non-null
- * pointers, raw and out 16-byte aligned (else CINE_EINVAL); CINE_EUNSUPPORTED only past the grid limit or the LDS limit (about 500
+ * pointers, raw and out 16-byte aligned (else CINE_EINVAL); CINE_EUNSUPPORTED only past the grid limit or the LDS limit (510
  * coils), named in the message. */
 int cine_raw_ingest(const float* raw, float* out, int t_in, int nx, int ny, int c, int t_out, float scale, void* stream);
 /* SVD coil compression (Buehrer et al., MRM 57:1131, 2007; Huang et al., MRI 26:133, 2008; BART's `cc`) of raw (t_in, nx, ny, c)

@@ -108,19 +108,21 @@ class GuardedInt:
 
 
 class GuardedF64:
-    """Guarded for a float64 output (cine_image_metrics' out): `n` doubles, NaN, between GUARD doubles of GUARD_VALUE on each side."""
+    """Guarded for a float64 output (cine_image_metrics' out, the complex128 Gram matrices as double pairs): `n` doubles, NaN, between
+    GUARD doubles of GUARD_VALUE at least on each side, at a storage offset of `off` doubles (an even `off` keeps 16-byte alignment)."""
 
-    def __init__(self, n, dev):
+    def __init__(self, n, dev, off=0):
         self.n = n
-        self.buf = torch.full((2 * GUARD + n,), GUARD_VALUE, dtype=torch.float64, device=dev)
-        self.t = self.buf[GUARD:GUARD + n]
+        self.lo = GUARD + off
+        self.buf = torch.full((self.lo + n + GUARD,), GUARD_VALUE, dtype=torch.float64, device=dev)
+        self.t = self.buf[self.lo:self.lo + n]
         self.t.fill_(float("nan"))
 
     def ptr(self):
         return self.t.data_ptr()
 
     def intact(self):
-        return bool((self.buf[:GUARD] == GUARD_VALUE).all()) and bool((self.buf[GUARD + self.n:] == GUARD_VALUE).all())
+        return bool((self.buf[:self.lo] == GUARD_VALUE).all()) and bool((self.buf[self.lo + self.n:] == GUARD_VALUE).all())
 
 
 def same_bits(a, b):
@@ -199,6 +201,15 @@ class Call:
         self.ins.append((t, t.clone()))
         return t
 
+    def inp_among_nan(self, x):
+        """inp with NaN in place of the guard value on both sides: a read outside the operand spoils the result."""
+        x = x.contiguous()
+        buf = torch.full((GUARD + self.off + x.numel() + GUARD,), NAN, device=self.dev)
+        t = buf[GUARD + self.off:GUARD + self.off + x.numel()].view(x.shape)
+        t.copy_(x)
+        self.ins.append((buf, buf.clone()))
+        return t
+
     def raw(self, x):
         """uint8 masks, int32 windows, the one float of lambda_dev: at their allocation's base."""
         t = x.contiguous().to(self.dev)
@@ -218,11 +229,18 @@ class Call:
         self.outs.append(g)
         return g
 
-    def ws(self, nbytes, past256=None):
+    def out64(self, n):
+        """A pure float64 output of n doubles (NaN prefill) at the call's storage offset: `off` floats are off / 2 doubles."""
+        assert self.off % 2 == 0
+        g = GuardedF64(n, self.dev, self.off // 2)
+        self.outs.append(g)
+        return g
+
+    def ws(self, nbytes, past256=None, fill=0xFF):
         if not nbytes:
             return None
         w = Workspace(nbytes, self.dev, past256)
-        w.buf[:w.nbytes] = 0xFF                     # NaN bit patterns: the result must not depend on what the workspace held
+        w.buf[:w.nbytes] = fill                     # 0xFF: NaN bit patterns; the result must not depend on what the workspace held
         self.wss.append(w)
         return w
 
