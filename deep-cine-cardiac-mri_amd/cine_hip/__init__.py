@@ -35,10 +35,12 @@ _hw_queue_default()
 from . import synth  # noqa: F401,E402  (host-only, numpy)
 
 __all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
-           "TotalVariation", "locally_low_rank", "LocallyLowRank"]
+           "TotalVariation", "locally_low_rank", "LocallyLowRank", "lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "grappa",
+           "Grappa"]
 
 _CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
               "TotalVariation", "locally_low_rank", "LocallyLowRank")
+_GRAPPA = ("lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "Grappa")
 
 
 def __getattr__(name):
@@ -46,7 +48,10 @@ def __getattr__(name):
     if name in _CLASSICAL:
         from . import classical
         return getattr(classical, name)
-    if name in ("noise", "gating", "augment"):    # cine_hip.noise: pseudo-replica noise maps; cine_hip.gating: retrospective gating;
-        import importlib                          # cine_hip.augment: training augmentation -- imported on first use as well
-        return importlib.import_module("." + name, __name__)
+    if name in ("noise", "gating", "augment", "grappa"):    # cine_hip.noise: pseudo-replica noise maps; cine_hip.gating: retrospective
+        import importlib                          # gating; cine_hip.augment: training augmentation; cine_hip.grappa: the GRAPPA / TGRAPPA
+        return importlib.import_module("." + name, __name__)    # baseline (the module; its function is cine_hip.grappa.grappa) -- on first use
+    if name in _GRAPPA:
+        import importlib
+        return getattr(importlib.import_module(".grappa", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1232,6 +1232,53 @@ int cine_gate_readouts(const float* lines, float* out, const int* row_ptr, const
 int cine_affine_warp(const float* in, float* out, int frames, int inner, int h, int w,
                      double a_yy, double a_yx, double b_y, double a_xy, double a_xx, double b_x,
                      int mode, int border, int t_shift, int t_reverse, void* stream);
+/* GRAPPA / TGRAPPA (cine_hip.grappa; no reference counterpart): k-space kernels fitted on a calibration array and applied coil by coil to
+ * the rows a frame did not acquire.  k-space of a slice is (t, c, h, w) complex64, h the phase-encode axis; the mask is (t, h) bytes.
+ * Acceleration 2 <= R <= 8; the kernel is ky x kx, ky in {2, 4} source rows R apart, kx in {3, 5, 7} columns, hx = kx / 2;
+ * ns = ky kx c sources in the order (j, dx, coil), j the source row, dx the column tap, the coil fastest; span = (ky - 1) R + 1,
+ * base = (ky / 2 - 1) R.  Limits: c <= 32 and n_aug = ns + (R - 1) c <= 1152 (else CINE_EUNSUPPORTED); R, ky, kx outside their sets:
+ * CINE_EINVAL.
+ * Lattice offset of a frame: the lowest r in [0, R) such that the rows r, r + R, ... are all acquired; none: offset -1, status 1.  A
+ * fully sampled frame has offset 0 and nothing to fill.  Every row of a frame that is not acquired is a target of type
+ * m = (y - off) mod R in [1, R); its source rows are y - m - base + j R, j < ky; source samples outside [0, h) x [0, w) are zero.
+ * Acquired rows (ACS rows and stray extra rows among them) are never written.
+ *   out[f, q, y, x] = sum_{j, dx, k} W[m - 1][(j, dx, k)][q] in[f, k, row_j, x + dx - hx]
+ * Calibration: from cal (c, hc, w) every window position y in [0, hc - span], x in [hx, w - hx) gives one row of the augmented patch
+ * matrix P = [sources | targets of types 1 .. R - 1], the target of type m being cal[:, y + base + m, x].  G = P^H P (n_aug x n_aug);
+ * G_ss = G[:ns, :ns], G_st = G[:ns, ns:], tau = lam trace(G_ss) / ns, and (G_ss + tau I) W = G_st.
+ *
+ * cine_grappa_offsets: mask (t, h) -> offsets (t) and status (t) int32 by the rule above, one workgroup per frame.
+ * cine_grappa_gram: G in complex128, row-major.  Products of floats are exact in float64 and the sums run in float64 in an order fixed by the
+ * shape (eight threads per entry add every eighth window row in window order, their sums are added in that order), so
+ * G is exactly Hermitian with a real diagonal and the same on every call.  hc < span or w < kx: CINE_EINVAL; gram and ws 16-byte
+ * aligned, cal 8-byte aligned (else CINE_EINVAL); ws_bytes >= cine_grappa_gram_ws_bytes() (0 for shapes it refuses), else
+ * CINE_EWORKSPACE; more than 2^22 calibration positions hc w: CINE_EUNSUPPORTED.
+ * cine_grappa_weights: weights (R - 1, ns, c) complex64, each entry rounded once from the float64 solution; info, 4 doubles: the relative
+ * residual |(G_ss + tau I) W - G_st|_F / |G_st|_F of the float64 solution (0 when G_st = 0), tau, the calibration fit
+ * sqrt(trace(G_tt - W^H G_st) / trace(G_tt)) clamped at 0 (0 when trace(G_tt) = 0), trace(G_ss).  The solve is a Newton-Schulz inverse
+ * X <- X (2 I - A X) of A = G_ss + tau I from X_0 = I / |A|_F on cine_zgemm_f64, ceil(log2(sqrt(ns) (ns / lam + 1))) + 6 steps (at most
+ * 100; A's condition number is at most ns / lam + 1), W = X G_st and one step of iterative refinement; the launch sequence depends on
+ * (ns, lam) only.  trace(G_ss) = 0 (an all-zero calibration array): the weights are exactly zero, the residual 0.  A NaN in the Gram
+ * matrix gives a NaN residual.  lam must be positive and finite, gram and ws 16-byte aligned, weights and info 8-byte aligned (else
+ * CINE_EINVAL); ws_bytes >= cine_grappa_weights_ws_bytes() (0 for shapes it refuses), else CINE_EWORKSPACE.
+ * cine_grappa_apply: the application above.  A workgroup owns 64 x-points of one lattice gap of one frame and computes all R - 1 target
+ * rows of the gap from the ky source rows, staged once in LDS; a skinny complex GEMM (M the x-points, K = ns, N = (R - 1) c) in exact
+ * fp32 on v_mfma_f32_16x16x4_f32, a k-ordered fmaf chain per output with the accumulators of cine_coil_compress (Cr += Ar Br - Ai Bi,
+ * Ci += Ar Bi + Ai Br), the weights staged in chunks of 64 k-values.  Targets that are acquired are skipped; frames whose offset is
+ * outside [0, R) are left alone.  out == in works in place (sources are acquired rows and targets are not) and gives the bits of the
+ * out-of-place call; with out != in the acquired rows, and every row of a frame that is left alone, are copied bit for bit; any other
+ * overlap is CINE_EINVAL.  in, out, weights 8-byte aligned, offsets 4-byte aligned (else CINE_EINVAL); more than 65535 frames or
+ * lattice gaps, more than 2^31 - 1 rows t c h: CINE_EUNSUPPORTED.
+ * Every entry checks every argument before the first launch; no allocation, no host read, no synchronisation, no atomics: capturable,
+ * and the same bits on every call. */
+int cine_grappa_offsets(const uint8_t* mask, int* offsets, int* status, int t, int h, int R, void* stream);
+size_t cine_grappa_gram_ws_bytes(int c, int hc, int w, int R, int ky, int kx);
+int cine_grappa_gram(const float* cal, double* gram, void* ws, size_t ws_bytes, int c, int hc, int w, int R, int ky, int kx, void* stream);
+size_t cine_grappa_weights_ws_bytes(int c, int R, int ky, int kx);
+int cine_grappa_weights(const double* gram, float* weights, double* info, void* ws, size_t ws_bytes, int c, int R, int ky, int kx,
+                        double lam, void* stream);
+int cine_grappa_apply(const float* in, const float* weights, const uint8_t* mask, const int* offsets, float* out, int t, int c, int h,
+                      int w, int R, int ky, int kx, void* stream);
 /* Welford's update of (mean, m2) with the k-th sample x, k >= 1, element-wise over n floats, in float64:
  *   d = x - mean;  mean += d / k;  m2 += d * (x - mean)
  * k == 1 initialises both buffers (they are not read and need not be zeroed).  Null pointers, n <= 0, k < 1, mean == m2: CINE_EINVAL. */

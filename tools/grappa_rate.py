@@ -1,0 +1,183 @@
+#!/usr/bin/env python3
+"""What GRAPPA / TGRAPPA (cine_hip.grappa) costs at 1 x 15 frames x 15 coils x 200 x 200, R = 4, kernel 2 x 5, in ONE process.
+
+    python tools/grappa_rate.py [--out profiles/grappa_rate.json] [--commit SHA]
+
+Mask: an interleaved lattice of step 4 without ACS lines; TGRAPPA on the central 32 rows of the temporal average; lam = 1e-4.
+hipEvent medians of 10 calls each:
+  * the four entry points alone (cine_grappa_offsets, cine_grappa_gram, cine_grappa_weights, cine_grappa_apply); for the apply kernel its
+    FLOP rate (8 FLOP per complex multiply-add, targets only) and the bytes it has to move (acquired rows read once, targets written once,
+    the weights once);
+  * the whole ``grappa(...)`` call (check off: nothing read by the host) in turn with a composed torch path: the temporal average, the
+    patch matrix by slicing, ``torch.linalg.solve`` in complex128 on the device (on the host where this torch build has no device solver;
+    the output says which), the application as ``torch.nn.functional.conv2d`` with dilation (R, 1) on the 2c real channels, one call per
+    type over every row of every frame, and a ``torch.where`` scatter of the target rows;
+  * peak memory of both above the baseline, and slices per second of ``Grappa`` through ``SlicePipeline`` (graphs, 4 slots, device inputs).
+--out writes the document, stamped with the commit and a sha256 over csrc/."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "deep-cine-cardiac-mri_amd"), os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from kt_fista_rate import C, H, SLICES, SLOTS, STEPS, T, W, measure, median  # noqa: E402
+
+R, KY, KX, LAM, CALIB_ROWS = 4, 2, 5, 1e-4, 32
+
+
+def device_solve_works(dev):
+    try:
+        a = torch.eye(4, dtype=torch.complex128, device=dev) * 2
+        x = torch.linalg.solve(a, torch.ones(4, 2, dtype=torch.complex128, device=dev))
+        torch.cuda.synchronize()
+        return bool(torch.isfinite(x.real).all())
+    except Exception:
+        return False
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--commit", default=None, help="the commit to stamp the result with (default: git rev-parse HEAD)")
+    args = ap.parse_args()
+    from cine_hip import grappa as G, ops, synth
+    from cine_hip._lib import lib
+    from cine_hip.pipeline import SlicePipeline
+    from pipeline_rate import _stamp
+    dev = torch.device("cuda:0")
+    ex = synth.make_cine_slice(T, C, H, W, accel=4, seed=0, noise_std=0.01)
+    mask = G.lattice_mask(T, H, R).to(dev)
+    commit, csrc = _stamp(args.commit)
+    solve_on_device = device_solve_works(dev)
+    ns, nr, base, hx = KY * KX * C, (R - 1) * C, (KY // 2 - 1) * R, KX // 2
+    doc = {"shape": [1, T, C, H, W], "accel": R, "kernel": [KY, KX], "lam": LAM, "calib": f"tgrappa, calib_rows={CALIB_ROWS}",
+           "mask": "interleaved lattice of step 4, no ACS lines", "device": torch.cuda.get_device_name(dev),
+           "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "steps": STEPS, "commit": commit, "csrc_sha256": csrc, "ns": ns,
+           "n_aug": ns + nr, "composed_solve": "torch.linalg.solve in complex128 on the " + ("device" if solve_on_device else "host")}
+    with torch.no_grad():
+        mk = ops.apply_mask(ex["kspace"].to(dev), mask)
+        rows = mask.view(T, H) != 0
+        off_host = torch.from_numpy(G.plan_lattice(mask, R)[0]).to(dev)
+        m_of_row = (torch.arange(H, device=dev)[None, :] - off_host[:, None].long()) % R                      # (t, h): 0 on the lattice
+        target = [(m_of_row == m) & ~rows for m in range(1, R)]
+        n_targets = int(sum(int(tm.sum()) for tm in target))
+
+        # ---- the entry points alone
+        off, status = G.lattice_offsets(mask, R)
+        cal = G.calibration_data(mk, mask, "tgrappa", None, CALIB_ROWS)
+        weights, info = G.grappa_weights(cal[0], R, (KY, KX), LAM)
+        hc = cal.shape[2]
+        gram = torch.empty((ns + nr, ns + nr), device=dev, dtype=torch.complex128)
+        nb_g, nb_w = lib().cine_grappa_gram_ws_bytes(C, hc, W, R, KY, KX), lib().cine_grappa_weights_ws_bytes(C, R, KY, KX)
+        ws = torch.empty(max(nb_g, nb_w), device=dev, dtype=torch.uint8)
+        st = ops._stream
+        out = torch.empty_like(mk)
+        parts = {
+            "cine_grappa_offsets": lambda: lib().cine_grappa_offsets(mask.data_ptr(), off.data_ptr(), status.data_ptr(), T, H, R, st()),
+            "cine_grappa_gram": lambda: lib().cine_grappa_gram(cal.data_ptr(), gram.data_ptr(), ws.data_ptr(), nb_g, C, hc, W, R, KY, KX, st()),
+            "cine_grappa_weights": lambda: lib().cine_grappa_weights(gram.data_ptr(), weights.data_ptr(), info.data_ptr(), ws.data_ptr(), nb_w, C,
+                                                                     R, KY, KX, LAM, st()),
+            "cine_grappa_apply": lambda: G.grappa_apply(mk[0], weights, mask.view(T, H), off[0], R, (KY, KX), out=out[0]),
+            "cine_grappa_apply_in_place": lambda: G.grappa_apply(out[0], weights, mask.view(T, H), off[0], R, (KY, KX), out=out[0]),
+        }
+        lib().cine_grappa_gram(cal.data_ptr(), gram.data_ptr(), ws.data_ptr(), nb_g, C, hc, W, R, KY, KX, st())
+        doc["entry_us"] = {k: median(measure(fn, dev)[0]) * 1e3 for k, fn in parts.items()}
+        flops = 8.0 * n_targets * W * ns * C
+        moved = 8 * W * C * (int(rows.sum()) + n_targets) + weights.numel() * 4
+        us = doc["entry_us"]["cine_grappa_apply_in_place"]
+        doc["apply"] = {"target_rows": n_targets, "flop": flops, "bytes": moved, "flop_per_byte": flops / moved, "tflops": flops / us * 1e-6,
+                        "gb_per_s": moved / us * 1e-3, "weights_info": info.cpu().tolist()}
+        print(json.dumps({"entry_us": doc["entry_us"], "apply": doc["apply"]}), flush=True)
+
+        # ---- the whole call against the composed torch path
+        def fused():
+            return G.grappa(mk, mask, R, kernel=(KY, KX), lam=LAM, calib="tgrappa", calib_rows=CALIB_ROWS, output="kspace", check=False)
+
+        def composed():
+            k = torch.view_as_complex(mk[0])                                                                  # (t, c, h, w)
+            cnt = rows.sum(0).clamp(min=1).to(torch.float32)
+            avg = (k * rows[:, None, :, None]).sum(0) / cnt[None, :, None]
+            lo = H // 2 - CALIB_ROWS // 2
+            cb = avg[:, lo:lo + CALIB_ROWS].to(torch.complex128)
+            span = (KY - 1) * R + 1
+            my, mx = CALIB_ROWS - span + 1, W - KX + 1
+            cols = [cb[:, j * R:j * R + my, dx:dx + mx] for j in range(KY) for dx in range(KX)]
+            cols += [cb[:, base + m:base + m + my, hx:hx + mx] for m in range(1, R)]
+            P = torch.stack(cols, 0).reshape(-1, my * mx).transpose(0, 1)
+            Gm = P.conj().transpose(0, 1) @ P
+            A = Gm[:ns, :ns] + LAM * Gm[:ns, :ns].diagonal().real.sum() / ns * torch.eye(ns, dtype=torch.complex128, device=dev)
+            Wc = torch.linalg.solve(A, Gm[:ns, ns:]) if solve_on_device else torch.linalg.solve(A.cpu(), Gm[:ns, ns:].cpu()).to(dev)
+            Wc = Wc.to(torch.complex64).reshape(KY, KX, C, R - 1, C)                                          # (j, dx, k, m - 1, q)
+            x = torch.cat((k.real, k.imag), 1)                                                                # (t, 2c, h, w)
+            filled = x
+            for m in range(1, R):
+                wq = Wc[:, :, :, m - 1].permute(3, 2, 0, 1)                                                   # (q, k, j, dx)
+                wt = torch.cat((torch.cat((wq.real, -wq.imag), 1), torch.cat((wq.imag, wq.real), 1)), 0).contiguous()
+                top = m + base
+                y = F.conv2d(F.pad(x, (hx, hx, top, (KY - 1) * R - top)), wt, dilation=(R, 1))
+                filled = torch.where(target[m - 1][:, None, :, None], y, filled)
+            return torch.stack((filled[:, :C], filled[:, C:]), -1)[None]
+
+        kf, kc = fused(), composed()
+        doc["fused_vs_composed_max_abs_over_peak"] = float((kf - kc).abs().max() / kc.abs().max())
+        del kf, kc
+        for variant, fn in (("fused", fused), ("composed", composed), ("fused_again", fused), ("composed_again", composed)):
+            G.release_workspaces()
+            torch.cuda.empty_cache()
+            ms, peak = measure(fn, dev)
+            doc[variant] = {"median_ms": median(ms), "ms": ms, "peak_bytes": peak}
+            print(json.dumps({variant: doc[variant]}), flush=True)
+        doc["composed_over_fused"] = doc["composed"]["median_ms"] / doc["fused"]["median_ms"]
+        doc["peak_fused_over_composed"] = doc["fused"]["peak_bytes"] / doc["composed"]["peak_bytes"]
+
+        # the application alone, composed: the convolutions and the scatter with the weights given
+        wts_c = torch.view_as_complex(weights).reshape(R - 1, KY, KX, C, C)
+        xin = torch.cat((torch.view_as_complex(mk[0]).real, torch.view_as_complex(mk[0]).imag), 1)
+
+        def conv_apply():
+            filled = xin
+            for m in range(1, R):
+                wq = wts_c[m - 1].permute(3, 2, 0, 1)
+                wt = torch.cat((torch.cat((wq.real, -wq.imag), 1), torch.cat((wq.imag, wq.real), 1)), 0).contiguous()
+                top = m + base
+                y = F.conv2d(F.pad(xin, (hx, hx, top, (KY - 1) * R - top)), wt, dilation=(R, 1))
+                filled = torch.where(target[m - 1][:, None, :, None], y, filled)
+            return filled
+        doc["entry_us"]["composed_conv2d_apply"] = median(measure(conv_apply, dev)[0]) * 1e3
+        doc["conv2d_apply_over_cine_grappa_apply"] = doc["entry_us"]["composed_conv2d_apply"] / doc["entry_us"]["cine_grappa_apply"]
+        print(json.dumps({k: doc[k] for k in ("composed_over_fused", "peak_fused_over_composed", "conv2d_apply_over_cine_grappa_apply",
+                                              "fused_vs_composed_max_abs_over_peak")}), flush=True)
+
+        model = G.Grappa(accel=R, kernel=(KY, KX), lam=LAM, calib="tgrappa", calib_rows=CALIB_ROWS).eval()
+        with SlicePipeline(model, slots=SLOTS) as pipe:
+            pipe.submit(mk, mask, tag="build")
+            list(pipe.drain())
+            rates = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for j in range(SLICES):
+                    pipe.submit(mk, mask, tag=j)
+                    for _ in pipe.results():
+                        pass
+                list(pipe.drain())
+                torch.cuda.synchronize()
+                rates.append(SLICES / (time.perf_counter() - t0))
+        doc["pipeline"] = {"model": f"Grappa(accel={R})", "slots": SLOTS, "slices": SLICES, "slices_per_s": median(rates), "runs": rates}
+        print(json.dumps({"pipeline": doc["pipeline"]}), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
