@@ -36,11 +36,12 @@ from . import synth  # noqa: F401,E402  (host-only, numpy)
 
 __all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
            "TotalVariation", "locally_low_rank", "LocallyLowRank", "lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "grappa",
-           "Grappa"]
+           "Grappa", "plan_gaps", "gap_table", "grappa_weights_gaps", "grappa_apply_gaps"]
 
 _CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
               "TotalVariation", "locally_low_rank", "LocallyLowRank")
-_GRAPPA = ("lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "Grappa")
+_GRAPPA = ("lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "Grappa", "plan_gaps", "gap_table", "grappa_weights_gaps",
+           "grappa_apply_gaps")
 
 
 def __getattr__(name):

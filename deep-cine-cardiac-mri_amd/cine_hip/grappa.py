@@ -20,11 +20,24 @@ by the host, it can be captured into a graph and goes through ``SlicePipeline.su
 ``cine_hip.noise.pseudo_replica`` gives its noise map.
 
 The reference's ``EquispacedMaskFunc`` (``synth.EquispacedMaskFunc``) spaces its rows by a non-integer step and rounds: its masks are no
-lattice.  ``lattice_mask`` makes masks that are.
+lattice.  ``lattice_mask`` makes masks that are; ``accel=None`` takes the others:
 
-Not built: irregular (variable-density) row masks, k-t GRAPPA with temporal source points, through-time calibration per frame,
-image-domain application, and a g-factor from the weights (``noise.pseudo_replica`` measures one).
+UNEVENLY SPACED ROWS (``accel=None``).  A frame is a list of gaps: two consecutive acquired rows ``G >= 2`` apart, filled from those two
+rows (``ky = 2`` only) with the lattice kernels fitted for step ``G``; the rows in front of the first and behind the last acquired row are
+ends, filled with the step ``max(neighbouring spacing, rows + 1)`` from one row and a zero row outside the frame.  ``plan_gaps`` states
+the rule on the host, ``cine_grappa_gaps`` lists the gaps on the device, ``grappa_weights_gaps`` fits one set of kernels per step (one Gram
+matrix and one solve each, through the lattice entry points) and ``cine_grappa_apply_gaps`` applies them.  On a pure lattice of step 2 .. 8
+this gives the bits of the lattice path; next to an ACS block it predicts from the nearer rows.  Steps above 8 are out of reach: rows in
+such a gap stay as they are and are counted (``unfilled``).  The reference's equispaced masks have steps {2 .. 6} at acceleration 4
+(7 at 32 rows), {2, 3, 4} at 3, {2, 3} at 2, and 11 - 12 at acceleration 8, which is NOT supported.  Gaussian-density masks
+(``synth.RandomMaskFunc``) are not what this is for either: at acceleration 4 some 61 % of their missing rows lie in gaps above 8; the
+proximal baselines of ``cine_hip.classical`` (k-t SPARSE-SENSE, L+S, TV, LLR) are the tools for those.
+
+Not built: gaps above 8 rows (the equispaced masks at acceleration 8), ``ky = 4`` on uneven masks, masks that vary along w, a batched
+Gram / solve over the steps (one pair per step runs in sequence), k-t GRAPPA with temporal source points, through-time calibration per
+frame, image-domain application, and a g-factor from the weights (``noise.pseudo_replica`` measures one).
 """
+import ctypes
 import threading
 from typing import Optional, Sequence, Tuple
 
@@ -36,9 +49,10 @@ from . import ops
 from ._lib import CineHipError, check, lib
 
 __all__ = ["lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "grappa_apply", "lattice_offsets", "grappa", "Grappa",
-           "RESIDUAL_MAX"]
+           "RESIDUAL_MAX", "plan_gaps", "gap_table", "grappa_weights_gaps", "grappa_apply_gaps", "MAX_GAP"]
 
 MAX_COILS, MAX_AUG = 32, 1152
+MAX_GAP = 8                # the largest step a gap can have: the lattice kernels exist for 2 .. 8
 RESIDUAL_MAX = 1e-8        # check=True: above this relative residual the float64 solve has diverged (a backward-stable one sits near 1e-15)
 
 
@@ -86,6 +100,76 @@ def plan_lattice(mask, accel: int) -> np.ndarray:
             raise ValueError(f"plan_lattice: {where} samples no lattice of step {accel}: for no offset r are the rows r, r + {accel}, ... all "
                              f"acquired (acquired rows: {np.flatnonzero(flat[f]).tolist()})")
     return off.reshape(m.shape[:-1])
+
+
+def _max_gap(max_gap) -> int:
+    if int(max_gap) != max_gap or not 2 <= int(max_gap) <= MAX_GAP:
+        raise ValueError(f"max_gap = {max_gap!r}: an integer 2 .. {MAX_GAP}")
+    return int(max_gap)
+
+
+def _gap_sizes(gaps, max_gap: int) -> Tuple[int, ...]:
+    """The steps with weights as a sorted tuple of distinct integers 2 .. max_gap."""
+    try:
+        given = list(gaps)
+        sizes = sorted({int(g) for g in given})
+        ok = bool(sizes) and len(sizes) == len(given) and all(int(g) == g for g in given) and sizes[0] >= 2 and sizes[-1] <= max_gap
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"gaps = {gaps!r}: expected distinct integers 2 .. {max_gap} (max_gap), at least one")
+    return tuple(sizes)
+
+
+def _plan_frame(row: np.ndarray, max_gap: int, allowed) -> Tuple[list, list]:
+    """One frame (h,) bool -> ([(lo, G), ...] in ascending lo, the rows that stay unfilled)."""
+    h = row.shape[0]
+    a = np.flatnonzero(row).tolist()
+    if not a:
+        return [], list(range(h))
+    n = len(a)
+    cand = []                                                        # (lo, G, its target rows inside the frame)
+    if a[0] > 0:
+        nb = a[1] - a[0] if n >= 2 and a[1] - a[0] >= 2 else 0
+        G = max(nb, a[0] + 1)
+        cand.append((a[0] - G, G, list(range(0, a[0]))))
+    for i in range(n - 1):
+        G = a[i + 1] - a[i]
+        if G >= 2:
+            cand.append((a[i], G, list(range(a[i] + 1, a[i + 1]))))
+    if a[-1] < h - 1:
+        nb = a[-1] - a[-2] if n >= 2 and a[-1] - a[-2] >= 2 else 0
+        G = max(nb, h - a[-1])
+        cand.append((a[-1], G, list(range(a[-1] + 1, h))))
+    gaps, unfilled = [], []
+    for lo, G, rows in cand:
+        if G <= max_gap and G in allowed:
+            gaps.append((lo, G))
+        else:
+            unfilled.extend(rows)
+    return gaps, unfilled
+
+
+def plan_gaps(mask, max_gap: int = MAX_GAP, allowed=None):
+    """The gaps of every frame of a (t, h) mask, or of a row mask (b, t, 1, h, 1, 1), by the rule of ``cine_grappa_gaps``
+    (include/cine_hip.h), whose host twin this is.  Per frame, with a_0 < ... < a_{n-1} the acquired rows: consecutive rows G >= 2 apart
+    are the gap (a_i, G); the e > 0 rows in front of a_0 are the gap (a_0 - G, G) with G = max(nb, e + 1), nb the spacing a_1 - a_0 if
+    there is one and it is >= 2, else 0; the rows behind a_{n-1} likewise, (a_{n-1}, G).  A gap with G > max_gap or G not in ``allowed``
+    (default: every step 2 .. max_gap) is left out and its rows count as unfilled; an empty frame has no gap and h unfilled rows.
+    Returns (gaps, sizes, unfilled): the list per frame of (lo, G) in ascending lo (nested per batch element for a row mask), the sorted
+    tuple of the steps that occur among them, and the unfilled rows per frame as int32 (t,) or (b, t)."""
+    max_gap = _max_gap(max_gap)
+    allowed = set(range(2, max_gap + 1)) if allowed is None else set(_gap_sizes(allowed, MAX_GAP))
+    m = _host_rows(mask)
+    flat = m.reshape(-1, m.shape[-1])
+    per_frame = [_plan_frame(flat[f], max_gap, allowed) for f in range(flat.shape[0])]
+    gaps = [g for g, _ in per_frame]
+    sizes = tuple(sorted({G for g in gaps for _, G in g}))
+    unfilled = np.array([len(u) for _, u in per_frame], np.int32).reshape(m.shape[:-1])
+    if m.ndim == 3:
+        t = m.shape[1]
+        gaps = [gaps[i * t:(i + 1) * t] for i in range(m.shape[0])]
+    return gaps, sizes, unfilled
 
 
 def _accel(accel) -> int:
@@ -198,6 +282,23 @@ def calibration_data(masked_kspace: torch.Tensor, mask: torch.Tensor, calib: str
     return (total / count).contiguous()
 
 
+def _fit(cal: torch.Tensor, accel: int, ky: int, kx: int, lam: float, weights: torch.Tensor, info: torch.Tensor) -> None:
+    """``cine_grappa_gram`` and ``cine_grappa_weights`` of cal (c, hc, w, 2) into ``weights`` (accel - 1, ns, c, 2) and ``info`` (4,)."""
+    c, hc, w, _ = cal.shape
+    ns, n_aug, span = _geometry(c, accel, ky, kx)
+    if hc < span or w < kx:
+        raise ValueError(f"grappa_weights: the {hc} x {w} calibration array is smaller than the {span} x {kx} window of a {ky} x {kx} kernel "
+                         f"at accel {accel}")
+    gram = torch.empty((n_aug, n_aug), device=cal.device, dtype=torch.complex128)
+    nb_gram = lib().cine_grappa_gram_ws_bytes(c, hc, w, accel, ky, kx)
+    nb_solve = lib().cine_grappa_weights_ws_bytes(c, accel, ky, kx)
+    ws = _workspace(max(nb_gram, nb_solve), cal.device)
+    check(lib().cine_grappa_gram(cal.data_ptr(), gram.data_ptr(), ws.data_ptr(), nb_gram, c, hc, w, accel, ky, kx, ops._stream()),
+          "cine_grappa_gram")
+    check(lib().cine_grappa_weights(gram.data_ptr(), weights.data_ptr(), info.data_ptr(), ws.data_ptr(), nb_solve, c, accel, ky, kx, lam,
+                                    ops._stream()), "cine_grappa_weights")
+
+
 def grappa_weights(cal: torch.Tensor, accel: int, kernel=(2, 5), lam: float = 1e-4) -> Tuple[torch.Tensor, torch.Tensor]:
     """cal (c, hc, w, 2) float32 on the GPU -> (weights (accel - 1, ns, c, 2) float32, info (4,) float64): ``cine_grappa_gram`` and
     ``cine_grappa_weights``.  info: the relative residual of the float64 solve, tau, the calibration fit
@@ -206,23 +307,102 @@ def grappa_weights(cal: torch.Tensor, accel: int, kernel=(2, 5), lam: float = 1e
     cal = ops._dev(cal, "grappa_weights cal")
     if cal.dim() != 4 or cal.shape[-1] != 2:
         raise ValueError(f"cal {tuple(cal.shape)}: expected (c, hc, w, 2)")
-    c, hc, w, _ = cal.shape
-    ns, n_aug, span = _geometry(c, accel, ky, kx)
-    if hc < span or w < kx:
-        raise ValueError(f"grappa_weights: the {hc} x {w} calibration array is smaller than the {span} x {kx} window of a {ky} x {kx} kernel "
-                         f"at accel {accel}")
-    dev = cal.device
-    gram = torch.empty((n_aug, n_aug), device=dev, dtype=torch.complex128)
-    weights = torch.empty((accel - 1, ns, c, 2), device=dev, dtype=torch.float32)
-    info = torch.empty(4, device=dev, dtype=torch.float64)
-    nb_gram = lib().cine_grappa_gram_ws_bytes(c, hc, w, accel, ky, kx)
-    nb_solve = lib().cine_grappa_weights_ws_bytes(c, accel, ky, kx)
-    ws = _workspace(max(nb_gram, nb_solve), dev)
-    check(lib().cine_grappa_gram(cal.data_ptr(), gram.data_ptr(), ws.data_ptr(), nb_gram, c, hc, w, accel, ky, kx, ops._stream()),
-          "cine_grappa_gram")
-    check(lib().cine_grappa_weights(gram.data_ptr(), weights.data_ptr(), info.data_ptr(), ws.data_ptr(), nb_solve, c, accel, ky, kx, lam,
-                                    ops._stream()), "cine_grappa_weights")
+    c = cal.shape[0]
+    ns, _, _ = _geometry(c, accel, ky, kx)
+    weights = torch.empty((accel - 1, ns, c, 2), device=cal.device, dtype=torch.float32)
+    info = torch.empty(4, device=cal.device, dtype=torch.float64)
+    _fit(cal, accel, ky, kx, lam, weights, info)
     return weights, info
+
+
+def _kernel_gaps(kernel) -> int:
+    ky, kx = _kernel(kernel)
+    if ky != 2:
+        raise ValueError(f"kernel = {kernel!r}: on unevenly spaced rows (accel=None) only ky = 2 source rows, the two acquired neighbours of "
+                         f"a gap; four need equal spacing on both sides")
+    return kx
+
+
+def _woff(gaps: Sequence[int], ns: int, c: int):
+    """The 9 host ints of ``cine_grappa_apply_gaps``: the offset of the block of step G in complex elements, blocks in ascending G."""
+    woff, row = [-1] * 9, 0
+    for G in gaps:
+        woff[G] = row * ns * c
+        row += G - 1
+    return (ctypes.c_int * 9)(*woff), row
+
+
+def gap_table(mask: torch.Tensor, gaps: Sequence[int], max_gap: int = MAX_GAP) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """mask (b, t, 1, h, 1, 1) (or (t, h)) uint8 on the GPU -> (table (b, t, cap, 2) int32 of (lo, G), count (b, t), unfilled (b, t)) by
+    ``cine_grappa_gaps``: the rule of ``plan_gaps`` with ``allowed = gaps``; entries from count on are (0, 0).  No host read."""
+    max_gap = _max_gap(max_gap)
+    sizes = _gap_sizes(gaps, max_gap)
+    mask = ops._dev(mask, "mask", torch.uint8)
+    if mask.dim() == 2:
+        lead, h = (mask.shape[0],), mask.shape[1]
+    elif mask.dim() == 6 and mask.numel() == mask.shape[0] * mask.shape[1] * mask.shape[3]:
+        lead, h = (mask.shape[0], mask.shape[1]), mask.shape[3]
+    else:
+        raise ValueError(f"mask shape {tuple(mask.shape)}: expected (t, h) or a row mask (b, t, 1, h, 1, 1)")
+    n = int(np.prod(lead))
+    cap = lib().cine_grappa_gaps_cap(h)
+    table = torch.empty(lead + (cap, 2), device=mask.device, dtype=torch.int32)
+    count = torch.empty(lead, device=mask.device, dtype=torch.int32)
+    unfilled = torch.empty(lead, device=mask.device, dtype=torch.int32)
+    bits = sum(1 << g for g in sizes)
+    check(lib().cine_grappa_gaps(mask.data_ptr(), table.data_ptr(), count.data_ptr(), unfilled.data_ptr(), n, h, max_gap, bits, ops._stream()),
+          "cine_grappa_gaps")
+    return table, count, unfilled
+
+
+def grappa_weights_gaps(cal: torch.Tensor, gaps: Sequence[int], kernel=(2, 5), lam: float = 1e-4) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cal (c, hc, w, 2) float32 on the GPU -> (weights (sum of G - 1, ns, c, 2) float32, info (len(gaps), 4) float64): for every step G of
+    ``gaps`` in ascending order the lattice fit ``grappa_weights(cal, G, (2, kx), lam)``, one Gram matrix and one solve each, written
+    into consecutive slices of one buffer; row i of info is that fit's.  hc must be at least max(gaps) + 1.  No host read."""
+    kx, lam = _kernel_gaps(kernel), _lam(lam)
+    sizes = _gap_sizes(gaps, MAX_GAP)
+    cal = ops._dev(cal, "grappa_weights_gaps cal")
+    if cal.dim() != 4 or cal.shape[-1] != 2:
+        raise ValueError(f"cal {tuple(cal.shape)}: expected (c, hc, w, 2)")
+    c = cal.shape[0]
+    ns, _, _ = _geometry(c, sizes[-1], 2, kx)
+    weights = torch.empty((sum(G - 1 for G in sizes), ns, c, 2), device=cal.device, dtype=torch.float32)
+    info = torch.empty((len(sizes), 4), device=cal.device, dtype=torch.float64)
+    row = 0
+    for i, G in enumerate(sizes):
+        _fit(cal, G, 2, kx, lam, weights[row:row + G - 1], info[i])
+        row += G - 1
+    return weights, info
+
+
+def grappa_apply_gaps(kspace: torch.Tensor, weights: torch.Tensor, gaps: Sequence[int], mask: torch.Tensor, table: torch.Tensor,
+                      count: torch.Tensor, kernel=(2, 5), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """kspace (t, c, h, w, 2), weights of ``grappa_weights_gaps(cal, gaps, kernel)``, mask (t, h) uint8, table (t, cap, 2) and count (t,)
+    of ``gap_table``, all on the GPU -> the filled k-space (``cine_grappa_apply_gaps``).  ``out=kspace`` fills in place.  Acquired rows,
+    rows of no listed gap and empty frames keep their bits."""
+    kx = _kernel_gaps(kernel)
+    sizes = _gap_sizes(gaps, MAX_GAP)
+    kspace = ops._dev(kspace, "grappa_apply_gaps kspace")
+    weights = ops._dev(weights, "grappa_apply_gaps weights")
+    mask = ops._dev(mask, "mask", torch.uint8)
+    table = ops._dev(table, "table", torch.int32)
+    count = ops._dev(count, "count", torch.int32)
+    t, c, h, w, _ = kspace.shape
+    ns, _, _ = _geometry(c, sizes[-1], 2, kx)
+    woff, rows = _woff(sizes, ns, c)
+    cap = table.shape[-2] if table.dim() >= 2 else 0
+    if (tuple(weights.shape) != (rows, ns, c, 2) or mask.numel() != t * h or count.numel() != t or cap < 1
+            or table.numel() != t * cap * 2 or table.shape[-1] != 2):
+        raise ValueError(f"grappa_apply_gaps: weights {tuple(weights.shape)}, mask {tuple(mask.shape)}, table {tuple(table.shape)}, count "
+                         f"{tuple(count.shape)} for k-space {tuple(kspace.shape)} and gaps {sizes}: expected {(rows, ns, c, 2)}, {(t, h)}, "
+                         f"(t, cap, 2), {(t,)}")
+    if out is None:
+        out = torch.empty_like(kspace)
+    elif out.shape != kspace.shape or out.dtype != kspace.dtype or not out.is_contiguous() or out.device != kspace.device:
+        raise ValueError("grappa_apply_gaps: out must be a contiguous tensor like kspace")
+    check(lib().cine_grappa_apply_gaps(kspace.data_ptr(), weights.data_ptr(), woff, mask.data_ptr(), table.data_ptr(), count.data_ptr(),
+                                       out.data_ptr(), t, c, h, w, cap, kx, ops._stream()), "cine_grappa_apply_gaps")
+    return out
 
 
 def grappa_apply(kspace: torch.Tensor, weights: torch.Tensor, mask: torch.Tensor, offsets: torch.Tensor, accel: int, kernel=(2, 5),
@@ -285,6 +465,40 @@ def _run(masked_kspace, mask, sens_maps, accel, ky, kx, lam, calib, acs, calib_r
     return res, info, offsets, status
 
 
+def _settings_gaps(gaps, max_gap, kernel, lam, calib, acs, calib_rows, output, sens_maps):
+    """The settings of the gap path: (steps or "auto", max_gap, kx, lam).  The lattice settings are checked with the step 2."""
+    max_gap = _max_gap(max_gap)
+    _, _, _, lam = _settings(2, kernel, lam, calib, acs, calib_rows, output, sens_maps)
+    kx = _kernel_gaps(kernel)
+    if not (isinstance(gaps, str) and gaps == "auto"):
+        gaps = _gap_sizes(gaps, max_gap)
+    return gaps, max_gap, kx, lam
+
+
+def _run_gaps(masked_kspace, mask, sens_maps, sizes, max_gap, kx, lam, calib, acs, calib_rows, output):
+    """The launch sequence of the gap path, shared by ``grappa`` and ``Grappa.forward``: (result, info (b, len(sizes), 4), count (b, t),
+    unfilled (b, t))."""
+    b, t, c, h, w, _ = masked_kspace.shape
+    table, count, unfilled = gap_table(mask, sizes, max_gap)
+    cal = calibration_data(masked_kspace, mask, calib, acs, calib_rows)
+    filled = torch.empty_like(masked_kspace)
+    infos = []
+    for i in range(b):
+        weights, info = grappa_weights_gaps(cal[i], sizes, (2, kx), lam)
+        grappa_apply_gaps(masked_kspace[i], weights, sizes, mask[i].view(t, h), table[i], count[i], (2, kx), out=filled[i])
+        infos.append(info)
+    info = torch.stack(infos)
+    if output == "kspace":
+        res = filled
+    elif sens_maps is None:
+        res = ops.zero_filled_rss(filled, destroy_input=True)
+    elif output == "magnitude":
+        res = ops.sens_reduce(filled, sens_maps, magnitude=True, destroy_input=True)
+    else:
+        res = ops.sens_reduce(filled, sens_maps, destroy_input=True).squeeze(2)
+    return res, info, count, unfilled
+
+
 def _inputs(what, masked_kspace, mask, sens_maps, accel, ky, kx, calib, acs, calib_rows):
     """Shapes against the limits (host only), then the tensors on the device: (masked_kspace, mask as uint8 row mask)."""
     if not isinstance(masked_kspace, torch.Tensor) or masked_kspace.dim() != 6 or masked_kspace.shape[-1] != 2:
@@ -303,9 +517,10 @@ def _inputs(what, masked_kspace, mask, sens_maps, accel, ky, kx, calib, acs, cal
     return ops._dev(masked_kspace, "masked_kspace"), mask, (lo, hi)
 
 
-def grappa(masked_kspace: torch.Tensor, mask: torch.Tensor, accel: int, kernel=(2, 5), lam: float = 1e-4, calib: str = "auto",
-           acs: Optional[Sequence[int]] = None, calib_rows: int = 32, sens_maps: Optional[torch.Tensor] = None, output: str = "magnitude",
-           check: bool = True, record: bool = False):
+def grappa(masked_kspace: torch.Tensor, mask: torch.Tensor, accel: Optional[int] = None, kernel=(2, 5), lam: float = 1e-4,
+           calib: str = "auto", acs: Optional[Sequence[int]] = None, calib_rows: int = 32, sens_maps: Optional[torch.Tensor] = None,
+           output: str = "magnitude", check: bool = True, record: bool = False, gaps="auto", max_gap: int = MAX_GAP,
+           max_unfilled: float = 0.0):
     """GRAPPA / TGRAPPA of ``masked_kspace`` (b, t, c, h, w, 2) under the row mask ``mask`` (b, t, 1, h, 1, 1), every frame of which samples
     a lattice of step ``accel`` (2 .. 8).  Each batch element is calibrated on its own.
 
@@ -318,7 +533,17 @@ def grappa(masked_kspace: torch.Tensor, mask: torch.Tensor, accel: int, kernel=(
     ``check``: read the solve's residual and raise ``CineHipError`` when it is not finite or above ``RESIDUAL_MAX`` (a NaN in the data, a
     diverged iteration; not a grade of accuracy).  ``record``: also return info (b, 4) float64 (``grappa_weights``) and offsets (b, t).
     Raises ``ValueError`` for settings and shapes outside the limits and for a frame without a lattice or a calibration row that no
-    frame acquired, ``CineHipError`` for CPU tensors (no fallback) and inputs that require grad.  Not differentiable."""
+    frame acquired, ``CineHipError`` for CPU tensors (no fallback) and inputs that require grad.  Not differentiable.
+
+    ``accel=None``: unevenly spaced rows (the module docstring; ``gaps``, ``max_gap`` and ``max_unfilled`` are read in this case only).
+    Every frame is filled gap by gap from the two acquired neighbours, so ``kernel[0]`` must be 2.  ``gaps``: the steps to fit kernels
+    for, "auto" for those that occur in the mask (read on the host, as the lattice path reads it); ``max_gap`` (<= 8): larger gaps stay
+    unfilled.  ``max_unfilled``: the share of a batch element's missing rows that may stay unfilled; above it ``ValueError`` names the
+    first such frame and row.  The calibration block needs at least max(gaps) + 1 rows.  ``record``: also return info
+    (b, len(gaps), 4), the steps as a tuple and the unfilled rows (b, t) int32."""
+    if accel is None:
+        return _grappa_gaps(masked_kspace, mask, kernel, lam, calib, acs, calib_rows, sens_maps, output, check, record, gaps, max_gap,
+                            max_unfilled)
     accel, ky, kx, lam = _settings(accel, kernel, lam, calib, acs, calib_rows, output, sens_maps)
     from .classical import _no_grad_inputs
     _no_grad_inputs("grappa", masked_kspace=masked_kspace, sens_maps=sens_maps)
@@ -340,22 +565,88 @@ def grappa(masked_kspace: torch.Tensor, mask: torch.Tensor, accel: int, kernel=(
     return (res, info, offsets) if record else res
 
 
+def _check_residuals(info, lam):
+    resid = info[..., 0].cpu().numpy()
+    if not np.all(np.isfinite(resid)) or float(resid.max()) > RESIDUAL_MAX:
+        raise CineHipError(f"grappa: the float64 solve of the kernels left the relative residuals {resid.tolist()} "
+                           f"(not finite, or above {RESIDUAL_MAX:g}): a NaN in the calibration data, or lam = {lam:g} too small")
+
+
+def _grappa_gaps(masked_kspace, mask, kernel, lam, calib, acs, calib_rows, sens_maps, output, check, record, gaps, max_gap, max_unfilled):
+    """``grappa(accel=None)``."""
+    gaps, max_gap, kx, lam = _settings_gaps(gaps, max_gap, kernel, lam, calib, acs, calib_rows, output, sens_maps)
+    max_unfilled = float(max_unfilled)
+    if not 0.0 <= max_unfilled <= 1.0:
+        raise ValueError(f"max_unfilled = {max_unfilled!r}: a share in [0, 1]")
+    from .classical import _no_grad_inputs
+    _no_grad_inputs("grappa", masked_kspace=masked_kspace, sens_maps=sens_maps)
+    with torch.no_grad():
+        if not isinstance(mask, torch.Tensor):
+            raise CineHipError("grappa: masked_kspace, mask and sens_maps must be GPU tensors (the HIP path has no CPU fallback)")
+        rows = _host_rows(mask)                                      # the mask on the host, to choose the steps and to fail early
+        if rows.ndim != 3:
+            raise ValueError(f"grappa: mask {tuple(mask.shape)} is no row mask (b, t, 1, h, 1, 1)")
+        sizes = plan_gaps(rows.reshape(-1, rows.shape[-1]), max_gap)[1] if gaps == "auto" else gaps
+        if not sizes:                                                # nothing to fill within reach: one step keeps the launch sequence whole
+            sizes = (2,)
+        for i in range(rows.shape[0]):
+            missing = int((~rows[i]).sum())
+            left = [(f, _plan_frame(rows[i, f], max_gap, set(sizes))[1]) for f in range(rows.shape[1])]
+            n_left = sum(len(u) for _, u in left)
+            if missing and n_left > max_unfilled * missing:
+                f, u = next((f, u) for f, u in left if u)
+                raise ValueError(f"grappa: {n_left} of the {missing} missing rows of batch element {i} would stay unfilled (max_unfilled = "
+                                 f"{max_unfilled:g}): the first is row {u[0]} of frame {f}, in a gap above max_gap = {max_gap} or of a step "
+                                 f"not in gaps = {tuple(sizes)}")
+        masked_kspace, mask, (lo, hi) = _inputs("grappa", masked_kspace, mask, sens_maps, sizes[-1], 2, kx, calib, acs, calib_rows)
+        for i in range(rows.shape[0]):
+            empty = np.flatnonzero(~rows[i, :, lo:hi].any(axis=0))
+            if empty.size:
+                raise ValueError(f"grappa: row {lo + int(empty[0])} of the calibration block [{lo}, {hi}) of batch element {i} was acquired by "
+                                 f"no frame")
+        res, info, _, unfilled = _run_gaps(masked_kspace, mask, sens_maps, sizes, max_gap, kx, lam, calib, acs, calib_rows, output)
+        if check:
+            _check_residuals(info, lam)
+    return (res, info, tuple(sizes), unfilled) if record else res
+
+
 class Grappa(nn.Module):
     """``grappa`` as a module with the models' ``forward`` signature and no parameters: ``SlicePipeline(Grappa(accel=4).eval())``
     reconstructs slices in flight, raw input included.  The lattice offsets come from ``cine_grappa_offsets`` and nothing is read by the
     host, so ``forward`` can be captured; there is no ``check`` -- frames without a lattice are left as they are and a failed solve shows
-    in ``last_info``: the device tensors ``info`` (b, 4), ``offsets`` (b, t) and ``status`` (b, t) of the last call."""
+    in ``last_info``: the device tensors ``info`` (b, 4), ``offsets`` (b, t) and ``status`` (b, t) of the last call.
 
-    def __init__(self, accel: int, kernel=(2, 5), lam: float = 1e-4, calib: str = "auto", acs: Optional[Sequence[int]] = None,
-                 calib_rows: int = 32):
+    ``accel=None``: unevenly spaced rows, with kernels for the steps ``gaps`` -- explicit, because ``forward`` reads nothing on the host;
+    the default is what the reference's equispaced masks have at acceleration 4.  The gap table comes from ``cine_grappa_gaps``; rows in
+    gaps of other steps, or above ``max_gap``, are left as they are.  ``last_info`` then holds ``info`` (b, len(gaps), 4), ``count``
+    (b, t), the gaps listed per frame, and ``unfilled`` (b, t), the rows left."""
+
+    def __init__(self, accel: Optional[int] = None, kernel=(2, 5), lam: float = 1e-4, calib: str = "auto",
+                 acs: Optional[Sequence[int]] = None, calib_rows: int = 32, gaps: Sequence[int] = (2, 3, 4, 5, 6), max_gap: int = MAX_GAP):
         super().__init__()
-        self.accel, self.ky, self.kx, self.lam = _settings(accel, kernel, lam, calib, acs, calib_rows, "magnitude", None)
-        self.kernel = (self.ky, self.kx)
         self.calib, self.acs, self.calib_rows = calib, (None if acs is None else tuple(int(v) for v in acs)), int(calib_rows)
         self.last_info = None
+        self.accel = None
+        if accel is None:
+            if isinstance(gaps, str):
+                raise ValueError(f"Grappa: gaps = {gaps!r}: the steps must be explicit, forward reads nothing on the host")
+            self.gaps, self.max_gap, self.kx, self.lam = _settings_gaps(gaps, max_gap, kernel, lam, calib, acs, calib_rows, "magnitude", None)
+            self.ky, self.kernel = 2, (2, self.kx)
+            return
+        self.accel, self.ky, self.kx, self.lam = _settings(accel, kernel, lam, calib, acs, calib_rows, "magnitude", None)
+        self.kernel = (self.ky, self.kx)
 
     def forward(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: Optional[torch.Tensor] = None,
                 output: str = "magnitude") -> torch.Tensor:
+        if self.accel is None:
+            _settings_gaps(self.gaps, self.max_gap, self.kernel, self.lam, self.calib, self.acs, self.calib_rows, output, sens_maps)
+            with torch.no_grad():
+                masked_kspace, mask, _ = _inputs("Grappa", masked_kspace, mask, sens_maps, self.gaps[-1], 2, self.kx, self.calib, self.acs,
+                                                 self.calib_rows)
+                res, info, count, unfilled = _run_gaps(masked_kspace, mask, sens_maps, self.gaps, self.max_gap, self.kx, self.lam, self.calib,
+                                                       self.acs, self.calib_rows, output)
+            self.last_info = {"info": info, "count": count, "unfilled": unfilled}
+            return res
         _settings(self.accel, self.kernel, self.lam, self.calib, self.acs, self.calib_rows, output, sens_maps)
         with torch.no_grad():
             masked_kspace, mask, _ = _inputs("Grappa", masked_kspace, mask, sens_maps, self.accel, self.ky, self.kx, self.calib, self.acs,

@@ -12,7 +12,10 @@
 //                         X <- X (2 I - A X), a number of steps fixed by ns and lam (the condition number is at most ns / lam + 1 by
 //                         construction); W = X G_st, one step of iterative refinement W += X (G_st - A W), and the residual of the W
 //                         that is handed out.  Every sum runs in a fixed order: the same bits on every call.
-//   cine_grappa_apply     the hot path: a skinny complex GEMM per lattice gap on v_mfma_f32_16x16x4_f32, see grappa_apply_kernel.
+//   cine_grappa_apply     the hot path: a skinny complex GEMM per lattice gap on v_mfma_f32_16x16x4_f32, see grappa_fill_gap.
+//   cine_grappa_gaps      unevenly spaced rows: one workgroup per frame lists the frame's gaps (lower source row, step) in ascending order,
+//                         an ordered compaction through an LDS prefix sum, no atomics.
+//   cine_grappa_apply_gaps  the hot path of those: the workgroup of cine_grappa_apply, its step and its weights taken from the gap.
 #include <cmath>
 #include <cstdint>
 #include <mutex>
@@ -286,6 +289,24 @@ struct GrappaApplyArgs {
     int c, h, w, R, ky, kx, ns, nsp, nr, groups;   // nsp: ns rounded up to 4
 };
 
+// N tiles of 16 columns in groups of at most 4 with accumulators of their own: the fewest tiles computed, then the fewest groups
+__host__ __device__ inline void grappa_tiling(int nr, int& ntg, int& groups) {
+    const int nt = (nr + 15) / 16;
+    int best = 1 << 30;
+    ntg = 1;
+    for (int k = 4; k >= 1; --k) {
+        const int padded = (nt + k - 1) / k * k;
+        if (padded < best) { best = padded; ntg = k; }
+    }
+    groups = (nt + ntg - 1) / ntg;
+}
+
+// dynamic LDS of one workgroup of grappa_fill_gap<ntg>
+__host__ __device__ inline size_t grappa_apply_lds(int ntg, int groups, int ky, int c, int nsp) {
+    const int ncol = 16 * ntg, pb = (ncol % 32 == 16) ? ncol : ncol + 16;
+    return ((size_t)ky * c * gr::PX + (size_t)gr::KC * pb) * sizeof(float2) + ((size_t)nsp + (size_t)3 * groups * ncol) * sizeof(int);
+}
+
 // the acquired rows (and every row of a frame without a lattice) of an out-of-place call, bit for bit
 __global__ __launch_bounds__(256) void grappa_copy_kernel(const float2* __restrict__ in, float2* __restrict__ out, const uint8_t* __restrict__ mask,
                                                           const int* __restrict__ offsets, long rows, int c, int h, int w, int R) {
@@ -300,8 +321,17 @@ __global__ __launch_bounds__(256) void grappa_copy_kernel(const float2* __restri
     for (int x = threadIdx.x; x < w; x += 256) dst[x] = src[x];
 }
 
-// Workgroup: x-tile blockIdx.x of lattice gap blockIdx.y - 1 of frame blockIdx.z; gap g holds the rows off + g R + m, m = 1 .. R - 1
-// (g = -1: the rows above the first lattice row).  All R - 1 target rows come from the ky source rows off + g R - base + j R, staged once:
+// One gap of one frame, what the workgroups of cine_grappa_apply and of cine_grappa_apply_gaps share.
+struct GrappaGap {
+    const float2* in;                            // the frame (c, h, w)
+    const float2* weights;                       // (R - 1, ns, c) of this gap's step
+    const uint8_t* mrow;                         // the frame's mask row (h)
+    float2* out;                                 // the frame
+    int c, h, w, R, ky, kx, ns, nsp, nr, groups; // R: the step of this gap; nsp: ns rounded up to 4
+    int y0;                                      // the targets are the rows y0 + m, m = 1 .. R - 1
+};
+
+// Workgroup: x-tile blockIdx.x of the gap.  All R - 1 target rows come from the ky source rows y0 - base + j R, staged once:
 //   out[x][n = (m - 1) c + q] = sum_k S[x][k] W[k][n],   k = (j, dx, coil),  S[x][k] = in[coil][row_j][x + dx - hx]
 // M = TX x-points (16 per wave), K = ns, N = (R - 1) c in `groups` groups of NTG 16-column tiles with accumulators of their own.
 // LDS (dynamic): S [ky c][PX] | Bs [KC][PB] float2 | koff [nsp] | noff, nrow, ncoil [groups 16 NTG] ints.
@@ -310,26 +340,18 @@ __global__ __launch_bounds__(256) void grappa_copy_kernel(const float2* __restri
 // apart, so the group covers 32 distinct slots (a group that straddles the last coil of a tap takes a two-way conflict).  The B fragment
 // [k = 4 q + (l >> 4)][n = l & 15] reads Bs[k PB + n] with PB = 16 (mod 32) likewise.  Weights come in chunks of KC k-values, whatever
 // ns is: at the upper limits one type is 229 KB.  Per output the k-ordered chain of cine_coil_compress: Cr += Ar Br, Ci += Ar Bi,
-// Cr += (-Ai) Bi, Ci += Ai Br, the chunks in ascending k into the same accumulators.
+// Cr += (-Ai) Bi, Ci += Ai Br, the chunks in ascending k into the same accumulators: the bits of an output depend on its sources and
+// its weights alone, not on NTG or on the grouping.
 template <int NTG>
-__global__ __launch_bounds__(gr::kThreads) void grappa_apply_kernel(GrappaApplyArgs g) {
+__device__ __forceinline__ void grappa_fill_gap(const GrappaGap& g) {
     using namespace gr;
     constexpr int NCOL = 16 * NTG;
     constexpr int PB = (NCOL % 32 == 16) ? NCOL : NCOL + 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char grappa_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = g.c, h = g.h, w = g.w, R = g.R, ns = g.ns, nsp = g.nsp;
-    const long f = blockIdx.z;
-    const int off = g.offsets[f];
-    if (off < 0 || off >= R) return;             // no lattice: the frame is left alone
-    const int y0 = off + ((int)blockIdx.y - 1) * R;
-    const uint8_t* mrow = g.mask + f * h;
-    bool any = false;
-    for (int m = 1; m < R; ++m) {
-        const int y = y0 + m;
-        any = any || (y >= 0 && y < h && !mrow[y]);
-    }
-    if (!any) return;                            // uniform: nothing to fill in this gap
+    const int y0 = g.y0;
+    const uint8_t* mrow = g.mrow;
 
     float2* S = reinterpret_cast<float2*>(grappa_lds);
     float2* Bs = S + g.ky * c * PX;
@@ -367,7 +389,7 @@ __global__ __launch_bounds__(gr::kThreads) void grappa_apply_kernel(GrappaApplyA
         const int j = rc / c, coil = rc - j * c;
         const int row = y0 - base + j * R, x = x0 - hx + xx;
         float2 v = zero;
-        if (row >= 0 && row < h && x >= 0 && x < w && xx < TX + g.kx - 1) v = g.in[((f * c + coil) * h + row) * w + x];
+        if (row >= 0 && row < h && x >= 0 && x < w && xx < TX + g.kx - 1) v = g.in[((long)coil * h + row) * w + x];
         S[e] = v;
     }
 
@@ -418,13 +440,189 @@ __global__ __launch_bounds__(gr::kThreads) void grappa_apply_kernel(GrappaApplyA
             const int col = grp * NCOL + 16 * n + fc;
             const int row = nrow[col];
             if (row < 0) continue;               // beyond (R - 1) c, outside the frame, or acquired
-            float2* dst = g.out + ((f * c + ncoil[col]) * h + row) * w;
+            float2* dst = g.out + ((long)ncoil[col] * h + row) * w;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int x = x0 + 16 * wave + 4 * fr + r;
                 if (x < w) dst[x] = make_float2(accr[n][r], acci[n][r]);
             }
         }
+    }
+}
+
+// Workgroup: x-tile blockIdx.x of lattice gap blockIdx.y - 1 of frame blockIdx.z; gap g holds the rows off + g R + m, m = 1 .. R - 1
+// (g = -1: the rows above the first lattice row), filled from the ky source rows off + g R - base + j R.
+template <int NTG>
+__global__ __launch_bounds__(gr::kThreads) void grappa_apply_kernel(GrappaApplyArgs g) {
+    const int h = g.h, R = g.R;
+    const long f = blockIdx.z;
+    const int off = g.offsets[f];
+    if (off < 0 || off >= R) return;             // no lattice: the frame is left alone
+    const int y0 = off + ((int)blockIdx.y - 1) * R;
+    const uint8_t* mrow = g.mask + f * h;
+    bool any = false;
+    for (int m = 1; m < R; ++m) {
+        const int y = y0 + m;
+        any = any || (y >= 0 && y < h && !mrow[y]);
+    }
+    if (!any) return;                            // uniform: nothing to fill in this gap
+    const long frame = f * g.c * h * g.w;
+    GrappaGap q;
+    q.in = g.in + frame; q.weights = g.weights; q.mrow = mrow; q.out = g.out + frame;
+    q.c = g.c; q.h = h; q.w = g.w; q.R = R; q.ky = g.ky; q.kx = g.kx;
+    q.ns = g.ns; q.nsp = g.nsp; q.nr = g.nr; q.groups = g.groups; q.y0 = y0;
+    grappa_fill_gap<NTG>(q);
+}
+
+// ------------------------------------------------------------------ unevenly spaced rows: the gap table and its application
+// Workgroup: frame blockIdx.x.  The acquired rows a_0 < ... < a_{n-1}; row a_i lists the leading end (i = 0), then the gap to a_{i+1} or
+// the trailing end (i = n - 1): at most two entries per row, placed by an exclusive prefix sum over the rows in chunks of 256.
+__global__ __launch_bounds__(256) void grappa_gaps_kernel(const uint8_t* __restrict__ mask, int* __restrict__ gaps, int* __restrict__ count,
+                                                          int* __restrict__ unfilled, int h, int cap, int max_gap, int allowed) {
+    __shared__ int sa[256], sb[256], sc[256];
+    const int tid = threadIdx.x;
+    const long f = blockIdx.x;
+    const uint8_t* m = mask + f * h;
+    int* tab = gaps + f * cap * 2;
+    int first = h, last = -1, n = 0;
+    for (int y = tid; y < h; y += 256)
+        if (m[y]) {
+            first = y < first ? y : first;
+            last = y > last ? y : last;
+            ++n;
+        }
+    sa[tid] = first; sb[tid] = last; sc[tid] = n;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) {
+            sa[tid] = sa[tid + s] < sa[tid] ? sa[tid + s] : sa[tid];
+            sb[tid] = sb[tid + s] > sb[tid] ? sb[tid + s] : sb[tid];
+            sc[tid] += sc[tid + s];
+        }
+        __syncthreads();
+    }
+    first = sa[0]; last = sb[0]; n = sc[0];
+    __syncthreads();
+    auto ok = [&](int G) { return G >= 2 && G <= max_gap && ((allowed >> G) & 1); };
+    int placed = 0, filled = 0;                  // entries placed so far (uniform); target rows of this thread's entries
+    for (int yb = 0; yb < h && n > 0; yb += 256) {
+        const int y = yb + tid;
+        int ne = 0, elo[2], eg[2];
+        if (y < h && m[y]) {
+            int d = 0;                           // the distance to the next acquired row, 0: none within max_gap
+            for (int k = 1; k <= max_gap && y + k < h; ++k)
+                if (m[y + k]) { d = k; break; }
+            if (y == first && y > 0) {           // the leading end: n >= 2 and no row within reach is a spacing above max_gap
+                int nb = n >= 2 ? (d ? d : max_gap + 1) : 0;
+                if (nb < 2) nb = 0;
+                const int G = nb > y + 1 ? nb : y + 1;
+                if (ok(G)) { elo[ne] = y - G; eg[ne] = G; ++ne; filled += y; }
+            }
+            if (y != last) {
+                if (ok(d)) { elo[ne] = y; eg[ne] = d; ++ne; filled += d - 1; }
+            } else if (y < h - 1) {              // the trailing end
+                const int e = h - 1 - y;
+                int b = 0;
+                for (int k = 1; k <= max_gap && y - k >= 0; ++k)
+                    if (m[y - k]) { b = k; break; }
+                int nb = n >= 2 ? (b ? b : max_gap + 1) : 0;
+                if (nb < 2) nb = 0;
+                const int G = nb > e + 1 ? nb : e + 1;
+                if (ok(G)) { elo[ne] = y; eg[ne] = G; ++ne; filled += e; }
+            }
+        }
+        sa[tid] = ne;
+        __syncthreads();
+        for (int s = 1; s < 256; s <<= 1) {      // inclusive prefix sum
+            const int v = tid >= s ? sa[tid - s] : 0;
+            __syncthreads();
+            sa[tid] += v;
+            __syncthreads();
+        }
+        int pos = placed + sa[tid] - ne;
+        for (int i = 0; i < ne; ++i, ++pos)
+            if (pos < cap) { tab[2 * pos] = elo[i]; tab[2 * pos + 1] = eg[i]; }
+        placed += sa[255];
+        __syncthreads();
+    }
+    if (placed > cap) placed = cap;              // cannot happen: a gap owns a run of missing rows, and there are at most (h + 1) / 2
+    for (int i = placed + tid; i < cap; i += 256) { tab[2 * i] = 0; tab[2 * i + 1] = 0; }
+    sc[tid] = filled;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sc[tid] += sc[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        count[f] = placed;
+        unfilled[f] = h - n - sc[0];
+    }
+}
+
+struct GrappaGapsArgs {
+    const float2* in;
+    const float2* weights;
+    const uint8_t* mask;
+    const int* gaps;
+    const int* count;
+    float2* out;
+    int c, h, w, cap, kx, ns, nsp;
+    int woff[9];                                 // per step: the offset of its (G - 1, ns, c) block in `weights`, or -1
+};
+
+// woff[G] of a step read from the table, -1 for a step outside 2 .. 8 (constant indices: the argument stays in scalar registers)
+__device__ __forceinline__ int grappa_gap_woff(const GrappaGapsArgs& a, int G) {
+    int o = -1;
+#pragma unroll
+    for (int k = 2; k <= 8; ++k) o = G == k ? a.woff[k] : o;
+    return o;
+}
+
+// every row that cine_grappa_apply_gaps does not write, bit for bit: acquired rows, rows of no listed gap, rows of a gap without weights
+__global__ __launch_bounds__(256) void grappa_copy_gaps_kernel(GrappaGapsArgs a, long rows) {
+    const long row = blockIdx.x;                 // (frame, coil, y)
+    if (row >= rows) return;
+    const int h = a.h, w = a.w;
+    const int y = (int)(row % h);
+    const long f = row / h / a.c;
+    int target = 0;
+    if (!a.mask[f * h + y]) {
+        int n = a.count[f];
+        n = n < a.cap ? n : a.cap;
+        const int* tab = a.gaps + f * a.cap * 2;
+        for (int i = threadIdx.x; i < n; i += 256) {
+            const int lo = tab[2 * i], G = tab[2 * i + 1];
+            if (grappa_gap_woff(a, G) >= 0 && y > lo && y < lo + G) target = 1;
+        }
+    }
+    if (__syncthreads_or(target)) return;
+    const float2* src = a.in + row * w;
+    float2* dst = a.out + row * w;
+    for (int x = threadIdx.x; x < w; x += 256) dst[x] = src[x];
+}
+
+// Workgroup: x-tile blockIdx.x of gap blockIdx.y of frame blockIdx.z.  The step G, and with it N = (G - 1) c, the tile grouping, the
+// skip tables and the LDS layout, are the gap's; the launch sizes the LDS for the largest step that has weights.
+__global__ __launch_bounds__(gr::kThreads) void grappa_apply_gaps_kernel(GrappaGapsArgs a) {
+    const long f = blockIdx.z;
+    const int gi = blockIdx.y;
+    if (gi >= a.count[f]) return;                // uniform, before anything is staged
+    const int* entry = a.gaps + (f * a.cap + gi) * 2;
+    const int lo = entry[0], G = entry[1];
+    const int wo = grappa_gap_woff(a, G);
+    if (wo < 0 || lo <= -G || lo >= a.h) return; // no weights for this step, or a gap outside the frame: left alone
+    const long frame = f * a.c * a.h * a.w;
+    GrappaGap q;
+    q.in = a.in + frame; q.weights = a.weights + wo; q.mrow = a.mask + f * a.h; q.out = a.out + frame;
+    q.c = a.c; q.h = a.h; q.w = a.w; q.R = G; q.ky = 2; q.kx = a.kx;
+    q.ns = a.ns; q.nsp = a.nsp; q.nr = (G - 1) * a.c; q.y0 = lo;
+    int ntg;
+    grappa_tiling(q.nr, ntg, q.groups);
+    switch (ntg) {
+        case 1: grappa_fill_gap<1>(q); break;
+        case 2: grappa_fill_gap<2>(q); break;
+        case 3: grappa_fill_gap<3>(q); break;
+        default: grappa_fill_gap<4>(q); break;
     }
 }
 
@@ -449,10 +647,8 @@ int gw_iters(int ns, double lam) {
 
 template <int NTG>
 int launch_apply(const GrappaApplyArgs& g, dim3 grid, hipStream_t st) {
-    constexpr int NCOL = 16 * NTG;
-    constexpr int PB = (NCOL % 32 == 16) ? NCOL : NCOL + 16;
     auto kern = grappa_apply_kernel<NTG>;
-    const size_t lds = ((size_t)g.ky * g.c * gr::PX + (size_t)gr::KC * PB) * sizeof(float2) + ((size_t)g.nsp + (size_t)3 * g.groups * NCOL) * sizeof(int);
+    const size_t lds = grappa_apply_lds(NTG, g.groups, g.ky, g.c, g.nsp);
     if (lds >= 64 * 1024) {
         static std::once_flag once[64];
         static hipError_t status[64];
@@ -624,14 +820,8 @@ extern "C" int cine_grappa_apply(const float* in, const float* weights, const ui
     g.out = reinterpret_cast<float2*>(out);
     g.c = c; g.h = h; g.w = w; g.R = R; g.ky = ky; g.kx = kx;
     g.ns = q.ns; g.nsp = (q.ns + 3) & ~3; g.nr = q.nr;
-    // N tiles of 16 in groups of at most 4: the fewest tiles computed, then the fewest groups
-    const int nt = ceil_div(q.nr, 16);
-    int ntg = 1, best = 1 << 30;
-    for (int k = 4; k >= 1; --k) {
-        const int padded = ceil_div(nt, k) * k;
-        if (padded < best) { best = padded; ntg = k; }
-    }
-    g.groups = ceil_div(nt, ntg);
+    int ntg;
+    grappa_tiling(q.nr, ntg, g.groups);
     const dim3 grid((unsigned)ceil_div(w, gr::TX), (unsigned)gaps, (unsigned)t);
     switch (ntg) {
         case 1: return launch_apply<1>(g, grid, st);
@@ -639,4 +829,85 @@ extern "C" int cine_grappa_apply(const float* in, const float* weights, const ui
         case 3: return launch_apply<3>(g, grid, st);
         default: return launch_apply<4>(g, grid, st);
     }
+}
+
+extern "C" int cine_grappa_gaps_cap(int h) { return h < 1 ? 0 : h / 2 + 1; }
+
+extern "C" int cine_grappa_gaps(const uint8_t* mask, int* gaps, int* count, int* unfilled, int t, int h, int max_gap, int allowed_bits,
+                                void* stream) {
+    CINE_REQUIRE(mask && gaps && count && unfilled && gaps != count && gaps != unfilled && count != unfilled, CINE_EINVAL,
+                 "cine_grappa_gaps: null or aliased pointers");
+    CINE_REQUIRE(t >= 1 && h >= 1, CINE_EINVAL, "cine_grappa_gaps: Invalid shapes. (frames %d, rows %d)", t, h);
+    CINE_REQUIRE(max_gap >= 2 && max_gap <= 8, CINE_EINVAL, "cine_grappa_gaps: max_gap %d, 2 .. 8 are supported", max_gap);
+    CINE_REQUIRE((allowed_bits & ~0x1FC) == 0, CINE_EINVAL, "cine_grappa_gaps: allowed_bits 0x%x, bit G stands for the step G in 2 .. 8", allowed_bits);
+    CINE_REQUIRE(gr_aligned(gaps, 4) && gr_aligned(count, 4) && gr_aligned(unfilled, 4), CINE_EINVAL,
+                 "cine_grappa_gaps: gaps, count and unfilled must be 4-byte aligned");
+    CINE_REQUIRE(h <= (1 << 20), CINE_EUNSUPPORTED, "cine_grappa_gaps: %d rows, at most 2^20", h);
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(F_MISC, st);
+    hipLaunchKernelGGL(grappa_gaps_kernel, dim3((unsigned)t), dim3(256), 0, st, mask, gaps, count, unfilled, h, cine_grappa_gaps_cap(h), max_gap,
+                       allowed_bits);
+    return check_launch("grappa_gaps_kernel");
+}
+
+extern "C" int cine_grappa_apply_gaps(const float* in, const float* weights, const int* woff, const uint8_t* mask, const int* gaps, const int* count,
+                                      float* out, int t, int c, int h, int w, int cap, int kx, void* stream) {
+    CINE_REQUIRE(in && weights && woff && mask && gaps && count && out, CINE_EINVAL, "cine_grappa_apply_gaps: null pointer");
+    CINE_REQUIRE(t >= 1 && c >= 1 && h >= 1 && w >= 1 && cap >= 1, CINE_EINVAL,
+                 "cine_grappa_apply_gaps: Invalid shapes. (frames %d, coils %d, %d x %d, %d table entries per frame)", t, c, h, w, cap);
+    CINE_REQUIRE(kx == 3 || kx == 5 || kx == 7, CINE_EINVAL,
+                 "cine_grappa_apply_gaps: kernel 2 x %d (3, 5 or 7 columns; two source rows, the neighbours of the gap, is all there is)", kx);
+    CINE_REQUIRE(c <= gr::kMaxCoils, CINE_EUNSUPPORTED, "cine_grappa_apply_gaps: %d coils, at most %d", c, gr::kMaxCoils);
+    int g_max = 0;
+    for (int G = 2; G <= 8; ++G) {
+        CINE_REQUIRE(woff[G] >= -1, CINE_EINVAL, "cine_grappa_apply_gaps: woff[%d] = %d, an offset in complex elements or -1", G, woff[G]);
+        if (woff[G] >= 0) g_max = G;
+    }
+    CINE_REQUIRE(g_max >= 2, CINE_EINVAL, "cine_grappa_apply_gaps: woff names no step 2 .. 8 with weights");
+    GrappaGeom q;
+    CINE_REQUIRE(grappa_geom(c, g_max, 2, kx, q), CINE_EUNSUPPORTED,
+                 "cine_grappa_apply_gaps: n_aug = 2 x %d x %d coils + %d x %d coils = %d, at most %d", kx, c, g_max - 1, c,
+                 2 * kx * c + (g_max - 1) * c, gr::kMaxAug);
+    CINE_REQUIRE(gr_aligned(in, 8) && gr_aligned(out, 8) && gr_aligned(weights, 8) && gr_aligned(gaps, 4) && gr_aligned(count, 4), CINE_EINVAL,
+                 "cine_grappa_apply_gaps: in, out and weights must be 8-byte aligned, gaps and count 4-byte aligned");
+    CINE_REQUIRE(t <= 65535 && cap <= 65535, CINE_EUNSUPPORTED, "cine_grappa_apply_gaps: %d frames, %d table entries per frame, at most 65535 each", t,
+                 cap);
+    const long rows = (long)t * c * h;
+    CINE_REQUIRE(rows <= 2147483647L, CINE_EUNSUPPORTED, "cine_grappa_apply_gaps: %ld rows, at most 2^31 - 1", rows);
+    const size_t bytes = (size_t)rows * w * sizeof(float2);
+    const char *ib = reinterpret_cast<const char*>(in), *ob = reinterpret_cast<const char*>(out);
+    CINE_REQUIRE(in == out || ib + bytes <= ob || ob + bytes <= ib, CINE_EINVAL,
+                 "cine_grappa_apply_gaps: out overlaps in (out == in is the in-place call)");
+
+    GrappaGapsArgs a{};
+    a.in = reinterpret_cast<const float2*>(in);
+    a.weights = reinterpret_cast<const float2*>(weights);
+    a.mask = mask; a.gaps = gaps; a.count = count;
+    a.out = reinterpret_cast<float2*>(out);
+    a.c = c; a.h = h; a.w = w; a.cap = cap; a.kx = kx;
+    a.ns = q.ns; a.nsp = (q.ns + 3) & ~3;
+    size_t lds = 0;                              // of the largest layout among the steps that have weights
+    for (int G = 0; G <= 8; ++G) {
+        a.woff[G] = G >= 2 ? woff[G] : -1;
+        if (a.woff[G] < 0) continue;
+        int ntg, groups;
+        grappa_tiling((G - 1) * c, ntg, groups);
+        const size_t need = grappa_apply_lds(ntg, groups, 2, c, a.nsp);
+        lds = need > lds ? need : lds;
+    }
+    auto kern = grappa_apply_gaps_kernel;
+    if (lds >= 64 * 1024) {
+        static std::once_flag once[64];
+        static hipError_t status[64];
+        if (int e = large_lds_opt_in(reinterpret_cast<const void*>(kern), "cine_grappa_apply_gaps", once, status)) return e;
+    }
+    hipStream_t st = as_stream(stream);
+    ProfScope prof(F_MISC, st);
+    if (in != out) {
+        hipLaunchKernelGGL(grappa_copy_gaps_kernel, dim3((unsigned)rows), dim3(256), 0, st, a, rows);
+        if (int e = check_launch("grappa_copy_gaps_kernel")) return e;
+    }
+    const dim3 grid((unsigned)ceil_div(w, gr::TX), (unsigned)cap, (unsigned)t);
+    hipLaunchKernelGGL(kern, grid, dim3(gr::kThreads), lds, st, a);
+    return check_launch("grappa_apply_gaps_kernel");
 }

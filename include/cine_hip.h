@@ -1279,6 +1279,48 @@ int cine_grappa_weights(const double* gram, float* weights, double* info, void* 
                         double lam, void* stream);
 int cine_grappa_apply(const float* in, const float* weights, const uint8_t* mask, const int* offsets, float* out, int t, int c, int h,
                       int w, int R, int ky, int kx, void* stream);
+/* GRAPPA on unevenly spaced rows (a frame that is no lattice, e.g. the reference's equispaced masks with their rounded non-integer
+ * step): a frame is a list of gaps, and a gap of step G is filled with the lattice weights of R = G.  Only ky = 2: the sources of a
+ * missing row are its two acquired neighbours.
+ * The rule, per frame, with a_0 < ... < a_{n-1} the acquired rows, max_gap <= 8 and `allowed` the set of steps that have weights:
+ *   interior gap   consecutive acquired rows G = a_{i+1} - a_i >= 2 apart: the gap (lo = a_i, G); targets lo + m, m = 1 .. G - 1, of
+ *                  type m; sources lo and lo + G.
+ *   leading end    the rows [0, a_0), e > 0 of them: G = max(nb, e + 1), nb = a_1 - a_0 if n >= 2 and that spacing is >= 2, else 0;
+ *                  the gap (a_0 - G, G).  Its lower source row is outside the frame and reads as zero; targets below row 0 are skipped.
+ *   trailing end   the mirror image: nb = a_{n-1} - a_{n-2}, the gap (a_{n-1}, G), the upper source row outside the frame.
+ *   unfilled       a gap or end with G > max_gap or G not in `allowed` is not listed; its rows stay as they are and are counted in
+ *                  unfilled[f].  A frame with n = 0 is left alone: count 0, unfilled = h.
+ *   order          ascending lo, the leading end first.
+ *   out[f, q, lo + m, x] = sum_{j, dx, k} W_G[m - 1][(j, dx, k)][q] in[f, k, lo + j G, x + dx - hx]
+ * with W_G the weights of cine_grappa_weights(R = G, ky = 2, kx), source samples outside [0, h) x [0, w) zero, acquired rows never
+ * written.  A frame that is a lattice of step R, 2 <= R <= 8, has every gap, both ends included, of step R, and the gap path then
+ * gives the bits of cine_grappa_apply; next to an ACS block or a stray extra row the two differ by design: the gap path predicts from
+ * the nearer rows.
+ *
+ * cine_grappa_gaps_cap: the entries per frame of a gap table of h rows, h / 2 + 1 (a gap owns a run of missing rows); 0 for h < 1.
+ * cine_grappa_gaps: mask (t, h) -> gaps (t, cap, 2) int32 pairs (lo, G), cap = cine_grappa_gaps_cap(h), count (t) and unfilled (t)
+ * int32.  allowed_bits: bit G set for every step G in `allowed` (bits outside 2 .. 8: CINE_EINVAL).  One workgroup per frame; each
+ * acquired row finds its neighbours within max_gap rows, and the entries are placed by an LDS prefix sum over the rows in row order:
+ * no atomics, the same table on every call; entries at and beyond count[f] are (0, 0).  max_gap outside 2 .. 8, null or aliased
+ * pointers, outputs off their 4-byte alignment: CINE_EINVAL; h above 2^20: CINE_EUNSUPPORTED.
+ * cine_grappa_apply_gaps: the application above.  weights: one buffer that holds the (G - 1, ns, c) complex64 blocks of the steps with
+ * weights, each as cine_grappa_weights wrote it; woff: 9 ints on the host, woff[G] the offset of the block of step G in complex
+ * elements or -1 (woff[0], woff[1] are not read; a value below -1, or no step with weights: CINE_EINVAL).  The workgroup is that of
+ * cine_grappa_apply: 64 x-points of one table entry of one frame, the two source rows staged once, all G - 1 target rows on
+ * v_mfma_f32_16x16x4_f32 with the same k-ordered chain per output; N = (G - 1) c, the tile grouping, the skip tables and the LDS
+ * layout follow the entry, the LDS is sized for the largest step with weights.  A workgroup whose entry index is >= count[f] ends
+ * before it stages anything; an entry whose step has no weights, or that lies outside the frame, is left alone.  out == in works in
+ * place and gives the bits of the out-of-place call; with out != in every row that is not written (acquired rows, unfilled rows, empty
+ * frames) is copied bit for bit first; any other overlap is CINE_EINVAL.  Limits and alignment as cine_grappa_apply: c <= 32 and
+ * ns + (G_max - 1) c <= 1152 for the largest step with weights (else CINE_EUNSUPPORTED), in, out, weights 8-byte aligned, gaps and
+ * count 4-byte aligned, kx outside {3, 5, 7}: CINE_EINVAL; more than 65535 frames or table entries per frame, more than 2^31 - 1 rows:
+ * CINE_EUNSUPPORTED.  Both entries check every argument before the first launch; no allocation, no host read, no synchronisation, no
+ * atomics: capturable. */
+int cine_grappa_gaps_cap(int h);
+int cine_grappa_gaps(const uint8_t* mask, int* gaps, int* count, int* unfilled, int t, int h, int max_gap, int allowed_bits,
+                     void* stream);
+int cine_grappa_apply_gaps(const float* in, const float* weights, const int* woff, const uint8_t* mask, const int* gaps,
+                           const int* count, float* out, int t, int c, int h, int w, int cap, int kx, void* stream);
 /* Welford's update of (mean, m2) with the k-th sample x, k >= 1, element-wise over n floats, in float64:
  *   d = x - mean;  mean += d / k;  m2 += d * (x - mean)
  * k == 1 initialises both buffers (they are not read and need not be zeroed).  Null pointers, n <= 0, k < 1, mean == m2: CINE_EINVAL. */

@@ -2,6 +2,7 @@
 """What GRAPPA / TGRAPPA (cine_hip.grappa) costs at 1 x 15 frames x 15 coils x 200 x 200, R = 4, kernel 2 x 5, in ONE process.
 
     python tools/grappa_rate.py [--out profiles/grappa_rate.json] [--commit SHA]
+    python tools/grappa_rate.py --gaps [--out profiles/grappa_gaps_rate.json] [--commit SHA]
 
 Mask: an interleaved lattice of step 4 without ACS lines; TGRAPPA on the central 32 rows of the temporal average; lam = 1e-4.
 hipEvent medians of 10 calls each:
@@ -13,7 +14,16 @@ hipEvent medians of 10 calls each:
     the output says which), the application as ``torch.nn.functional.conv2d`` with dilation (R, 1) on the 2c real channels, one call per
     type over every row of every frame, and a ``torch.where`` scatter of the target rows;
   * peak memory of both above the baseline, and slices per second of ``Grappa`` through ``SlicePipeline`` (graphs, 4 slots, device inputs).
---out writes the document, stamped with the commit and a sha256 over csrc/."""
+--out writes the document, stamped with the commit and a sha256 over csrc/.
+
+--gaps measures the path for unevenly spaced rows (``accel=None``) instead, same shape, kernel and lam, hipEvent medians of 10:
+  (a) on the pure lattice of step 4, ``cine_grappa_apply_gaps`` beside ``cine_grappa_apply`` with the same weights (equal work: the gap
+      kernel adds one table read per workgroup and a weight base per gap), and the figure of profiles/grappa_rate.json if it is there;
+  (b) on the mask of ``synth.EquispacedMaskFunc([0.08], [4])`` (seed 0; calibrated on its centre block): ``cine_grappa_gaps``, the fit of
+      the steps that occur and of the module's default steps (one Gram matrix and one solve per step), ``cine_grappa_apply_gaps`` and the whole ``grappa(accel=None)`` call (check off)
+      in turn with a composed torch path -- per step the patch matrix, ``torch.linalg.solve`` and one dilated ``conv2d`` plus
+      ``torch.where`` per row type -- with the peak memory of both;
+  (c) slices per second of ``Grappa(accel=None)`` through a 4-slot ``SlicePipeline``."""
 import argparse
 import json
 import os
@@ -43,11 +53,172 @@ def device_solve_works(dev):
         return False
 
 
+def pipeline_rate(model, mk, mask):
+    from cine_hip.pipeline import SlicePipeline
+    with SlicePipeline(model, slots=SLOTS) as pipe:
+        pipe.submit(mk, mask, tag="build")
+        list(pipe.drain())
+        rates = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for j in range(SLICES):
+                pipe.submit(mk, mask, tag=j)
+                for _ in pipe.results():
+                    pass
+            list(pipe.drain())
+            torch.cuda.synchronize()
+            rates.append(SLICES / (time.perf_counter() - t0))
+    return {"slots": SLOTS, "slices": SLICES, "slices_per_s": median(rates), "runs": rates}
+
+
+def gaps_main(args):
+    import numpy as np
+    from cine_hip import grappa as G, ops, synth
+    from pipeline_rate import _stamp
+    dev = torch.device("cuda:0")
+    ex = synth.make_cine_slice(T, C, H, W, accel=4, seed=0, noise_std=0.01)
+    commit, csrc = _stamp(args.commit)
+    solve_on_device = device_solve_works(dev)
+    ns, hx = KY * KX * C, KX // 2
+    doc = {"shape": [1, T, C, H, W], "kernel": [KY, KX], "lam": LAM, "device": torch.cuda.get_device_name(dev),
+           "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "steps": STEPS, "commit": commit, "csrc_sha256": csrc, "ns": ns,
+           "composed_solve": "torch.linalg.solve in complex128 on the " + ("device" if solve_on_device else "host")}
+    st = ops._stream
+    with torch.no_grad():
+        full = ex["kspace"].to(dev)
+
+        # ---- (a) equal work on the pure lattice of step 4
+        lat = G.lattice_mask(T, H, R).to(dev)
+        mk = ops.apply_mask(full, lat)
+        off, _ = G.lattice_offsets(lat, R)
+        cal = G.calibration_data(mk, lat, "tgrappa", None, CALIB_ROWS)
+        weights, _ = G.grappa_weights(cal[0], R, (KY, KX), LAM)
+        table, count, unfilled = G.gap_table(lat, (R,))
+        assert not bool(unfilled.any())
+        out_l, out_g = torch.empty_like(mk), torch.empty_like(mk)
+        m2 = lat.view(T, H)
+        parts = {
+            "cine_grappa_apply": lambda: G.grappa_apply(mk[0], weights, m2, off[0], R, (KY, KX), out=out_l[0]),
+            "cine_grappa_apply_gaps": lambda: G.grappa_apply_gaps(mk[0], weights, (R,), m2, table[0], count[0], (KY, KX), out=out_g[0]),
+            "cine_grappa_apply_in_place": lambda: G.grappa_apply(out_l[0], weights, m2, off[0], R, (KY, KX), out=out_l[0]),
+            "cine_grappa_apply_gaps_in_place": lambda: G.grappa_apply_gaps(out_g[0], weights, (R,), m2, table[0], count[0], (KY, KX), out=out_g[0]),
+        }
+        us = {}
+        for rnd in range(2):                                             # in turn, twice: the second round is what is reported
+            for k, fn in parts.items():
+                us[k] = median(measure(fn, dev)[0]) * 1e3
+        assert torch.equal(out_l, out_g)
+        a = {"mask": "interleaved lattice of step 4, no ACS lines", "entry_us": us,
+             "gaps_over_lattice": us["cine_grappa_apply_gaps"] / us["cine_grappa_apply"],
+             "gaps_over_lattice_in_place": us["cine_grappa_apply_gaps_in_place"] / us["cine_grappa_apply_in_place"]}
+        published = os.path.join(ROOT, "profiles", "grappa_rate.json")
+        if os.path.exists(published):
+            with open(published) as f:
+                old = json.load(f)
+            a["published_lattice_us"] = {k: old["entry_us"][k] for k in ("cine_grappa_apply", "cine_grappa_apply_in_place")}
+            a["published_commit"] = old.get("commit")
+            a["gaps_over_published_lattice"] = us["cine_grappa_apply_gaps"] / old["entry_us"]["cine_grappa_apply"]
+        doc["lattice"] = a
+        print(json.dumps({"lattice": a}), flush=True)
+
+        # ---- (b) the reference's equispaced mask
+        row = synth.EquispacedMaskFunc([0.08], [4])((T, 1, H, 1, 2), seed=0).numpy().reshape(H) != 0
+        n_low = int(round(H * 0.08))
+        acs = ((H - n_low + 1) // 2, (H - n_low + 1) // 2 + n_low)
+        mask = torch.from_numpy(np.repeat(row[None], T, 0).astype(np.uint8).reshape(1, T, 1, H, 1, 1)).to(dev)
+        plan, sizes, left = G.plan_gaps(mask)
+        assert not left.any()
+        mk = ops.apply_mask(full, mask)
+        m2 = mask.view(T, H)
+        cal = G.calibration_data(mk, mask, "acs", acs)
+        weights, info = G.grappa_weights_gaps(cal[0], sizes, (KY, KX), LAM)
+        table, count, _ = G.gap_table(mask, sizes)
+        out = torch.empty_like(mk)
+        n_targets = int((~row).sum()) * T
+        parts = {
+            "cine_grappa_gaps": lambda: G.gap_table(mask, sizes),
+            "fit_all_steps": lambda: G.grappa_weights_gaps(cal[0], sizes, (KY, KX), LAM),
+            "cine_grappa_apply_gaps": lambda: G.grappa_apply_gaps(mk[0], weights, sizes, m2, table[0], count[0], (KY, KX), out=out[0]),
+            "cine_grappa_apply_gaps_in_place": lambda: G.grappa_apply_gaps(out[0], weights, sizes, m2, table[0], count[0], (KY, KX), out=out[0]),
+        }
+        default = G.Grappa().gaps                                       # the steps of the module's default: five Gram / solve pairs
+        parts["fit_steps_" + "_".join(map(str, default))] = lambda: G.grappa_weights_gaps(cal[0], default, (KY, KX), LAM)
+        for G_ in sizes:
+            parts[f"fit_step_{G_}"] = (lambda g: (lambda: G.grappa_weights(cal[0], g, (KY, KX), LAM)))(G_)
+        us = {k: median(measure(fn, dev)[0]) * 1e3 for k, fn in parts.items()}
+        b = {"mask": "EquispacedMaskFunc([0.08], [4]), seed 0, the same for every frame", "acs": list(acs), "gap_steps": list(sizes),
+             "gaps_per_frame": len(plan[0][0]), "target_rows": n_targets, "entry_us": us, "weights_info": info.cpu().tolist()}
+        flops = 8.0 * n_targets * W * ns * C
+        b["apply_tflops"] = flops / us["cine_grappa_apply_gaps_in_place"] * 1e-6
+        print(json.dumps({"equispaced": b}), flush=True)
+
+        def fused():
+            return G.grappa(mk, mask, None, kernel=(KY, KX), lam=LAM, acs=acs, output="kspace", check=False, gaps=sizes)
+
+        rows_t = torch.from_numpy(row).to(dev)
+        targets = {}                                                     # (step, type) -> (h,) rows of that type
+        for lo, g in plan[0][0]:
+            for m in range(1, g):
+                if 0 <= lo + m < H:
+                    targets.setdefault((g, m), torch.zeros(H, dtype=torch.bool, device=dev))[lo + m] = True
+
+        def composed():
+            k = torch.view_as_complex(mk[0])                             # (t, c, h, w)
+            cb = k[:, :, acs[0]:acs[1]].mean(0).to(torch.complex128)     # every frame acquired the block
+            x = torch.cat((k.real, k.imag), 1)
+            filled = x
+            for g in sizes:
+                my, mx = (acs[1] - acs[0]) - g, W - KX + 1
+                cols = [cb[:, j * g:j * g + my, dx:dx + mx] for j in range(KY) for dx in range(KX)]
+                cols += [cb[:, m:m + my, hx:hx + mx] for m in range(1, g)]
+                P = torch.stack(cols, 0).reshape(-1, my * mx).transpose(0, 1)
+                Gm = P.conj().transpose(0, 1) @ P
+                A = Gm[:ns, :ns] + LAM * Gm[:ns, :ns].diagonal().real.sum() / ns * torch.eye(ns, dtype=torch.complex128, device=dev)
+                Wc = torch.linalg.solve(A, Gm[:ns, ns:]) if solve_on_device else torch.linalg.solve(A.cpu(), Gm[:ns, ns:].cpu()).to(dev)
+                Wc = Wc.to(torch.complex64).reshape(KY, KX, C, g - 1, C)
+                for m in range(1, g):
+                    if (g, m) not in targets:
+                        continue
+                    wq = Wc[:, :, :, m - 1].permute(3, 2, 0, 1)
+                    wt = torch.cat((torch.cat((wq.real, -wq.imag), 1), torch.cat((wq.imag, wq.real), 1)), 0).contiguous()
+                    y = F.conv2d(F.pad(x, (hx, hx, m, g - m)), wt, dilation=(g, 1))
+                    filled = torch.where(targets[(g, m)][None, None, :, None], y, filled)
+            return torch.stack((filled[:, :C], filled[:, C:]), -1)[None]
+
+        kf, kc = fused(), composed()
+        b["fused_vs_composed_max_abs_over_peak"] = float((kf - kc).abs().max() / kc.abs().max())
+        del kf, kc
+        for variant, fn in (("fused", fused), ("composed", composed), ("fused_again", fused), ("composed_again", composed)):
+            G.release_workspaces()
+            torch.cuda.empty_cache()
+            ms, peak = measure(fn, dev)
+            b[variant] = {"median_ms": median(ms), "ms": ms, "peak_bytes": peak}
+            print(json.dumps({variant: b[variant]}), flush=True)
+        ms, _ = measure(lambda: G.grappa(mk, mask, None, kernel=(KY, KX), lam=LAM, acs=acs, output="kspace", check=False, gaps=default), dev)
+        b["fused_default_steps"] = {"gaps": list(default), "median_ms": median(ms), "ms": ms}
+        b["composed_over_fused"] = b["composed"]["median_ms"] / b["fused"]["median_ms"]
+        b["peak_fused_over_composed"] = b["fused"]["peak_bytes"] / b["composed"]["peak_bytes"]
+        doc["equispaced"] = b
+
+        # ---- (c) through the pipeline
+        model = G.Grappa(accel=None, gaps=sizes, kernel=(KY, KX), lam=LAM, acs=acs).eval()
+        doc["pipeline"] = dict(pipeline_rate(model, mk, mask), model=f"Grappa(accel=None, gaps={tuple(sizes)})")
+        print(json.dumps({"pipeline": doc["pipeline"]}), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None, help="the commit to stamp the result with (default: git rev-parse HEAD)")
+    ap.add_argument("--gaps", action="store_true", help="measure the path for unevenly spaced rows (accel=None)")
     args = ap.parse_args()
+    if args.gaps:
+        return gaps_main(args)
     from cine_hip import grappa as G, ops, synth
     from cine_hip._lib import lib
     from cine_hip.pipeline import SlicePipeline
