@@ -36,12 +36,13 @@ from . import synth  # noqa: F401,E402  (host-only, numpy)
 
 __all__ = ["synth", "fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
            "TotalVariation", "locally_low_rank", "LocallyLowRank", "lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "grappa",
-           "Grappa", "plan_gaps", "gap_table", "grappa_weights_gaps", "grappa_apply_gaps"]
+           "Grappa", "plan_gaps", "gap_table", "grappa_weights_gaps", "grappa_apply_gaps", "grappa_image_weights",
+           "grappa_gfactor_from_weights", "grappa_noise_maps"]
 
 _CLASSICAL = ("fista_momentum", "kt_sparse_sense", "KtSparseSense", "low_rank_plus_sparse", "LowRankPlusSparse", "total_variation",
               "TotalVariation", "locally_low_rank", "LocallyLowRank")
 _GRAPPA = ("lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "Grappa", "plan_gaps", "gap_table", "grappa_weights_gaps",
-           "grappa_apply_gaps")
+           "grappa_apply_gaps", "grappa_image_weights", "grappa_gfactor_from_weights", "grappa_noise_maps")
 
 
 def __getattr__(name):

@@ -33,10 +33,26 @@ such a gap stay as they are and are counted (``unfilled``).  The reference's equ
 (``synth.RandomMaskFunc``) are not what this is for either: at acceleration 4 some 61 % of their missing rows lie in gaps above 8; the
 proximal baselines of ``cine_hip.classical`` (k-t SPARSE-SENSE, L+S, TV, LLR) are the tools for those.
 
+ANALYTIC NOISE MAPS.  On a lattice the reconstruction is linear and shift-invariant, so its noise map has a closed form (Breuer et al.,
+MRM 62:739, 2009): the ``accel - 1`` kernels are one convolution kernel, its transform is a ``c x c`` matrix ``Wimg`` per pixel
+(``grappa_image_weights``), and a linear coil combination ``p`` has the noise variance ``p Wimg Psi Wimg^H p^H``.
+``grappa_gfactor_from_weights`` gives g and the standard deviation from a set of weights in one launch of ``cine_grappa_gfactor``,
+which never writes ``Wimg`` out; ``grappa_noise_maps`` and ``Grappa.noise_maps`` calibrate as ``grappa`` does and hand out the maps
+for ``p = conj(S)`` or per coil.  The conventions are those of ``cine_hip.noise``: noise ``scale^2 Psi`` on every acquired sample
+(``add_noise``), ``std`` the standard deviation of the complex pixel (``ReplicaStats(pairs=True)``), ``g = std_accel / (std_full
+sqrt(R))`` (``noise.g_factor``); ``noise.pseudo_replica`` measures the same maps with ``2 x replicas`` reconstructions and a sampling
+error of ``1 / sqrt(2 N)``.  What the closed form leaves out: the kernels treat rows and columns outside the frame as zero where the
+formula wraps around (a little less noise near the edges, visible on small matrices); ACS rows are kept as acquired where the formula
+knows the lattice only (the map is that of the lattice everywhere); ``h`` need not be a multiple of ``accel`` and the formula uses
+``accel``; and the weights count as fixed -- the noise of a calibration that is refitted on every noisy replica is not in it.
+Unevenly spaced rows (``accel=None``) are not shift-invariant and have no such map.
+
 Not built: gaps above 8 rows (the equispaced masks at acceleration 8), ``ky = 4`` on uneven masks, masks that vary along w, a batched
 Gram / solve over the steps (one pair per step runs in sequence), k-t GRAPPA with temporal source points, through-time calibration per
-frame, image-domain application, and a g-factor from the weights (``noise.pseudo_replica`` measures one).
+frame, image-domain application of the weights to the data, noise maps that know the ACS block or the zero boundary, and noise maps of
+the gap path.
 """
+import collections
 import ctypes
 import threading
 from typing import Optional, Sequence, Tuple
@@ -49,7 +65,10 @@ from . import ops
 from ._lib import CineHipError, check, lib
 
 __all__ = ["lattice_mask", "plan_lattice", "calibration_data", "grappa_weights", "grappa_apply", "lattice_offsets", "grappa", "Grappa",
-           "RESIDUAL_MAX", "plan_gaps", "gap_table", "grappa_weights_gaps", "grappa_apply_gaps", "MAX_GAP"]
+           "RESIDUAL_MAX", "plan_gaps", "gap_table", "grappa_weights_gaps", "grappa_apply_gaps", "MAX_GAP", "GfactorMaps",
+           "grappa_image_weights", "grappa_gfactor_from_weights", "grappa_noise_maps"]
+
+GfactorMaps = collections.namedtuple("GfactorMaps", "g std")
 
 MAX_COILS, MAX_AUG = 32, 1152
 MAX_GAP = 8                # the largest step a gap can have: the lattice kernels exist for 2 .. 8
@@ -428,6 +447,125 @@ def grappa_apply(kspace: torch.Tensor, weights: torch.Tensor, mask: torch.Tensor
     return out
 
 
+# ------------------------------------------------------------------ analytic noise maps
+def _weights_for_maps(what, weights, accel, kernel, h, w):
+    """(accel, ky, kx, c, h, w) with every shape checked, before anything asks for a device."""
+    accel, (ky, kx) = _accel(accel), _kernel(kernel)
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"{what}: h = {h}, w = {w}")
+    if not isinstance(weights, torch.Tensor):
+        raise TypeError(f"{what} weights: expected a tensor")
+    if weights.dim() != 4 or weights.shape[-1] != 2 or weights.shape[0] != accel - 1 or weights.shape[2] < 1 \
+            or weights.shape[1] != ky * kx * weights.shape[2]:
+        raise ValueError(f"{what}: weights {tuple(weights.shape)}: expected ({accel - 1}, {ky} x {kx} x c, c, 2) for accel {accel} and a "
+                         f"{ky} x {kx} kernel (grappa_weights)")
+    c = weights.shape[2]
+    _geometry(c, accel, ky, kx)
+    return accel, ky, kx, c, h, w
+
+
+def grappa_image_weights(weights: torch.Tensor, accel: int, kernel, h: int, w: int) -> torch.Tensor:
+    """weights (accel - 1, ns, c, 2) of ``grappa_weights`` -> the image-domain weights (c, c, h, w, 2) of an h x w frame
+    (``cine_grappa_image_weights``): ``out[q, k]`` is the map that coil image k contributes to coil image q,
+    ``ifft2c(reconstruction)[q] = sum_k out[q, k] * ifft2c(zero-filled lattice)[k]`` up to the zero boundary of the k-space kernels.
+    c^2 h w complex numbers (72 MB at 15 coils, 200 x 200): for a look at the weights or a check; the noise maps do not need it."""
+    from .classical import _no_grad_inputs
+    _no_grad_inputs("grappa_image_weights", weights=weights)
+    accel, ky, kx, c, h, w = _weights_for_maps("grappa_image_weights", weights, accel, kernel, h, w)
+    weights = ops._dev(weights, "grappa_image_weights weights")
+    out = torch.empty((c, c, h, w, 2), device=weights.device, dtype=torch.float32)
+    check(lib().cine_grappa_image_weights(weights.data_ptr(), out.data_ptr(), c, h, w, accel, ky, kx, ops._stream()),
+          "cine_grappa_image_weights")
+    return out
+
+
+def grappa_gfactor_from_weights(weights: torch.Tensor, accel: int, kernel, h: int, w: int, chol: Optional[torch.Tensor] = None,
+                                coef: Optional[torch.Tensor] = None, scale: float = 1.0) -> GfactorMaps:
+    """The analytic noise maps of the lattice reconstruction with these weights on an h x w frame, ``GfactorMaps(g, std)``, one launch of
+    ``cine_grappa_gfactor``; no host read.
+
+    ``chol``: L (c, c) complex64 of ``noise.noise_cholesky`` (noise covariance ``scale^2 L L^H`` on every acquired sample, what
+    ``noise.add_noise`` adds), None: white.  ``coef``: the coefficients p (n, c, h, w, 2) of the linear combination ``sum_q p_q x_q`` of
+    the coil images whose noise is asked for -- ``conj(S)`` for the combination with sensitivity maps -- or None: every coil image on
+    its own.  The maps are float32 (n, h, w) with ``coef`` and (c, h, w) without: ``std = scale * sqrt(p Wimg Psi Wimg^H p^H / accel)``,
+    the standard deviation of the complex pixel, and ``g = std_accel / (std_full * sqrt(accel))``, 0 where ``p Psi p^H`` is 0.
+    A root-sum-of-squares image is not linear in the data; to first order its noise is that of the combination with the image's own
+    phase, ``coef = conj(x_q) / rss`` per pixel from the reconstructed coil images x_q (``x = ops.fft2c(filled[i, f], inverse=True)`` of one frame,
+    ``coef = x * x.new_tensor([1.0, -1.0]) / (x ** 2).sum((0, -1)).sqrt()[None, ..., None]``), passed here with n = 1."""
+    from .classical import _no_grad_inputs
+    from .noise import _chol_pairs
+    _no_grad_inputs("grappa_gfactor_from_weights", weights=weights, chol=chol, coef=coef)
+    accel, ky, kx, c, h, w = _weights_for_maps("grappa_gfactor_from_weights", weights, accel, kernel, h, w)
+    low = _chol_pairs(chol, c, weights.device)                       # its type and shape first, then where it is
+    weights = ops._dev(weights, "grappa_gfactor_from_weights weights")
+    n = c
+    if coef is not None:
+        coef = ops._dev(coef, "grappa_gfactor_from_weights coef")
+        if coef.dim() != 5 or tuple(coef.shape[1:]) != (c, h, w, 2) or coef.shape[0] < 1:
+            raise ValueError(f"grappa_gfactor_from_weights: coef {tuple(coef.shape)}: expected (n, {c}, {h}, {w}, 2)")
+        if coef.device != weights.device:
+            raise CineHipError(f"grappa_gfactor_from_weights: coef is on {coef.device}, the weights on {weights.device}")
+        n = coef.shape[0]
+    g = torch.empty((n, h, w), device=weights.device, dtype=torch.float32)
+    amp = torch.empty((n, h, w), device=weights.device, dtype=torch.float32)
+    check(lib().cine_grappa_gfactor(weights.data_ptr(), ops._p(low), ops._p(coef), g.data_ptr(), amp.data_ptr(), n if coef is not None else 1,
+                                    c, h, w, accel, ky, kx, ops._stream()), "cine_grappa_gfactor")
+    return GfactorMaps(g, amp.mul_(float(scale) / float(np.sqrt(accel))))
+
+
+def _run_noise_maps(masked_kspace, mask, sens_maps, chol, scale, accel, ky, kx, lam, calib, acs, calib_rows):
+    """The launch sequence shared by ``grappa_noise_maps`` and ``Grappa.noise_maps``: (GfactorMaps, info (b, 4))."""
+    b, t, c, h, w, _ = masked_kspace.shape
+    cal = calibration_data(masked_kspace, mask, calib, acs, calib_rows)
+    coef = None
+    if sens_maps is not None:
+        sens_maps = ops._dev(sens_maps, "sens_maps")
+        if tuple(sens_maps.shape) != (b, 1, c, h, w, 2):
+            raise ValueError(f"sens_maps shape {tuple(sens_maps.shape)} does not match k-space {tuple(masked_kspace.shape)}")
+        coef = sens_maps.clone()                                     # p = conj(S), (b, 1, c, h, w, 2); no host data: capturable
+        coef[..., 1].neg_()
+    gs, stds, infos = [], [], []
+    for i in range(b):
+        weights, info = grappa_weights(cal[i], accel, (ky, kx), lam)
+        maps = grappa_gfactor_from_weights(weights, accel, (ky, kx), h, w, chol, None if coef is None else coef[i], scale)
+        gs.append(maps.g if coef is None else maps.g[0])
+        stds.append(maps.std if coef is None else maps.std[0])
+        infos.append(info)
+    return GfactorMaps(torch.stack(gs), torch.stack(stds)), torch.stack(infos)
+
+
+def grappa_noise_maps(masked_kspace: torch.Tensor, mask: torch.Tensor, accel: int, kernel=(2, 5), lam: float = 1e-4, calib: str = "auto",
+                      acs: Optional[Sequence[int]] = None, calib_rows: int = 32, sens_maps: Optional[torch.Tensor] = None,
+                      chol: Optional[torch.Tensor] = None, scale: float = 1.0, check: bool = True):
+    """The analytic noise maps of ``grappa(masked_kspace, mask, accel, ...)``: ``(GfactorMaps(g, std), info)``.  The kernels are fitted
+    exactly as ``grappa`` fits them (the same checks, calibration data and ``grappa_weights``, per batch element), then
+    ``grappa_gfactor_from_weights`` turns each set into maps: (b, h, w) for the combination ``sum_c conj(S_c) x_c`` with ``sens_maps``
+    (b, 1, c, h, w, 2), else per coil (b, c, h, w).  ``chol``, ``scale``: the noise, as ``noise.add_noise`` takes it.  ``info`` (b, 4)
+    and ``check`` as in ``grappa``.  The maps hold for every frame (they do not depend on a frame's lattice offset) and for the
+    lattice alone: see the module docstring for what the closed form leaves out, and ``grappa_gfactor_from_weights`` for the map of a
+    root-sum-of-squares image.  ``accel=None`` raises ``ValueError``: unevenly spaced rows are not shift-invariant."""
+    if accel is None:
+        raise ValueError("grappa_noise_maps: accel=None (unevenly spaced rows) has no analytic noise map: the reconstruction is not "
+                         "shift-invariant; noise.pseudo_replica measures one")
+    accel, ky, kx, lam = _settings(accel, kernel, lam, calib, acs, calib_rows, "magnitude", sens_maps)
+    from .classical import _no_grad_inputs
+    _no_grad_inputs("grappa_noise_maps", masked_kspace=masked_kspace, sens_maps=sens_maps, chol=chol)
+    with torch.no_grad():
+        masked_kspace, mask, (lo, hi) = _inputs("grappa_noise_maps", masked_kspace, mask, sens_maps, accel, ky, kx, calib, acs, calib_rows)
+        rows = _host_rows(mask)
+        plan_lattice(mask, accel)
+        for i in range(rows.shape[0]):
+            empty = np.flatnonzero(~rows[i, :, lo:hi].any(axis=0))
+            if empty.size:
+                raise ValueError(f"grappa_noise_maps: row {lo + int(empty[0])} of the calibration block [{lo}, {hi}) of batch element {i} was "
+                                 f"acquired by no frame")
+        maps, info = _run_noise_maps(masked_kspace, mask, sens_maps, chol, scale, accel, ky, kx, lam, calib, acs, calib_rows)
+        if check:
+            _check_residuals(info, lam)
+    return maps, info
+
+
 # ------------------------------------------------------------------ the reconstruction
 def _settings(accel, kernel, lam, calib, acs, calib_rows, output, sens_maps):
     accel, (ky, kx), lam = _accel(accel), _kernel(kernel), _lam(lam)
@@ -655,3 +793,21 @@ class Grappa(nn.Module):
                                               self.calib_rows, output)
         self.last_info = {"info": info, "offsets": offsets, "status": status}
         return res
+
+    def noise_maps(self, masked_kspace: torch.Tensor, mask: torch.Tensor, sens_maps: Optional[torch.Tensor] = None,
+                   chol: Optional[torch.Tensor] = None, scale: float = 1.0) -> GfactorMaps:
+        """The analytic noise maps of this reconstruction, ``GfactorMaps(g, std)`` as ``grappa_noise_maps`` returns them, with nothing
+        read by the host (capturable; there is no ``check``): the fit's ``info`` (b, 4) is in ``last_info``.  ``accel=None`` raises
+        ``ValueError``: unevenly spaced rows are not shift-invariant."""
+        if self.accel is None:
+            raise ValueError("Grappa.noise_maps: accel=None (unevenly spaced rows) has no analytic noise map: the reconstruction is not "
+                             "shift-invariant; noise.pseudo_replica measures one")
+        from .classical import _no_grad_inputs
+        _no_grad_inputs("Grappa.noise_maps", masked_kspace=masked_kspace, sens_maps=sens_maps, chol=chol)
+        with torch.no_grad():
+            masked_kspace, mask, _ = _inputs("Grappa.noise_maps", masked_kspace, mask, sens_maps, self.accel, self.ky, self.kx, self.calib,
+                                             self.acs, self.calib_rows)
+            maps, info = _run_noise_maps(masked_kspace, mask, sens_maps, chol, scale, self.accel, self.ky, self.kx, self.lam, self.calib,
+                                         self.acs, self.calib_rows)
+        self.last_info = {"info": info}
+        return maps

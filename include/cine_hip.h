@@ -1321,6 +1321,38 @@ int cine_grappa_gaps(const uint8_t* mask, int* gaps, int* count, int* unfilled, 
                      void* stream);
 int cine_grappa_apply_gaps(const float* in, const float* weights, const int* woff, const uint8_t* mask, const int* gaps,
                            const int* count, float* out, int t, int c, int h, int w, int cap, int kx, void* stream);
+/* The analytic noise map of the lattice reconstruction (Breuer et al., MRM 62:739, 2009).  On a zero-filled lattice z of ANY offset
+ * cine_grappa_apply is one convolution, out[q, y, x] = sum K[q, k, dy, dx] z[k, y + dy, x + dx], with the combined kernel
+ *   K[., ., 0, 0] = I;   K[q, k, -m - base + j R, dx - hx] = W[m - 1][(j, dx, k)][q],   m = 1 .. R - 1, j < ky, dx < kx
+ * (1 + (R - 1) ky distinct row offsets, kx column offsets; W as cine_grappa_weights writes it).  With the package's centred orthonormal
+ * transform, rho_y = y - h / 2, rho_x = x - w / 2 (integer division), the image-domain weights are, without any scale factor,
+ *   Wimg[q, k](y, x) = sum_{dy, dx} K[q, k, dy, dx] exp(-2 pi i (dy rho_y / h + dx rho_x / w))
+ * and ifft2c(K applied circularly to z)[q] = sum_k Wimg[q, k] ifft2c(z)[k].  With noise of covariance scale^2 Psi, Psi = L L^H, on
+ * every acquired sample (cine_noise_add), a linear combination sum_q p_q(y, x) x_q of the coil images has
+ *   amp^2 = p Wimg Psi Wimg^H p^H = sum_j |sum_{q, k} p_q Wimg[q, k] L[k, j]|^2,     std = scale sqrt(amp^2 / R)
+ * (std of the complex pixel, var_re + var_im: cine_replica_finish with pairs) and the g-factor std_accel / (std_full sqrt(R)) is
+ *   g = sqrt(amp^2 / (p Psi p^H)) / R,   0 where p Psi p^H is not positive;      per coil, p = e_q: g_q = sqrt((Wimg Psi Wimg^H)_qq / Psi_qq) / R.
+ * What the closed form leaves out: the application treats rows and columns outside the frame as zero where the formula wraps around;
+ * ACS rows and stray extra rows are kept as acquired where the formula knows the lattice only; and h need not be a multiple of R.
+ *
+ * cine_grappa_image_weights: weights (R - 1, ns, c) complex64 -> out (c, c, h, w) complex64, out[q][k][y][x] = Wimg[q, k](y, x).
+ * cine_grappa_gfactor: the fused form, Wimg is never written to memory.  chol: L (c, c) complex64, row-major, of which the lower
+ * triangle is read (noise_cholesky's), or NULL for Psi = I.  coef: p (n, c, h, w) complex64, or NULL for the c unit vectors (n is then
+ * not used but must still be >= 1).  g and amp = sqrt(amp^2): float32 (n, h, w) with coef, (c, h, w) without; either may be NULL,
+ * not both.
+ * A workgroup of 256 lanes owns 256 pixels of one row y: it contracts the row offsets with their phases into B[dx][q][k] in LDS (kx c^2
+ * complex, (R - 1) ky terms each, (m, j) ascending, on top of the identity tap), multiplies every row B[dx][q][:] by L in place, and each
+ * lane then forms sum_dx B[dx][q][j] e_x(dx) for its pixel, dx ascending, and sums over q (ascending, with coef) and the squares over j
+ * (ascending) in fp32 fmaf chains.  A phase factor is sincospif(-2 r / n) of the exactly reduced integer r = d rho mod n folded into
+ * (-n / 2, n / 2].  No atomics, a fixed order: the same bits on every call.  LDS: ((kx + 1) c (c + 1) + (R - 1) ky + c) 8 bytes, 68 KB
+ * at the limits.
+ * Limits as cine_grappa_apply: 2 <= R <= 8, ky in {2, 4}, kx in {3, 5, 7} (else CINE_EINVAL); c <= 32, ns + (R - 1) c <= 1152, h and w
+ * at most 2^20 (else CINE_EUNSUPPORTED).  A null weights / out, g and amp both null, sizes below 1, weights, chol, coef or out off
+ * their 8-byte alignment, g or amp off their 4-byte alignment, an output that overlaps an input or the other output: CINE_EINVAL.
+ * Every argument is checked before the launch; one launch, no allocation, no host read, no synchronisation: capturable. */
+int cine_grappa_image_weights(const float* weights, float* out, int c, int h, int w, int R, int ky, int kx, void* stream);
+int cine_grappa_gfactor(const float* weights, const float* chol, const float* coef, float* g, float* amp, int n, int c, int h, int w,
+                        int R, int ky, int kx, void* stream);
 /* Welford's update of (mean, m2) with the k-th sample x, k >= 1, element-wise over n floats, in float64:
  *   d = x - mean;  mean += d / k;  m2 += d * (x - mean)
  * k == 1 initialises both buffers (they are not read and need not be zeroed).  Null pointers, n <= 0, k < 1, mean == m2: CINE_EINVAL. */

@@ -3,6 +3,7 @@
 
     python tools/grappa_rate.py [--out profiles/grappa_rate.json] [--commit SHA]
     python tools/grappa_rate.py --gaps [--out profiles/grappa_gaps_rate.json] [--commit SHA]
+    python tools/grappa_rate.py --gfactor [--out profiles/grappa_gfactor_rate.json] [--commit SHA]
 
 Mask: an interleaved lattice of step 4 without ACS lines; TGRAPPA on the central 32 rows of the temporal average; lam = 1e-4.
 hipEvent medians of 10 calls each:
@@ -23,7 +24,13 @@ hipEvent medians of 10 calls each:
       the steps that occur and of the module's default steps (one Gram matrix and one solve per step), ``cine_grappa_apply_gaps`` and the whole ``grappa(accel=None)`` call (check off)
       in turn with a composed torch path -- per step the patch matrix, ``torch.linalg.solve`` and one dilated ``conv2d`` plus
       ``torch.where`` per row type -- with the peak memory of both;
-  (c) slices per second of ``Grappa(accel=None)`` through a 4-slot ``SlicePipeline``."""
+  (c) slices per second of ``Grappa(accel=None)`` through a 4-slot ``SlicePipeline``.
+
+--gfactor measures the analytic noise maps instead, same shape, kernel and lam, hipEvent medians of 10, each with its peak memory:
+  ``cine_grappa_gfactor`` per coil and with maps (p = conj(S)), white noise and with a Cholesky factor; ``cine_grappa_image_weights``;
+  a composed torch path (the combined kernel zero-padded to c^2 planes of h x w, ``torch.fft.fft2``, ``einsum`` with L and with the
+  maps); ``Grappa.noise_maps`` (calibration included); and ``noise.pseudo_replica`` of ``Grappa`` with 64 replicas under the lattice
+  mask and under the full one, which is what a measured g-factor map costs."""
 import argparse
 import json
 import os
@@ -211,14 +218,116 @@ def gaps_main(args):
             json.dump(doc, f, indent=1)
 
 
+def gfactor_main(args):
+    import numpy as np
+    from cine_hip import grappa as G, noise as N, ops, synth
+    from pipeline_rate import _stamp
+    dev = torch.device("cuda:0")
+    ex = synth.make_cine_slice(T, C, H, W, accel=4, seed=0, noise_std=0.01)
+    commit, csrc = _stamp(args.commit)
+    ns, base, hx = KY * KX * C, (KY // 2 - 1) * R, KX // 2
+    replicas = 64
+    doc = {"shape": [1, T, C, H, W], "accel": R, "kernel": [KY, KX], "lam": LAM, "calib": f"tgrappa, calib_rows={CALIB_ROWS}",
+           "device": torch.cuda.get_device_name(dev), "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "steps": STEPS,
+           "commit": commit, "csrc_sha256": csrc, "replicas": replicas}
+    with torch.no_grad():
+        full = ex["kspace"].to(dev)
+        mask = G.lattice_mask(T, H, R).to(dev)
+        ones = torch.ones_like(mask)
+        mk = ops.apply_mask(full, mask)
+        sens = ex["sens_maps"].to(dev) if "sens_maps" in ex else None
+        if sens is None:
+            sm = synth.coil_maps(C, H, W)
+            sens = torch.from_numpy(np.stack((sm.real, sm.imag), -1).astype(np.float32))[None, None].to(dev)
+        coef = sens[0].clone()
+        coef[..., 1].neg_()                                                                                   # p = conj(S), (1, c, h, w, 2)
+        rs = np.random.RandomState(0)
+        M = rs.standard_normal((C, C)) + 1j * rs.standard_normal((C, C))
+        chol = N.noise_cholesky(torch.from_numpy(M @ M.conj().T / C + np.eye(C))).to(dev)
+        cal = G.calibration_data(mk, mask, "tgrappa", None, CALIB_ROWS)
+        weights, _ = G.grappa_weights(cal[0], R, (KY, KX), LAM)
+        model = G.Grappa(accel=R, kernel=(KY, KX), lam=LAM, calib="tgrappa", calib_rows=CALIB_ROWS).eval()
+
+        def composed(low, p):
+            wc = torch.view_as_complex(weights).reshape(R - 1, KY, KX, C, C)                                  # (m - 1, j, dx, k, q)
+            kpad = torch.zeros(C, C, H, W, dtype=torch.complex64, device=dev)
+            kpad[:, :, 0, 0] = torch.eye(C, dtype=torch.complex64, device=dev)
+            for m in range(1, R):
+                for j in range(KY):
+                    for dx in range(KX):
+                        kpad[:, :, (-m - base + j * R) % H, (dx - hx) % W] = wc[m - 1, j, dx].transpose(0, 1)
+            wimg = torch.fft.fftshift(torch.fft.fft2(kpad), dim=(-2, -1))
+            lc = torch.eye(C, dtype=torch.complex64, device=dev) if low is None else torch.view_as_complex(low.contiguous()).tril()
+            if p is None:
+                t_ = torch.einsum("qkyx,kj->qjyx", wimg, lc)
+                den = (lc.abs() ** 2).sum(1)[:, None, None]
+            else:
+                pc = torch.view_as_complex(p)
+                t_ = torch.einsum("nqyx,qkyx,kj->njyx", pc, wimg, lc)
+                den = (torch.einsum("nqyx,qj->njyx", pc, lc).abs() ** 2).sum(1)
+            amp2 = (t_.abs() ** 2).sum(1)
+            return torch.sqrt(amp2 / den) / R, torch.sqrt(amp2)
+
+        low = torch.view_as_real(chol).contiguous()
+        fused = G.grappa_gfactor_from_weights(weights, R, (KY, KX), H, W, chol=chol, coef=coef)
+        g_c, _ = composed(low, coef)
+        doc["fused_vs_composed_max_rel_g"] = float(((fused.g - g_c).abs() / g_c).max())
+        doc["g_maps"] = {"min": float(fused.g.min()), "median": float(fused.g.median()), "max": float(fused.g.max())}
+        del g_c, fused
+        from cine_hip._lib import lib
+        g_pc, a_pc = torch.empty(C, H, W, device=dev), torch.empty(C, H, W, device=dev)
+        g_m, a_m = torch.empty(1, H, W, device=dev), torch.empty(1, H, W, device=dev)
+        wp, lp, cp, st = weights.data_ptr(), low.data_ptr(), coef.data_ptr(), ops._stream
+
+        def entry(l_ptr, c_ptr, g_t, a_t):                                                                    # the C entry alone, outputs in place
+            return lambda: lib().cine_grappa_gfactor(wp, l_ptr, c_ptr, g_t.data_ptr(), a_t.data_ptr(), 1, C, H, W, R, KY, KX, st())
+        parts = {
+            "entry_gfactor_per_coil": entry(None, None, g_pc, a_pc),
+            "entry_gfactor_per_coil_chol": entry(lp, None, g_pc, a_pc),
+            "entry_gfactor_maps": entry(None, cp, g_m, a_m),
+            "entry_gfactor_maps_chol": entry(lp, cp, g_m, a_m),
+            "cine_grappa_gfactor_per_coil": lambda: G.grappa_gfactor_from_weights(weights, R, (KY, KX), H, W),
+            "cine_grappa_gfactor_per_coil_chol": lambda: G.grappa_gfactor_from_weights(weights, R, (KY, KX), H, W, chol=chol),
+            "cine_grappa_gfactor_maps": lambda: G.grappa_gfactor_from_weights(weights, R, (KY, KX), H, W, coef=coef),
+            "cine_grappa_gfactor_maps_chol": lambda: G.grappa_gfactor_from_weights(weights, R, (KY, KX), H, W, chol=chol, coef=coef),
+            "cine_grappa_image_weights": lambda: G.grappa_image_weights(weights, R, (KY, KX), H, W),
+            "composed_per_coil_chol": lambda: composed(low, None),
+            "composed_maps_chol": lambda: composed(low, coef),
+            "grappa_noise_maps_with_calibration": lambda: model.noise_maps(mk, mask, sens, chol=chol),
+            "pseudo_replica_lattice": lambda: N.pseudo_replica(model, mk, mask, sens, chol=chol, replicas=replicas, output="complex"),
+            "pseudo_replica_full": lambda: N.pseudo_replica(model, full, ones, sens, chol=chol, replicas=replicas, output="complex"),
+        }
+        doc["entry_ms"], doc["peak_bytes"] = {}, {}
+        for name, fn in parts.items():
+            G.release_workspaces()
+            torch.cuda.empty_cache()
+            ms, peak = measure(fn, dev)
+            doc["entry_ms"][name], doc["peak_bytes"][name] = median(ms), peak
+            print(json.dumps({name: {"median_ms": median(ms), "peak_bytes": peak}}), flush=True)
+        e = doc["entry_ms"]
+        doc["flop_maps_chol"] = 8.0 * H * W * (C * C * KX + C * C + C * C / 2)
+        doc["composed_over_fused_maps_chol"] = e["composed_maps_chol"] / e["cine_grappa_gfactor_maps_chol"]
+        doc["composed_over_fused_per_coil_chol"] = e["composed_per_coil_chol"] / e["cine_grappa_gfactor_per_coil_chol"]
+        doc["measured_g_map_over_analytic"] = (e["pseudo_replica_lattice"] + e["pseudo_replica_full"]) / e["grappa_noise_maps_with_calibration"]
+        print(json.dumps({k: doc[k] for k in ("composed_over_fused_maps_chol", "composed_over_fused_per_coil_chol", "measured_g_map_over_analytic",
+                                              "fused_vs_composed_max_rel_g", "g_maps")}), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default=None, help="the commit to stamp the result with (default: git rev-parse HEAD)")
     ap.add_argument("--gaps", action="store_true", help="measure the path for unevenly spaced rows (accel=None)")
+    ap.add_argument("--gfactor", action="store_true", help="measure the analytic noise maps (cine_grappa_gfactor, cine_grappa_image_weights)")
     args = ap.parse_args()
     if args.gaps:
         return gaps_main(args)
+    if args.gfactor:
+        return gfactor_main(args)
     from cine_hip import grappa as G, ops, synth
     from cine_hip._lib import lib
     from cine_hip.pipeline import SlicePipeline
